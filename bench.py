@@ -10,11 +10,23 @@ AdamW update.  Nothing is skipped or cached inside the timed region.
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
-  roofline     - the fused window-attention kernel (dhz_fused_window_attn_fwd / _fwd6), timed live with HIP events on the stream
-                 it is launched on; algorithmic work per DESIGN.md §9
-  cpu_baseline - the CPU oracle's training step timed on this node's host cores on a bounded sample
-                 (rank 0, N=1 only).
+Rank 0 prints ONE JSON line: metric, value (patches/s), unit, higher_is_better, dtype, ms_per_step (one timed step) and the
+configuration.  A plain run does nothing else: set up, warm up, time the --steps steps, print the line.  The last timed step
+starts from the seeded initial state (weights, AdamW state, random streams), restored outside the clock: the same inputs in every
+run, so what it computes differs between runs by the rounding of its fp32 atomic sums alone (earlier steps would grow that into
+different weights).
+
+  --dump-outputs DIR  after the timed steps, write what the last timed step handed back as DIR/<name>.npy (float32): the losses
+                      train_step returns and a fixed seeded sample of the parameters it updated and of their gradients
+                      (dump_outputs).  Same arguments, same inputs: two builds can be compared output for output.
+  --full              also measure everything beside the headline, appended to the same line:
+    roofline*    - per-kernel HIP-event timings in a separate pass (the fused window-attention kernel dhz_fused_window_attn_fwd /
+                   _fwd6 and the other hot kernels), with HBM traffic from two rocprofv3 --pmc child passes
+    fp32_pipe    - the same step on the fp32 matrix pipe
+    config4, config5 - BASELINE configs[3] (bf16, E=64 ps=256) and configs[4] (whole-image eval forward)
+    cpu_baseline - the CPU oracle's training step timed on this node's host cores on a bounded sample (rank 0, N=1 only)
+    exchange     - (N > 1) the exposed all-reduce wait and the step without overlap
+  The --no-* switches below leave out single parts of --full.
 """
 import argparse
 import json
@@ -34,6 +46,48 @@ import torch.distributed as dist  # noqa: E402
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 MFMA_F32_PEAK_TF = 157.3       # fp32-input MFMA dense peak
 MFMA_BF16_PEAK_TF = 2500.0     # bf16 MFMA dense peak (MI355X_MICROARCH.md: ~2.5 PF dense)
+DUMP_SAMPLE = 1 << 22          # --dump-outputs: elements kept of the parameter / gradient vectors (16 MiB each in float32)
+
+
+def snapshot_state(model, opt):
+    """the model's and the optimizer's state as the seeded setup left it: flat parameters, AdamW moments, step count, buffers"""
+    f = opt._flat
+    return {"p": f["p"].clone(), "m": f["m"].clone(), "v": f["v"].clone(), "step": opt._step,
+            "buffers": [b.detach().clone() for b in model.buffers()]}
+
+
+def restore_state(model, opt, snap):
+    """back to snapshot_state(); the derived weight copies (split planes / bf16 shadow) are re-derived from the restored parameters"""
+    f = opt._flat
+    for k in ("p", "m", "v"):
+        f[k].copy_(snap[k])
+    opt._step = snap["step"]
+    with torch.no_grad():
+        for b, s in zip(model.buffers(), snap["buffers"]):
+            b.copy_(s)
+    opt.sync_shadows(force=True)
+
+
+def dump_outputs(path, model, loss, loss_rec, loss_cr):
+    """--dump-outputs: what the last timed step handed back, as float32 .npy files under `path` - the three losses of train_step
+    and the step's effect on the model: its updated parameters and the gradients they were updated with, each the concatenation
+    over the parameters that received a gradient, in registration order (independent of the optimizer's flat layout).  Vectors
+    longer than DUMP_SAMPLE are reduced to the same seeded sample of positions (sorted) on every run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    live = [p for p in model.parameters() if p.grad is not None]
+    with torch.no_grad():
+        params = torch.cat([p.detach().reshape(-1) for p in live])
+        grads = torch.cat([p.grad.reshape(-1) for p in live])
+        n = params.numel()
+        if n > DUMP_SAMPLE:
+            idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values.to(params.device)
+            params, grads = params[idx], grads[idx]
+    arrays = {"loss": loss, "loss_rec": loss_rec, "params": params, "grads": grads}
+    if loss_cr is not None:
+        arrays["loss_cr"] = loss_cr
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().reshape(-1).cpu().numpy())
 
 
 def _cpu_steps(P, params, opt, hazy, gt, vggW, w_cr, steps, warm=1):
@@ -292,14 +346,20 @@ def main():
     ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32",
                     help="storage type of the token tensors: f32 (BASELINE configs 2/3) or bf16 (config 4: --embed_dim 64 --ps 256 --batch 8)")
     ap.add_argument("--no-cr", action="store_true", help="Charbonnier only (NOT the headline config)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure everything beside it (roofline objects, fp32_pipe, config4, config5, cpu_baseline, "
+                         "N > 1 exchange diagnostics); the --no-* switches leave out single parts of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the losses, parameters and gradients of the last timed step as DIR/<name>.npy (float32; see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--bucket-mb", type=float, default=25.0, help="gradient all-reduce bucket size (N > 1)")
     ap.add_argument("--no-config4", action="store_true",
-                    help="skip the BASELINE configs[3] measurement (E=64 ps=256 bs=8 bf16) that the default configs[1] run appends as the "
+                    help="skip the BASELINE configs[3] measurement (E=64 ps=256 bs=8 bf16) that a --full configs[1] run appends as the "
                          "`config4` object")
     ap.add_argument("--no-config5", action="store_true",
-                    help="skip the BASELINE configs[4] measurement (whole-image eval forward on [1,3,1664,1664]) appended as the `config5` object")
+                    help="skip the BASELINE configs[4] measurement (whole-image eval forward on [1,3,1664,1664]) that --full appends as the "
+                         "`config5` object")
     ap.add_argument("--no-overlap", action="store_true",
                     help="N > 1 diagnostics: launch every gradient bucket's all-reduce AFTER backward instead of from the hooks (separates "
                          "'RCCL starved by the persistent compute grids' from 'RCCL slow')")
@@ -361,6 +421,7 @@ def main():
         cr = None if args.no_cr else My_CR.ContrastLoss(ablation=False).to(dev)
     target, input_ = synthetic_batch(args.batch, args.ps, seed=1234 + rank, device=dev)
     torch.manual_seed(4321 + rank)                # per-rank sampling / DropPath streams
+    initial = snapshot_state(model, opt)          # the seeded state the last timed step starts from (below)
 
     side = None
     if args.side_stream and not args.no_cr:
@@ -381,31 +442,51 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        loss, _, _ = step()
+    for _ in range(args.steps - 1):
+        step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    # The last timed step starts from the seeded initial state (model, AdamW state, sampling / DropPath streams), restored
+    # outside the clock: the weight gradients and the loss sums accumulate with fp32 atomics, whose order varies from run to
+    # run, and over the earlier steps AdamW grows those last-bit differences into different weights.  So that one step has the
+    # same inputs in every run and what it computes (--dump-outputs, loss_last_step) differs by rounding alone.
+    restore_state(model, opt, initial)
+    torch.manual_seed(4321 + rank)
+    torch.cuda.synchronize()
+    if world > 1:
+        dist.barrier()
+    t1 = time.perf_counter()
+    step_out = step()
+    torch.cuda.synchronize()
+    if world > 1:
+        dist.barrier()
+    elapsed += time.perf_counter() - t1
+    loss = step_out[0]
     if world > 1:
         tmax = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = tmax.item()
+    if args.dump_outputs and rank == 0:
+        # before anything else runs a step: what the last timed step computed and left
+        dump_outputs(args.dump_outputs, model, *step_out)
 
+    # everything below up to the JSON line measures beside the headline: --full only
     # per-kernel HIP-event timing for the roofline objects: a SEPARATE pass of the same step after the timed region (the
     # product path records no events; ~180 event records per step would be work the timed steps do not do)
     timing = None
-    if not args.no_kernel_timing and rank == 0:
-        ops.KERNEL_TIMING = {"dhz_ps_attn_fwd": [], "dhz_fused_window_attn_fwd": [], "dhz_winograd_conv3x3": [],
-                             "dhz_linear_bf16": [], "dhz_vgg_conv3x3_bf16": [], "dhz_linear_split6": [], "dhz_linear_wgrad_split": []}
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
+        if rank == 0:
+            ops.KERNEL_TIMING = {"dhz_ps_attn_fwd": [], "dhz_fused_window_attn_fwd": [], "dhz_winograd_conv3x3": [],
+                                 "dhz_linear_bf16": [], "dhz_vgg_conv3x3_bf16": [], "dhz_linear_split6": [], "dhz_linear_wgrad_split": []}
         for _ in range(min(args.steps, 5)):
             step()                                # every rank runs it (the step holds a collective)
         torch.cuda.synchronize()
-    timing = ops.KERNEL_TIMING
-    ops.KERNEL_TIMING = None
+        timing = ops.KERNEL_TIMING
+        ops.KERNEL_TIMING = None
     exchange_diag = None
-    if reducer is not None:
+    if reducer is not None and args.full:
         # N > 1 self-diagnosis (the 8-GPU run is the driver's, not the builder's): (a) how long the compute stream sits in
         # reducer.wait() per step - the exchange time NOT hidden behind the backward pass; (b) the same step with every bucket
         # launched after backward (no overlap at all).  (a) near 0 and (b) - headline near the ring time: the overlap works;
@@ -435,7 +516,7 @@ def main():
                          "steps": n_diag, "how": "HIP events around the joins of GradReducer.wait() on the compute stream (max over ranks); "
                                                  "then the same step with every bucket's all-reduce launched after backward"}
     fp32_pipe = None
-    if headline_terms and not args.no_fp32_pipe:
+    if headline_terms and args.full and not args.no_fp32_pipe:
         # the same model / optimizer state / batch with every product on the fp32 matrix pipe (v_mfma_f32_16x16x4_f32)
         ops.SPLIT_BF16 = 0
         for _ in range(min(args.warmup, 5)):
@@ -466,7 +547,7 @@ def main():
         # `roofline.traffic` - two profiler child processes on the same GPU - run after the last of them
         plan = reducer.plan() if reducer is not None else None
         reserve = reducer.reserve_cus if reducer is not None else None
-        if world == 1 and not args.no_config4 and (args.dtype, args.embed_dim, args.ps, args.batch) == ("f32", 32, 128, 32) \
+        if args.full and world == 1 and not args.no_config4 and (args.dtype, args.embed_dim, args.ps, args.batch) == ("f32", 32, 128, 32) \
                 and not args.no_cr:
             # on the same clock: free the config-2 state first
             model = opt = cr = reducer = None
@@ -479,7 +560,7 @@ def main():
                 torch.cuda.empty_cache()
                 torch.cuda.reset_peak_memory_stats(dev)
                 extras["config5"] = run_config5(dev)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             extras["cpu_baseline"] = cpu_baseline()
         total = args.batch * world * args.steps
         out = {
@@ -512,7 +593,7 @@ def main():
                                "measured": "ring time is the plan's figure, not a measurement",
                                **(exchange_diag or {})}
         build_id = _lib.load().dhz_build_id().decode()
-        pmc, traffic_source = load_pmc_traffic(os.path.join(ROOT, "profiles", "pmc_traffic.json"), build_id)
+        pmc, traffic_source = load_pmc_traffic(os.path.join(ROOT, "profiles", "pmc_traffic.json"), build_id) if timing else ({}, None)
         if world == 1 and timing and not args.no_live_traffic and args.dtype == "f32":
             extra = ["--batch", str(args.batch), "--embed_dim", str(args.embed_dim), "--ps", str(args.ps)] + (["--no-cr"] if args.no_cr else [])
             live, why = live_pmc_traffic(extra)

@@ -15,6 +15,7 @@ Harness shims (none of them is product code):
   * nn.Module.cuda -> identity (My_CR.py:94 hard-codes .cuda())
 
 usage:  python tests/golden/gen_golden.py
+        python tests/golden/gen_golden.py --only init_stats     (the sd_stats arrays of the init-stream fixtures alone)
 """
 import hashlib
 import os
@@ -22,9 +23,13 @@ import random
 import sys
 import types
 
-import numpy as np
-import torch
-import torch.nn as nn
+# trunc_normal_'s erfinv_ runs in MKL, whose default code path differs between CPU vendors (Intel hosts take the AVX-512 one):
+# fixtures are made on MKL's vendor-independent path, which tests/test_host.py pins the same way when it recomputes sd_stats
+os.environ["MKL_CBWR"] = "COMPATIBLE"
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+import torch.nn as nn  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REF = "/root/reference/Uformer_ProbSparse"
@@ -410,6 +415,31 @@ def gen_dead_branches(M1):
     npz("dead_branches", **out)
 
 
+def gen_init_stats(M1, M0):
+    """the sd_stats arrays of the init-stream fixtures alone (tests/test_host.py), written into the existing files with the same
+    seeds and constructors as gen_full / gen_full_ctor_default / gen_dead_branches; every other array is left as it is"""
+    def stats(model):
+        return np.array([[float(v.double().sum()), float(v.double().abs().sum())] for v in model.state_dict().values()])
+
+    def update(name, **arrays):
+        with np.load(os.path.join(HERE, name + ".npz"), allow_pickle=False) as f:
+            old = {k: f[k] for k in f.files}
+        old.update(arrays)
+        npz(name, **old)
+
+    for modname, MM in (("m1", M1), ("m0", M0)):
+        seed_all(1234)
+        update(f"full_{modname}_e32", sd_stats=stats(MM.Uformer(img_size=128, embed_dim=32, win_size=8, token_projection='linear',
+                                                                token_mlp='leff')))
+    seed_all(1234)
+    update("full_m1_ctor_default", sd_stats=stats(M1.Uformer()))
+    out = {}
+    for tag, kw in (("conv_se", dict(token_projection='conv', se_layer=True)), ("concat", dict(token_projection='linear_concat'))):
+        seed_all(1234)
+        out[tag + "/sd_stats"] = stats(M1.Uformer(img_size=128, embed_dim=32, win_size=8, token_mlp='leff', **kw))
+    update("dead_branches", **out)
+
+
 def gen_trajectory(M1, losses):
     seed_all(1234)
     model = M1.Uformer(img_size=128, embed_dim=32, win_size=8, token_projection='linear', token_mlp='leff')
@@ -559,6 +589,15 @@ def main():
         gen_full_e16(M1, losses)
         gen_full_ctor_default(M1, losses)
         gen_dead_branches(M1)
+        return
+    if len(sys.argv) > 2 and sys.argv[1] == "--only" and sys.argv[2] == "init_stats":
+        install_shims()
+        import warnings
+        warnings.filterwarnings("ignore")
+        import My_model_1 as M1
+        import My_model as M0
+        torch.set_num_threads(8)
+        gen_init_stats(M1, M0)
         return
     if len(sys.argv) > 2 and sys.argv[1] == "--only" and sys.argv[2] == "block128":
         install_shims()

@@ -28,5 +28,5 @@ python tools/pmc_summary.py $(ls $O/p_fetch/*/*counter_collection.csv | head -1)
     --filter "ps_attn|fused_window|winograd|linear_wgrad|linear_gemm|split6|gemm_split|wgrad_split|conv_gemm|conv_wgrad|leff|ln_partition|reverse_residual|charbonnier|adamw|bias_|maxpool|l1_pair|blocked|crop|thin_conv|conv3x3_in3" \
     > $O/${N}_pmc_traffic.txt
 rm -rf $O/p_*
-python bench.py $BENCH_ARGS > $O/${N}_bench_line.json
+python bench.py --full $BENCH_ARGS > $O/${N}_bench_line.json
 cut -c1-200 $O/${N}_bench_line.json
