@@ -860,7 +860,7 @@ extern "C" int dhz_leff_dwconv_bwd_scaled_dt(const void* dz, const void* u, cons
     const int tiles_x = (Wres + TW - 1) / TW, tiles_y = (Hres + TH - 1) / TH;
     const int lpp = dw_lanes_per_position(DW_BWD_LPP, Ch);
     const int ntiles = B * tiles_x * tiles_y, ncg = Ch / (4 * lpp);
-    int wg_per_cg = (lpp == 16 ? 512 : 256 * DWB_WAVES) / ncg;   // one resident round: 3 (2 at 512 threads) workgroups per CU, persistent over tiles
+    int wg_per_cg = (lpp == 16 ? 2 : DWB_WAVES) * dhz_num_cus() / ncg;   // one resident round: 3 (2 at 512 threads) workgroups per CU, persistent over tiles
     if (wg_per_cg < 1) wg_per_cg = 1;
     if (wg_per_cg > ntiles) wg_per_cg = ntiles;
 #define DW_BWD(LPP_) hipLaunchKernelGGL((leff_dwconv_bwd_kernel<T, LPP_>), dim3(wg_per_cg * ncg), dim3(32 * LPP_), 0, (hipStream_t)stream,   \

@@ -21,6 +21,7 @@
 namespace {
 
 constexpr int NT = 64, NU = 25, SS = 68, DS = 36, C = 32;
+static_assert(NU + 1 + 4 <= 32, "the four waves' partials of the unselected sum sit in spare dO rows");
 
 __device__ __forceinline__ float row8_max(float v) {
     v = fmaxf(v, __shfl_xor(v, 1));
@@ -74,7 +75,7 @@ struct BwdSmem {
     float k[NT * DS];        // K; later dK; at the very end the dxn staging rows (wave-private)
     float v[NT * DS];        // V; later dV
     float qr[32 * DS];       // Q[top] rows (25 live)                 } later, contiguous: xn rows [64][DS]
-    float dor[32 * DS];      // dO[top] rows, row 25 = unselected sum  }
+    float dor[32 * DS];      // dO[top] rows, row 25 = unselected sum (rows 26..29: its per-wave partials, transiently)  }
     float p1[32 * SS];       // selected scores -> P1; later dQ[top] (32 x DS)
     float p2[32 * SS];       // P2; later dA                           } later, contiguous from p2: dy rows [64][DS]
     float dsb[32 * SS];      // dP2 -> dS                              }
@@ -255,9 +256,16 @@ __global__ __launch_bounds__(256, 2) void fused_window_attn_bwd_c32_kernel(
                 else { us0 += dacc[0][r]; us1 += dacc[1][r]; }
             }
             us0 = tok4sum(us0); us1 = tok4sum(us1);
-            if (g == 0) { atomicAdd(&sm.dor[NU * DS + i16], us0); atomicAdd(&sm.dor[NU * DS + 16 + i16], us1); }
+            // each wave's partial of the unselected sum into its own spare row (NU + 1 + w, zeroed at S0): summed in wave order below,
+            // so the sum does not depend on the order in which the waves arrive
+            if (g == 0) { sm.dor[(NU + 1 + w) * DS + i16] = us0; sm.dor[(NU + 1 + w) * DS + 16 + i16] = us1; }
         }
         __syncthreads();                                  // S2
+        if (t < C) {                                      // row NU = the four partials in a fixed order; the spare rows back to zero
+            float* col = sm.dor + NU * DS + t;
+            col[0] = ((col[DS] + col[2 * DS]) + col[3 * DS]) + col[4 * DS];
+            col[DS] = 0.f; col[2 * DS] = 0.f; col[3 * DS] = 0.f; col[4 * DS] = 0.f;
+        }                                                 // (read first in phase D, behind S3)
         // ---- C. scores of the selected rows: Sr = Q[top] K^T (32 x 64), two tiles per wave
         {
             const int tr = w & 1;

@@ -330,7 +330,7 @@ static int wgrad_dispatch(const char* who, const float* dy, int ldy, const float
 #endif
     const int bm = 32 * wm, bn = 32 * wn;
     const int tiles = (N / bm) * (K / bn);
-    const int splits2 = 256 / tiles > 0 ? 256 / tiles : 1;
+    const int splits2 = dhz_num_cus() / tiles > 0 ? dhz_num_cus() / tiles : 1;
     const bool two = tg_env ? tg_env == 2 : (T / TK) / splits2 >= 8;
 #define CASE(a, b)                                                               \
     if (wm == a && wn == b) {                                                    \

@@ -708,7 +708,7 @@ static int ps_attn_fwd_t(const T* q, const T* k, const T* v, int ld, const uint8
     DHZ_REQUIRE(!mask || (nW > 0 && B_ % nW == 0), "dhz_ps_attn_fwd: B_=%d not a multiple of nW=%d", B_, nW);
     hipStream_t s = (hipStream_t)stream;
     // persistent workgroups, three per CU (LDS: 36.3 KiB at d = 32, 52.7 KiB at d = 64)
-    const int resident = 256 * (d == 32 ? PSF_WG32 : PSF_WG64);
+    const int resident = (d == 32 ? PSF_WG32 : PSF_WG64) * dhz_num_cus();
     const int grid = B_ * H < resident ? B_ * H : resident;
     if (d == 16) {                                 // embed_dim 16 ("Uformer16", utils/model_utils.py:96-98): four MFMA k-steps per score tile
         hipLaunchKernelGGL((ps_attn_fwd_kernel<16, T>), dim3(grid), dim3(256), sizeof(FwdSmem<16>), s, q, k, v, ld, idx,
