@@ -17,7 +17,7 @@ import torch
 from torch.autograd import Function
 
 from . import _lib, ops
-from .ops import NTOK, _p, _require_gpu, _stream
+from .ops import NTOK, _grad_buf, _int_array, _p, _ptr_array, _ready, _require_gpu, _stream
 
 SUPPORTED_C = (32, 64, 128)
 ENABLED = True      # set False to force the unfused chain (tests compare the two)
@@ -51,56 +51,8 @@ LEFF_FUSED_P6_C = (64,)
 
 
 def _wgrad(dy, off, x, w, b, row_scale=None):
-    """dW/db of one Linear from dy[:, off:off+N] and x.  In place into .grad when the parameter is a leaf and
-    the split-T kernel is the better choice; returns (dw, db) to hand to autograd, or (None, None)."""
-    T, K = x.shape
-    N = w.shape[0]
-    if not w.requires_grad and (b is None or not b.requires_grad):
-        return None, None                                   # frozen Linear: nothing to compute
-    q = 64 if dy.dtype == ops.BF16 else 16                  # fp32: 16-wide tiles for the embed_dim = 16 model (csrc/linear_wgrad.hip)
-    mine = T % 32 == 0 and N % q == 0 and K % q == 0        # (the kernel's shape contract; always true on this model)
-    if mine and w.is_leaf and w.requires_grad and (b is None or (b.is_leaf and b.requires_grad)):
-        ops._accumulate_param_grads(dy, off, x, [(w, b)], row_scale)
-        return None, None
-    if mine:
-        fp = w.dtype == torch.float32
-        dw = ops.zeros_f32(tuple(w.shape), w.device) if fp else torch.zeros_like(w, memory_format=torch.contiguous_format)
-        db = (ops.zeros_f32(tuple(b.shape), b.device) if fp else torch.zeros_like(b)) if b is not None else None
-        ops.wgrad_into(dy, off, x, N, dw, db, row_scale)
-        return dw, db
-    raise RuntimeError(f"dehaze_hip: Linear weight gradient for T={T}, N={N}, K={K}: the HIP kernel needs multiples of 16 "
-                       "(there is deliberately no library fallback)")
-
-
-def _wgrad_qkv(dqkv, xn, C, pairs):
-    """The three projections' gradients from the packed dqkv [T,3C]: one launch (x read once) when all of them can be
-    accumulated in place, else one _wgrad each.  Returns the six autograd slots (g_wq, g_bq, g_wk, g_bk, g_wv, g_bv)."""
-    T, K = xn.shape
-    q = 64 if dqkv.dtype == ops.BF16 else 16
-    if T % 32 == 0 and C % q == 0 and K % q == 0 and all(w.is_leaf and w.requires_grad and (b is None or (b.is_leaf and b.requires_grad))
-                                                           for w, b in pairs):
-        ops._accumulate_param_grads(dqkv, 0, xn, pairs)
-        return (None,) * 6
-    out = ()
-    for i, (w, b) in enumerate(pairs):
-        out += _wgrad(dqkv, i * C, xn, w, b)
-    return out
-
-
-def _grad_buf(p):
-    """Zero-initialised, contiguous .grad of a leaf parameter (the optimizer's flat-buffer view when FlatAdamW is in
-    use), or None when in-place accumulation is not possible."""
-    if not (p.is_leaf and p.requires_grad):
-        return None
-    if p.grad is None:
-        p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
-    return p.grad if p.grad.is_contiguous() else None
-
-
-def _ready(*params):
-    if ops.GRAD_READY is not None:
-        for p in params:
-            ops.GRAD_READY(p)
+    """(dw, db) of one Linear from dy[:, off:off+N] and x: the autograd slots of ops.linear_wgrad"""
+    return ops.linear_wgrad(dy, off, x, [(w, b)], row_scale)
 
 
 def _ln_backward(dxn, x, gamma_p, beta_p, gamma, stats, dres, B, Hres, Wres, C, shift, partition, dres_windowed=False, dx_window=None,
@@ -146,11 +98,9 @@ _PENDING_TABLES = []
 
 
 def _flush_table_grads():
-    import ctypes
     pend = list(_PENDING_TABLES)
     _PENDING_TABLES.clear()
-    arr = lambda ptrs: ctypes.cast((ctypes.c_void_p * len(ptrs))(*ptrs), ctypes.c_void_p)
-    ints = lambda v: ctypes.cast((ctypes.c_int * len(v))(*v), ctypes.c_void_p)
+    arr, ints = _ptr_array, _int_array
     for i0 in range(0, len(pend), 32):
         part = pend[i0: i0 + 32]
         _lib.call("dhz_bias_table_grad_multi", arr([_p(d) for d, _, _, _ in part]), ints([n for _, n, _, _ in part]),
@@ -187,7 +137,6 @@ def _table_backward(dpart, parts, table_p, H, dev):
 STAGED_BIAS = {}        # id(table parameter) -> [H, 64, 64]
 STAGED_PREPACK = {}     # id(query weight)    -> (wqkv_p, wo_p)
 STAGED_PACK6 = {}       # id(query weight)    -> six-term planes of Q / K / V / out-projection for the fused attention kernel
-STAGED_LEFF6 = {}       # id(linear1 weight)  -> six-term planes of linear1 / linear2 for the fused LeFF kernel
 
 
 def _n6(C):
@@ -198,13 +147,11 @@ def _n6(C):
 
 def stage_block_operands(entries, device):
     """entries: [(table or None, H, (wq, wk, wv, wo) or None, C)] in execution order (Uformer.forward builds it)."""
-    import ctypes
     STAGED_BIAS.clear()
     STAGED_PREPACK.clear()
     STAGED_PACK6.clear()
-    STAGED_LEFF6.clear()
     _PENDING_TABLES.clear()          # (a backward pass that died before its end-of-pass callback)
-    arr = lambda ptrs: ctypes.cast((ctypes.c_void_p * len(ptrs))(*ptrs), ctypes.c_void_p)
+    arr, ints = _ptr_array, _int_array
     tabs = [(t, H) for t, H, _, _ in entries if t is not None]
     if tabs:
         flat = torch.empty((sum(H for _, H in tabs) * NTOK * NTOK,), device=device, dtype=torch.float32)
@@ -216,7 +163,7 @@ def stage_block_operands(entries, device):
             part = list(zip(tabs, outs))[i0: i0 + 32]
             tcs = [t.contiguous() for (t, _), _ in part]
             _lib.call("dhz_bias_gather_multi", arr([_p(t) for t in tcs]), arr([_p(o) for _, o in part]),
-                      ctypes.cast((ctypes.c_int * len(part))(*[H for (_, H), _ in part]), ctypes.c_void_p), len(part), _stream())
+                      ints([H for (_, H), _ in part]), len(part), _stream())
         for (t, _), o in zip(tabs, outs):
             STAGED_BIAS[id(t)] = (t, o)          # (the parameter itself rides along: its id cannot be reused while the entry lives)
     p6 = lambda C: ATTN_FUSED_P6 and C in ATTN_FUSED_P6_C
@@ -232,7 +179,7 @@ def stage_block_operands(entries, device):
             part = list(zip(packs6, outs))[i0: i0 + 16]
             ws = [[_p(w[k].contiguous()) for (w, _), _ in part] for k in range(4)]
             _lib.call("dhz_fused_attn_prepack6_multi", arr(ws[0]), arr(ws[1]), arr(ws[2]), arr(ws[3]), arr([_p(o) for _, o in part]),
-                      ctypes.cast((ctypes.c_int * len(part))(*[C for (_, C), _ in part]), ctypes.c_void_p), len(part), _stream())
+                      ints([C for (_, C), _ in part]), len(part), _stream())
         for (w, _), o in zip(packs6, outs):
             STAGED_PACK6[id(w[0])] = (w[0], o)
     packs = [(w, C) for _, _, w, C in entries if w is not None and (not p6(C) or C in (32, 128))]     # (C = 128: the out-projection's fp32 pack too; C = 32: the fused backward's)
@@ -246,7 +193,7 @@ def stage_block_operands(entries, device):
             part = list(zip(packs, outs))[i0: i0 + 16]
             ws = [[_p(w[k].contiguous()) for (w, _), _ in part] for k in range(4)]
             _lib.call("dhz_fused_attn_prepack_multi", arr(ws[0]), arr(ws[1]), arr(ws[2]), arr(ws[3]), arr([_p(o[0]) for _, o in part]),
-                      arr([_p(o[1]) for _, o in part]), ctypes.cast((ctypes.c_int * len(part))(*[C for (_, C), _ in part]), ctypes.c_void_p),
+                      arr([_p(o[1]) for _, o in part]), ints([C for (_, C), _ in part]),
                       len(part), _stream())
         for (w, _), o in zip(packs, outs):
             STAGED_PREPACK[id(w[0])] = (w[0], o)
@@ -309,16 +256,11 @@ def _attn_fused_fwd(train, x, gamma, beta, wq, bq, wk, bk, wv, bv, wo, bo, table
             stats = torch.empty((T, 2), **f32)
         rank = torch.empty(((T // NTOK) * H * NTOK,), device=dev, dtype=torch.uint8)
     entry = "dhz_fused_window_attn_fwd6" if use6 else "dhz_fused_window_attn_fwd"
-    timing = ops.KERNEL_TIMING.get("dhz_fused_window_attn_fwd") if ops.KERNEL_TIMING is not None else None
-    if timing is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    ev = ops._timed("dhz_fused_window_attn_fwd")
     _lib.call(entry, _p(x), _p(gamma), _p(beta), _p(wqkv_p), _p(bqkv), _p(wo_p), _p(bo), _p(idx),
               _p(bias), _p(mask), _p(dscale), _p(out), _p(xn), _p(qkv), _p(cx), _p(stats), _p(rank), B, Hres, Wres, C,
               shift, _stream())
-    if timing is not None:
-        e1.record()
-        timing.append((e0, e1, T // NTOK, C))
+    ops._timed_end(ev, T // NTOK, C)
     rec = None
     params = (wq, bq, wk, bk, wv, bv, wo, bo, gamma, beta, table)
     geom = (B, Hres, Wres, C, shift, H)
@@ -349,18 +291,7 @@ def _attn_chain_fwd(train, x, gamma, beta, wq, bq, wk, bk, wv, bv, wo, bo, table
     bias = _bias_tile(table, H, dev)
     cx = torch.empty((T, C), device=dev, dtype=x.dtype)
     rank = torch.empty(((T // NTOK) * H * NTOK,), device=dev, dtype=torch.uint8)
-    nW = mask.shape[0] if mask is not None else 1
-    base = qkv.data_ptr()
-    timing = ops.KERNEL_TIMING.get("dhz_ps_attn_fwd") if ops.KERNEL_TIMING is not None else None
-    if timing is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    es = qkv.element_size()
-    _lib.call("dhz_ps_attn_fwd_dt", base, base + es * C, base + 2 * es * C, 3 * C, _p(idx), _p(bias), _p(mask), _p(cx), C,
-              _p(rank), T // NTOK, H, nW, d, ops._dt(qkv), _stream())
-    if timing is not None:
-        e1.record()
-        timing.append((e0, e1, (T // NTOK) * H * 4 * NTOK * d * qkv.element_size()))
+    ops.ps_attn_fwd_launch(qkv, idx, bias, mask, cx, rank, T // NTOK, H, d)
     out = ops.gemm_fwd_res(cx, wo, bo, x.view(T, C), dscale, B, Hres, Wres, shift, True).view(B, L, C)
     rec = None
     if train:
@@ -434,15 +365,11 @@ def _attn_bwd(rec, dout, windowed=False, daw_pre=None):
     dqkv = torch.empty_like(qkv)
     parts = _lib.load().dhz_ps_attn_bwd_parts_d(B_, H, d)
     dpart = torch.empty((parts, NTOK, NTOK), **f32) if bias is not None else None
-    nW = mask.shape[0] if mask is not None else 1
-    base, gb = qkv.data_ptr(), dqkv.data_ptr()
-    es = qkv.element_size()
-    _lib.call("dhz_ps_attn_bwd_dt", base, base + es * C, base + 2 * es * C, 3 * C, _p(bias), _p(mask), _p(rank), _p(dctx), C,
-              gb, gb + es * C, gb + 2 * es * C, 3 * C, _p(dpart), B_, H, nW, d, ops._dt(qkv), _stream())
+    ops.ps_attn_bwd_launch(qkv, dqkv, bias, mask, rank, dctx, dpart, B_, H, d)
     dtable = _table_backward(dpart, parts, table_p, H, dev) if bias is not None else None
     # (4) QKV projection
     dxn = ops.gemm_dgrad(dqkv, ops.cat_rows([wq_.detach(), wk_.detach(), wv_.detach()]))
-    g_wq, g_bq, g_wk, g_bk, g_wv, g_bv = _wgrad_qkv(dqkv, xn, C, [(wq, bq), (wk, bk), (wv, bv)])
+    g_wq, g_bq, g_wk, g_bk, g_wv, g_bv = ops.linear_wgrad(dqkv, 0, xn, [(wq, bq), (wk, bk), (wv, bv)])      # one launch, x read once
     # (5) LayerNorm backward + shortcut gradient in one pass
     dx, dgamma, dbeta = _ln_backward(dxn, x, gamma_p, beta_p, gamma, stats, dout, B, Hres, Wres, C, shift, 1, dres_windowed=windowed)
     return (dx, dgamma, dbeta, g_wq, g_bq, g_wk, g_bk, g_wv, g_bv, g_wo, g_bo, dtable)
@@ -454,9 +381,9 @@ def fused_c128_ok(HW):
     return HW <= ATTN_FUSED_C128_MAX_HW or not torch.is_grad_enabled()
 
 
-def _use_fused_attn(x, heads, Hres, Wres):
-    C = x.shape[-1]
-    return ENABLED and x.dtype == torch.float32 and C == 32 * heads and (C in (32, 64) or (C == 128 and fused_c128_ok(Hres * Wres)))
+def use_fused_attn(C, dtype, heads, HW):
+    """the attention branch's forward: the fused kernel (True) or the kernel chain"""
+    return ENABLED and dtype == torch.float32 and C == 32 * heads and (C in (32, 64) or (C == 128 and fused_c128_ok(HW)))
 
 
 class _AttnNode(Function):
@@ -492,7 +419,7 @@ def fused_attn_branch(x, norm, layer, table, idx, mask, dscale, Hres, Wres, shif
 def attn_branch(x, norm, layer, table, idx, mask, dscale, Hres, Wres, shift, heads):
     """Dispatch: fused kernel where it wins (measured, tools/bench_fused.py), kernel chain elsewhere."""
     q, k, v, o = layer.query_projection, layer.key_projection, layer.value_projection, layer.out_projection
-    return _AttnNode.apply(_use_fused_attn(x, heads, Hres, Wres), x, norm.weight, norm.bias, q.weight, q.bias, k.weight, k.bias, v.weight,
+    return _AttnNode.apply(use_fused_attn(x.shape[-1], x.dtype, heads, Hres * Wres), x, norm.weight, norm.bias, q.weight, q.bias, k.weight, k.bias, v.weight,
                            v.bias, o.weight, o.bias, table, idx, mask, dscale, Hres, Wres, shift, heads, torch.is_grad_enabled())
 
 
@@ -522,13 +449,9 @@ def _leff_fwd(train, x, gamma, beta, w1, b1, wd, bd, w2, b2, dscale, Hres, Wres)
             tg = torch.empty((T, Ch), **f32)
             z = torch.empty((T, Ch), **f32)
         if LEFF_FUSED_P6 and C in LEFF_FUSED_P6_C:
-            # both weight products six-term on the bf16 matrix pipe: planes in the kernel's fragment order (staged per forward, or packed here)
-            hit = STAGED_LEFF6.pop(id(w1), None)
-            if hit is not None and hit[0] is w1 and hit[1].numel() == 24 * C * C and hit[1].device == dev:
-                w6 = hit[1]
-            else:
-                w6 = torch.empty(24 * C * C, device=dev, dtype=torch.bfloat16)
-                _lib.call("dhz_leff_prepack6", _p(w1), _p(w2), _p(w6), C, _stream())
+            # both weight products six-term on the bf16 matrix pipe: planes in the kernel's fragment order
+            w6 = torch.empty(24 * C * C, device=dev, dtype=torch.bfloat16)
+            _lib.call("dhz_leff_prepack6", _p(w1), _p(w2), _p(w6), C, _stream())
             _lib.call("dhz_leff_fused_fwd6", _p(x), _p(gamma), _p(beta), _p(w6), _p(b1), _p(wdc), _p(bd), _p(b2),
                       _p(dscale), _p(out), _p(xn), _p(stats), _p(u), _p(tg), _p(z), B, Hres, Wres, C, _stream())
         else:
@@ -729,7 +652,7 @@ class _BlockNode(Function):
 def block(x, norm1, layer, table, idx, mask, dscale_attn, Hres, Wres, shift, heads, norm2, mlp, dscale_mlp):
     """both branches of a LeWin block with a LeFF token mixer as one autograd node"""
     q, k, v, o = layer.query_projection, layer.key_projection, layer.value_projection, layer.out_projection
-    return _BlockNode.apply(_use_fused_attn(x, heads, Hres, Wres), x,
+    return _BlockNode.apply(use_fused_attn(x.shape[-1], x.dtype, heads, Hres * Wres), x,
                             norm1.weight, norm1.bias, q.weight, q.bias, k.weight, k.bias, v.weight, v.bias, o.weight, o.bias, table, idx,
                             mask, dscale_attn, Hres, Wres, shift, heads,
                             norm2.weight, norm2.bias, mlp.linear1[0].weight, mlp.linear1[0].bias, mlp.dwconv[0].weight, mlp.dwconv[0].bias,

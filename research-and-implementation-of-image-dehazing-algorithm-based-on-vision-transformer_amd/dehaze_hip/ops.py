@@ -132,7 +132,7 @@ def _split_terms(v):
 
 
 SPLIT_BF16 = _split_terms(os.environ.get("DHZ_SPLIT_BF16", "6"))
-SPLIT_MIN_K = int(os.environ.get("DHZ_SPLIT_MIN_K", "128"))      # smallest contraction the forward / backward-data GEMMs split
+SPLIT_MIN_K = 128          # smallest contraction the three-term experiment splits in the forward / backward-data GEMMs
 
 
 def set_bf16_shadow(f32, b16, b16t=None, desc=None, index=None, ntiles=0):
@@ -148,16 +148,22 @@ def refresh_bf16_shadow_t():
         _lib.call("dhz_bf16_transpose_batched", sh[0].data_ptr(), sh[2].data_ptr(), sh[3].data_ptr(), sh[3].shape[0], sh[5], _stream())
 
 
+def _t_offset(sh, t, index, W):
+    """element offset of W in the flat buffer when the shadow `sh` keeps a TRANSPOSED copy of it (slot t; slot index: the registered
+    matrices), else -1.  No side effect: the route function asks this, the lookups below validate and hand out the views."""
+    if sh is None or sh[t] is None or not W.is_contiguous() or W.dim() != 2:
+        return -1
+    o = _view_of(sh[0], W)
+    return o if o >= 0 and (o, W.shape[0], W.shape[1]) in sh[index] else -1
+
+
 def bf16_copy_t(W):
     """bf16 copy of W^T ([K, N] row-major for W [N, K]) when FlatAdamW keeps one for this matrix, else None."""
-    sh = BF16_SHADOW
-    if sh is None or sh[2] is None or not W.is_contiguous() or W.dim() != 2:
-        return None
-    o = _view_of(sh[0], W)
-    if o < 0 or (o, W.shape[0], W.shape[1]) not in sh[4]:
+    o = _t_offset(BF16_SHADOW, 2, 4, W)
+    if o < 0:
         return None
     _shadow_fresh(o, W.numel())
-    return sh[2][o: o + W.numel()]
+    return BF16_SHADOW[2][o: o + W.numel()]
 
 
 def refresh_bf16_shadow():
@@ -209,15 +215,12 @@ def refresh_split_shadow():
 def split_planes_t(W):
     """(hi, mid, lo) planes of W^T ([K, N] row-major for W [N, K]) when FlatAdamW keeps them for this matrix (every Linear weight of
     the flat buffer; the adjacent Q / K / V weights as ONE packed [3C, C] matrix), else None."""
-    sh = SPLIT_SHADOW
-    if sh is None or sh[4] is None or not W.is_contiguous() or W.dim() != 2:
-        return None
-    o = _view_of(sh[0], W)
-    if o < 0 or (o, W.shape[0], W.shape[1]) not in sh[6]:
+    o = _t_offset(SPLIT_SHADOW, 4, 6, W)
+    if o < 0:
         return None
     n = W.numel()
     _shadow_fresh(o, n)
-    pt = sh[4]
+    pt = SPLIT_SHADOW[4]
     return pt[0][o: o + n], pt[1][o: o + n], pt[2][o: o + n]
 
 
@@ -238,8 +241,8 @@ def split_planes(W):
     return pl[0], pl[1], pl[2]
 
 
-_ROUTE6_FORCE = os.environ.get("DHZ_S6_ROUTE", "")
 _NO_TPLANES = bool(os.environ.get("DHZ_S6_NO_TPLANES"))       # diagnostics: backward-data through the transposed-read kernel
+RES_EPILOGUE = not os.environ.get("DHZ_NO_RES_EPILOGUE")        # A/B switch: K4 / the DropPath row factor as a pass of its own
 
 
 def _route6(T, contraction, out, dgrad):
@@ -250,10 +253,6 @@ def _route6(T, contraction, out, dgrad):
     if contraction % 32 or out % 32 or contraction < 64 or out < 64:
         return "f32"
     old_ok = contraction % 64 == 0 and out % 64 == 0
-    if _ROUTE6_FORCE == "old" and old_ok and contraction >= 128:          # diagnostics: the round-3 dispatch
-        return "old"
-    if _ROUTE6_FORCE == "old":
-        return "f32"
     new_ok = not dgrad or out % 64 == 0
     if T <= 2048 and out < 2048 and old_ok:
         return "old"
@@ -266,13 +265,49 @@ def _route6(T, contraction, out, dgrad):
     return "old" if old_ok else "f32"
 
 
+def _route(product, T, contraction, out, bf16, ld, HW=0, tplanes=False):
+    """THE answer to "which kernel takes this token-Linear product", from numbers and switches alone.
+    product: 'fwd' (y = x W^T + b), 'fwd_res' (the same with the residual epilogue over images of HW tokens), 'dgrad' (dx = dy W; the
+    contraction runs over W's rows), 'dgrad_rs' (the same with a factor per image of HW rows); bf16: storage dtype of the activations;
+    ld: their row stride; tplanes: the optimizer keeps a copy of W^T in the operand format of this dtype.  Returns
+      'bf16'     bf16 operands, fp32 accumulation                        'bf16_t'   ... the FORWARD kernel on the bf16 copy of W^T
+      'split6'   six-term, pre-split weight planes (split6_gemm.hip)     'split6_t' ... the FORWARD kernel on the planes of W^T
+      'split'    six-term, both operands split in the kernel             'split3'   the three-term experiment
+      'f32'      the fp32 matrix pipe
+      'two'      (fwd_res / dgrad_rs only) no single kernel: the plain product, then dhz_reverse_residual_*_dt."""
+    back = product in ("dgrad", "dgrad_rs")
+    fused_rows = product in ("fwd_res", "dgrad_rs")
+    t_form = back and tplanes and not _NO_TPLANES
+    if bf16:
+        if fused_rows:
+            ok = product == "fwd_res" and RES_EPILOGUE and HW % 64 == 0 and out % 64 == 0 and contraction % 64 == 0 and ld % 8 == 0
+            return "bf16" if ok else "two"
+        return "bf16_t" if t_form else "bf16"
+    if SPLIT_BF16 == 6 and ld % 4 == 0 and (not fused_rows or (RES_EPILOGUE and HW % 64 == 0)):
+        # backward-data asks two different questions: "is W^T a forward problem for the plane kernel" (it then needs no transposed
+        # fragment reads), and only if not, "which backward-data kernel"
+        r = _route6(T, contraction, out, back and not t_form)
+        if t_form:
+            return "split6_t" if r == "new" else _route(product, T, contraction, out, bf16, ld, HW, False)
+        if product == "dgrad_rs":
+            return "split" if r == "old" else "two"          # (the plane backward-data kernel has no row-factor form)
+        if r != "f32":
+            return "split6" if r == "new" else "split"
+    if fused_rows:
+        return "two"
+    if SPLIT_BF16 == 3 and contraction >= SPLIT_MIN_K and contraction % 64 == 0 and out % 64 == 0:
+        return "split3"
+    return "f32"
+
+
 def _terms():
     """3 or 6 for the split kernels (True counts as 3)"""
     return 6 if SPLIT_BF16 == 6 else 3
 
 
 def _timed(name):
-    """(list, start event) when bench.py collects HIP-event timings for this entry point, else None."""
+    """(list, start event) when bench.py collects HIP-event timings under this KERNEL_TIMING key, else None: the event is recorded on
+    the launch stream right before the kernel it brackets."""
     lst = KERNEL_TIMING.get(name) if KERNEL_TIMING is not None else None
     if lst is None:
         return None
@@ -281,151 +316,137 @@ def _timed(name):
     return lst, e0
 
 
-def _timed_end(ev, units):
+def _timed_end(ev, *tail):
+    """appends (start event, end event, *tail)"""
     if ev is not None:
         e1 = torch.cuda.Event(enable_timing=True)
         e1.record()
-        ev[0].append((ev[1], e1, units))
+        ev[0].append((ev[1], e1) + tail)
+
+
+def _ptr_array(ptrs):
+    """device-pointer list -> void** argument"""
+    return ctypes.cast((ctypes.c_void_p * len(ptrs))(*ptrs), ctypes.c_void_p)
+
+
+def _int_array(vals):
+    return ctypes.cast((ctypes.c_int * len(vals))(*vals), ctypes.c_void_p)
+
+
+# KERNEL_TIMING key and issued FLOPs per multiply-add of a route (six products per multiply-add in the six-term kernels)
+_GEMM_TIMING = {"bf16": ("dhz_linear_bf16", 2.0), "bf16_t": ("dhz_linear_bf16", 2.0), "split6": ("dhz_linear_split6", 12.0),
+                "split6_t": ("dhz_linear_split6", 12.0), "split": ("dhz_linear_split6", 12.0)}
+
+
+def _gemm(route, name, T, N, K, *args):
+    key, flops = _GEMM_TIMING.get(route, (None, 0.0))
+    ev = _timed(key)
+    _lib.call(name, *args, _stream())
+    _timed_end(ev, flops * T * N * K)
+
+
+def _weight_operand(route, W):
+    """the pointer argument(s) that stand for W on this route, and the trailing term count of the kernels that split in flight"""
+    if route in ("split6", "split6_t"):
+        return tuple(_p(pl) for pl in (split_planes(W) if route == "split6" else split_planes_t(W))), ()
+    if route in ("bf16", "bf16_t"):
+        return (_p(bf16_copy(W) if route == "bf16" else bf16_copy_t(W)),), ()
+    return (_p(W),), {"split": (6,), "split3": (3,)}.get(route, ())
 
 
 def gemm_fwd(x, W, b=None):
-    """y[T,N] = x[T,K] W[N,K]^T + b on the fp32 matrix pipe (dhz_linear_fwd).  x: rows of K contiguous floats (any row
-    stride), W contiguous."""
+    """y[T,N] = x[T,K] W[N,K]^T + b.  x: rows of K contiguous elements (any row stride)."""
     _require_gpu(x, W, b)
     T, K = x.shape
     N = W.shape[0]
     assert x.stride(1) == 1 and W.shape[1] == K
     W = W if W.is_contiguous() else W.contiguous()
     y = torch.empty((T, N), device=x.device, dtype=x.dtype)
-    if x.dtype == BF16:                     # bf16 activations x bf16 weight copy, fp32 accumulate, fp32 bias (config 4)
-        Wb = bf16_copy(W)
-        ev = _timed("dhz_linear_bf16")
-        _lib.call("dhz_linear_fwd_bf16", _p(x), x.stride(0), _p(Wb), _p(b), _p(y), N, T, N, K, _stream())
-        _timed_end(ev, 2.0 * T * N * K)
-    elif SPLIT_BF16 == 6 and x.stride(0) % 4 == 0 and _route6(T, K, N, False) != "f32":
-        if _route6(T, K, N, False) == "new":
-            hi, mid, lo = split_planes(W)
-            ev = _timed("dhz_linear_split6")
-            _lib.call("dhz_linear_fwd_split6", _p(x), x.stride(0), _p(hi), _p(mid), _p(lo), _p(b), _p(y), N, T, N, K, _stream())
-        else:
-            ev = _timed("dhz_linear_split6")
-            _lib.call("dhz_linear_fwd_split", _p(x), x.stride(0), _p(W), _p(b), _p(y), N, T, N, K, 6, _stream())
-        _timed_end(ev, 12.0 * T * N * K)                         # ISSUED bf16 FLOPs: six products per multiply-add
-    elif SPLIT_BF16 == 3 and K >= SPLIT_MIN_K and K % 64 == 0 and N % 64 == 0:      # experiment
-        _lib.call("dhz_linear_fwd_split", _p(x), x.stride(0), _p(W), _p(b), _p(y), N, T, N, K, 3, _stream())
-    else:
-        _lib.call("dhz_linear_fwd", _p(x), x.stride(0), _p(W), _p(b), _p(y), N, T, N, K, _stream())
+    route = _route("fwd", T, K, N, x.dtype == BF16, x.stride(0))
+    name = {"bf16": "dhz_linear_fwd_bf16", "split6": "dhz_linear_fwd_split6", "split": "dhz_linear_fwd_split", "split3": "dhz_linear_fwd_split",
+            "f32": "dhz_linear_fwd"}[route]
+    w, terms = _weight_operand(route, W)
+    _gemm(route, name, T, N, K, _p(x), x.stride(0), *w, _p(b), _p(y), N, T, N, K, *terms)
     return y
-
-
-RES_EPILOGUE = not os.environ.get("DHZ_NO_RES_EPILOGUE")        # A/B switch: K4 as a pass of its own (the pre-round-6 chain)
 
 
 def gemm_fwd_res(x, W, b, res, scale, B, Hres, Wres, shift, windowed):
     """out = res + scale[image] * (x W^T + b) with the rows stored at their token-order position: K4 (window reverse, un-roll,
-    DropPath factor, residual; M1:859-873) as the EPILOGUE of the out-projection / linear2 GEMM (dhz_linear_fwd_split6_res,
-    csrc/tok_epilogue.h).  x: [T, K] (window order when `windowed`, the order dhz_ln_partition_fwd writes); res: [T, N] in token
-    order; scale: [B] or None.  Shapes / arithmetic the epilogue kernels do not cover (bf16 storage, the fp32 matrix pipe) run
-    the GEMM and dhz_reverse_residual_fwd as two launches."""
+    DropPath factor, residual; M1:859-873) as the EPILOGUE of the out-projection / linear2 GEMM (csrc/tok_epilogue.h).  x: [T, K]
+    (window order when `windowed`, the order dhz_ln_partition_fwd writes); res: [T, N] in token order; scale: [B] or None.  Shapes /
+    arithmetic the epilogue kernels do not cover run the GEMM and dhz_reverse_residual_fwd as two launches."""
     _require_gpu(x, W, b, res, scale)
     T, K = x.shape
     N = W.shape[0]
     HW = Hres * Wres
-    assert x.stride(1) == 1 and W.shape[1] == K and res.is_contiguous() and T == B * HW
-    route = "f32"
-    if RES_EPILOGUE and x.dtype == torch.float32 and SPLIT_BF16 == 6 and x.stride(0) % 4 == 0 and HW % 64 == 0 and W.is_contiguous():
-        route = _route6(T, K, N, False)
-    if RES_EPILOGUE and x.dtype == BF16 and res.dtype == BF16 and HW % 64 == 0 and N % 64 == 0 and K % 64 == 0 and x.stride(0) % 8 == 0:
-        Wb = bf16_copy(W if W.is_contiguous() else W.contiguous())
-        out = torch.empty_like(res)
-        ev = _timed("dhz_linear_bf16")
-        _lib.call("dhz_linear_fwd_bf16_res", _p(x), x.stride(0), _p(Wb), _p(b), _p(res), _p(scale), _p(out), N, T, N, K, HW, Hres, Wres, shift,
-                  1 if windowed else 0, _stream())
-        _timed_end(ev, 2.0 * T * N * K)
-        return out
-    if route == "f32":
-        y = gemm_fwd(x, W, b)
-        out = torch.empty_like(res)
-        _lib.call("dhz_reverse_residual_fwd_dt", _p(y), _p(res), _p(scale), _p(out), B, Hres, Wres, N, shift, 1 if windowed else 0,
-                  _dt(res), _stream())
-        return out
+    assert x.stride(1) == 1 and W.shape[1] == K and res.is_contiguous() and T == B * HW and x.dtype == res.dtype
+    W = W if W.is_contiguous() else W.contiguous()
     out = torch.empty_like(res)
-    ev = _timed("dhz_linear_split6")
-    if route == "new":
-        hi, mid, lo = split_planes(W)
-        _lib.call("dhz_linear_fwd_split6_res", _p(x), x.stride(0), _p(hi), _p(mid), _p(lo), _p(b), _p(res), _p(scale), _p(out), N, T, N, K,
-                  HW, Hres, Wres, shift, 1 if windowed else 0, _stream())
-    else:
-        _lib.call("dhz_linear_fwd_split_res", _p(x), x.stride(0), _p(W), _p(b), _p(res), _p(scale), _p(out), N, T, N, K, HW, Hres, Wres,
-                  shift, 1 if windowed else 0, 6, _stream())
-    _timed_end(ev, 12.0 * T * N * K)
+    win = 1 if windowed else 0
+    route = _route("fwd_res", T, K, N, x.dtype == BF16, x.stride(0), HW)
+    if route == "two":
+        y = gemm_fwd(x, W, b)
+        _lib.call("dhz_reverse_residual_fwd_dt", _p(y), _p(res), _p(scale), _p(out), B, Hres, Wres, N, shift, win, _dt(res), _stream())
+        return out
+    name = {"bf16": "dhz_linear_fwd_bf16_res", "split6": "dhz_linear_fwd_split6_res", "split": "dhz_linear_fwd_split_res"}[route]
+    w, terms = _weight_operand(route, W)
+    _gemm(route, name, T, N, K, _p(x), x.stride(0), *w, _p(b), _p(res), _p(scale), _p(out), N, T, N, K, HW, Hres, Wres, shift, win, *terms)
     return out
 
 
 def gemm_dgrad(dy, W, row_scale=None):
-    """dx[T,K] = dy[T,N] W[N,K] (dhz_linear_dgrad).  row_scale = (scale[B], rows_per_image): dx rows carry the per-image factor
-    (the DropPath factor of the branch in the backward pass) - in the epilogue of the six-term kernels, a pass of its own elsewhere."""
+    """dx[T,K] = dy[T,N] W[N,K].  row_scale = (scale[B], rows_per_image): dx rows carry the per-image factor (the DropPath factor of
+    the branch in the backward pass) - in the epilogue of the six-term kernels, a pass of its own elsewhere."""
     _require_gpu(dy, W)
     T, N = dy.shape
     K = W.shape[1]
     assert dy.stride(1) == 1 and W.shape[0] == N
     W = W if W.is_contiguous() else W.contiguous()
-    if row_scale is not None:
-        sc, rows = row_scale
-        assert T % rows == 0
-        f32ok = RES_EPILOGUE and dy.dtype == torch.float32 and SPLIT_BF16 == 6 and dy.stride(0) % 4 == 0 and rows % 64 == 0
-        if f32ok and _route6(T, N, K, False) == "new" and not _NO_TPLANES and split_planes_t(W) is not None:
-            hi, mid, lo = split_planes_t(W)
-            dx = torch.empty((T, K), device=dy.device, dtype=dy.dtype)
-            ev = _timed("dhz_linear_split6")
-            _lib.call("dhz_linear_fwd_split6_res", _p(dy), dy.stride(0), _p(hi), _p(mid), _p(lo), None, None, _p(sc), _p(dx), K, T, K, N,
-                      rows, 0, 0, 0, 0, _stream())
-            _timed_end(ev, 12.0 * T * N * K)
-            return dx
-        if f32ok and _route6(T, N, K, True) == "old":
-            dx = torch.empty((T, K), device=dy.device, dtype=dy.dtype)
-            ev = _timed("dhz_linear_split6")
-            _lib.call("dhz_linear_dgrad_split_scaled", _p(dy), dy.stride(0), _p(W), _p(sc), _p(dx), K, T, N, K, rows, 6, _stream())
-            _timed_end(ev, 12.0 * T * N * K)
-            return dx
+    bf16 = dy.dtype == BF16
+    tplanes = (_t_offset(BF16_SHADOW, 2, 4, W) if bf16 else _t_offset(SPLIT_SHADOW, 4, 6, W)) >= 0
+    sc, rows = row_scale if row_scale is not None else (None, 0)
+    assert row_scale is None or T % rows == 0
+    route = _route("dgrad" if row_scale is None else "dgrad_rs", T, N, K, bf16, dy.stride(0), rows, tplanes)
+    if route == "two":
         dx = gemm_dgrad(dy, W)
         out = torch.empty_like(dx)
         _lib.call("dhz_reverse_residual_bwd_dt", _p(dx), _p(sc), _p(out), T // rows, rows, 1, K, 0, 0, _dt(dx), _stream())
         return out
     dx = torch.empty((T, K), device=dy.device, dtype=dy.dtype)
-    if dy.dtype == BF16:
-        Wt = None if _NO_TPLANES else bf16_copy_t(W)
-        ev = _timed("dhz_linear_bf16")
-        if Wt is not None:
-            # dx = dy . W = dy . (W^T)^T: the forward kernel (software-pipelined, csrc/gemm_bf16_pipe.hip) on the optimizer's bf16 copy of W^T
-            _lib.call("dhz_linear_fwd_bf16", _p(dy), dy.stride(0), Wt.data_ptr(), None, _p(dx), K, T, K, N, _stream())
+    w, terms = _weight_operand(route, W)
+    if route in ("split6_t", "bf16_t"):
+        # dx = dy . W = dy . (W^T)^T: the FORWARD kernel on the optimizer's copy of W^T - no transposed fragment reads
+        if row_scale is not None:
+            _gemm(route, "dhz_linear_fwd_split6_res", T, N, K, _p(dy), dy.stride(0), *w, None, None, _p(sc), _p(dx), K, T, K, N, rows, 0, 0, 0, 0)
         else:
-            Wb = bf16_copy(W)
-            _lib.call("dhz_linear_dgrad_bf16", _p(dy), dy.stride(0), _p(Wb), _p(dx), K, T, N, K, _stream())
-        _timed_end(ev, 2.0 * T * N * K)
-    elif SPLIT_BF16 == 6 and dy.stride(0) % 4 == 0 and _route6(T, N, K, False) == "new" and not _NO_TPLANES \
-            and split_planes_t(W) is not None:
-        # dx = dy . W = dy . (W^T)^T: the FORWARD kernel on the planes of W^T (kept by the optimizer) - no transposed fragment reads
-        hi, mid, lo = split_planes_t(W)
-        ev = _timed("dhz_linear_split6")
-        _lib.call("dhz_linear_fwd_split6", _p(dy), dy.stride(0), _p(hi), _p(mid), _p(lo), None, _p(dx), K, T, K, N, _stream())
-        _timed_end(ev, 12.0 * T * N * K)
-    elif SPLIT_BF16 == 6 and dy.stride(0) % 4 == 0 and _route6(T, N, K, True) != "f32":
-        ev = _timed("dhz_linear_split6")
-        if _route6(T, N, K, True) == "new":
-            hi, mid, lo = split_planes(W)
-            _lib.call("dhz_linear_dgrad_split6", _p(dy), dy.stride(0), _p(hi), _p(mid), _p(lo), _p(dx), K, T, N, K, _stream())
-        else:
-            _lib.call("dhz_linear_dgrad_split", _p(dy), dy.stride(0), _p(W), _p(dx), K, T, N, K, 6, _stream())
-        _timed_end(ev, 12.0 * T * N * K)
-    elif SPLIT_BF16 == 3 and N >= SPLIT_MIN_K and N % 64 == 0 and K % 64 == 0:      # experiment
-        _lib.call("dhz_linear_dgrad_split", _p(dy), dy.stride(0), _p(W), _p(dx), K, T, N, K, 3, _stream())
+            _gemm(route, "dhz_linear_fwd_split6" if route == "split6_t" else "dhz_linear_fwd_bf16", T, N, K, _p(dy), dy.stride(0), *w, None,
+                  _p(dx), K, T, K, N)
+    elif row_scale is not None:
+        _gemm(route, "dhz_linear_dgrad_split_scaled", T, N, K, _p(dy), dy.stride(0), *w, _p(sc), _p(dx), K, T, N, K, rows, *terms)
     else:
-        _lib.call("dhz_linear_dgrad", _p(dy), dy.stride(0), _p(W), _p(dx), K, T, N, K, _stream())
+        name = {"bf16": "dhz_linear_dgrad_bf16", "split6": "dhz_linear_dgrad_split6", "split": "dhz_linear_dgrad_split",
+                "split3": "dhz_linear_dgrad_split", "f32": "dhz_linear_dgrad"}[route]
+        _gemm(route, name, T, N, K, _p(dy), dy.stride(0), *w, _p(dx), K, T, N, K, *terms)
     return dx
 
 
 # ----------------------------------------------------------------------------- K3 / K7
+def ps_attn_fwd_launch(qkv, idx, bias, mask, out, rank, B_, H, d):
+    """dhz_ps_attn_fwd_dt on a packed [T, 3C] buffer (columns [Q | K | V]), inside bench.py's timing bracket"""
+    C, es, base = H * d, qkv.element_size(), qkv.data_ptr()
+    ev = _timed("dhz_ps_attn_fwd")
+    _lib.call("dhz_ps_attn_fwd_dt", base, base + es * C, base + 2 * es * C, 3 * C, _p(idx), _p(bias), _p(mask), _p(out), C, _p(rank), B_, H,
+              mask.shape[0] if mask is not None else 1, d, _dt(qkv), _stream())
+    _timed_end(ev, B_ * H * 4 * NTOK * d * es)
+
+
+def ps_attn_bwd_launch(qkv, dqkv, bias, mask, rank, dout, dpart, B_, H, d):
+    """dhz_ps_attn_bwd_dt: packed qkv / dqkv [T, 3C]"""
+    C, es, base, gb = H * d, qkv.element_size(), qkv.data_ptr(), dqkv.data_ptr()
+    _lib.call("dhz_ps_attn_bwd_dt", base, base + es * C, base + 2 * es * C, 3 * C, _p(bias), _p(mask), _p(rank), _p(dout), C,
+              gb, gb + es * C, gb + 2 * es * C, 3 * C, _p(dpart), B_, H, mask.shape[0] if mask is not None else 1, d, _dt(qkv), _stream())
+
+
 class _PSWindowAttention(Function):
     """ProbAttention.forward (ATT:287-342) on a packed QKV buffer.
 
@@ -447,36 +468,22 @@ class _PSWindowAttention(Function):
         if table is not None:
             bias = torch.empty((H, NTOK, NTOK), device=qkv.device, dtype=torch.float32)
             _lib.call("dhz_bias_gather", _p(table.contiguous()), _p(bias), H, _stream())
-        nW = mask.shape[0] if mask is not None else 1
-        base, es = qkv.data_ptr(), qkv.element_size()
-        timing = KERNEL_TIMING.get("dhz_ps_attn_fwd") if KERNEL_TIMING is not None else None
-        if timing is not None:      # HIP events on the launch stream, bracketing exactly this kernel
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        _lib.call("dhz_ps_attn_fwd_dt", base, base + es * C, base + 2 * es * C, 3 * C, _p(idx), _p(bias), _p(mask), _p(out), C,
-                  _p(rank), B_, H, nW, d, _dt(qkv), _stream())
-        if timing is not None:
-            e1.record()
-            timing.append((e0, e1, B_ * H * 4 * NTOK * d * qkv.element_size()))
+        ps_attn_fwd_launch(qkv, idx, bias, mask, out, rank, B_, H, d)
         ctx.save_for_backward(qkv, bias, mask, rank)
-        ctx.dims = (B_, H, d, nW)
+        ctx.dims = (B_, H, d)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         qkv, bias, mask, rank = ctx.saved_tensors
-        B_, H, d, nW = ctx.dims
-        C = H * d
+        B_, H, d = ctx.dims
         dout = dout.contiguous()
         dqkv = torch.empty_like(qkv)
-        lib = _lib.load()
         dpart, dtable = None, None
-        parts = lib.dhz_ps_attn_bwd_parts_d(B_, H, d)
+        parts = _lib.load().dhz_ps_attn_bwd_parts_d(B_, H, d)
         if bias is not None:
             dpart = torch.empty((parts, NTOK, NTOK), device=qkv.device, dtype=torch.float32)
-        base, gb, es = qkv.data_ptr(), dqkv.data_ptr(), qkv.element_size()
-        _lib.call("dhz_ps_attn_bwd_dt", base, base + es * C, base + 2 * es * C, 3 * C, _p(bias), _p(mask), _p(rank), _p(dout), C,
-                  gb, gb + es * C, gb + 2 * es * C, 3 * C, _p(dpart), B_, H, nW, d, _dt(qkv), _stream())
+        ps_attn_bwd_launch(qkv, dqkv, bias, mask, rank, dout, dpart, B_, H, d)
         if bias is not None:
             dtable = torch.empty((225, H), device=qkv.device, dtype=torch.float32)
             _lib.call("dhz_bias_table_grad", _p(dpart), parts, _p(dtable), H, 0, _stream())
@@ -579,97 +586,96 @@ def zeros_f32(shape, device):
     return torch.zeros(shape, device=device, dtype=torch.float32)
 
 
-def _accumulate_param_grads(dy, ldy_off, x, params, row_scale=None):
-    """dW += dy[:, off:off+N]^T x, db += colsum for every (W, b) pair, straight into .grad (zero-init).  Pairs of equal
-    shape (the Q / K / V projections) go through ONE launch that reads x once (dhz_linear_wgrad_multi).
-    row_scale = (scale[B], rows_per_scale): row t of dy counts as scale[t // rows_per_scale] * dy[t] (fp32, one pair only)."""
-    T, K = x.shape
-    for W, b in params:
-        for p in (W, b):
-            if p is not None and p.grad is None:
-                p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
-        assert W.grad.is_contiguous()
-    N = params[0][0].shape[0]
-    same = 1 < len(params) <= 4 and all(W.shape[0] == N for W, _ in params) and \
-        len({b is None for _, b in params}) == 1
-    assert row_scale is None or (dy.dtype == torch.float32 and len(params) == 1)
-    if dy.dtype == BF16:
-        # bf16 dy / x, fp32 accumulation straight into the fp32 .grad buffers; equal-shaped parameters share one launch
-        groups = [params] if (same or len(params) == 1) else [[pr] for pr in params]
-        off = ldy_off
-        for grp in groups:
-            n = len(grp)
-            Ng = grp[0][0].shape[0]
-            dws = (ctypes.c_void_p * n)(*[W.grad.data_ptr() for W, _ in grp])
-            dbs = (ctypes.c_void_p * n)(*[(b.grad.data_ptr() if b is not None else None) for _, b in grp])
-            _lib.call("dhz_linear_wgrad_bf16", dy.data_ptr() + 2 * off, dy.stride(0), _p(x), x.stride(0), T, n, Ng, K,
-                      ctypes.cast(dws, ctypes.c_void_p), ctypes.cast(dbs, ctypes.c_void_p), _stream())
-            off += n * Ng
-    elif SPLIT_BF16 and T % 64 == 0 and K % 64 == 0 and all(W.shape[0] % 64 == 0 for W, _ in params):
-        # the default fp32-class path (SPLIT_BF16 == 6): contraction over T on the bf16 pipe with split operands (csrc/linear_split.hip)
-        groups = [params] if (same or len(params) == 1) else [[pr] for pr in params]
-        off = ldy_off
-        for grp in groups:
-            n = len(grp)
-            Ng = grp[0][0].shape[0]
-            dws = (ctypes.c_void_p * n)(*[W.grad.data_ptr() for W, _ in grp])
-            dbs = (ctypes.c_void_p * n)(*[(b.grad.data_ptr() if b is not None else None) for _, b in grp])
-            ev = _timed("dhz_linear_wgrad_split")
-            _lib.call("dhz_linear_wgrad_split", dy.data_ptr() + 4 * off, dy.stride(0), _p(x), x.stride(0), T, n, Ng, K,
-                      ctypes.cast(dws, ctypes.c_void_p), ctypes.cast(dbs, ctypes.c_void_p),
-                      _p(row_scale[0]) if row_scale is not None else None, int(row_scale[1]) if row_scale is not None else 0,
-                      _terms(), _stream())
-            _timed_end(ev, 2.0 * _terms() * T * n * Ng * K)
-            off += n * Ng
-    elif same:
-        n = len(params)
-        dws = (ctypes.c_void_p * n)(*[W.grad.data_ptr() for W, _ in params])
-        dbs = (ctypes.c_void_p * n)(*[(b.grad.data_ptr() if b is not None else None) for _, b in params])
-        _lib.call("dhz_linear_wgrad_multi", dy.data_ptr() + 4 * ldy_off, dy.stride(0), _p(x), x.stride(0), T, n, N, K,
-                  ctypes.cast(dws, ctypes.c_void_p), ctypes.cast(dbs, ctypes.c_void_p), _stream())
-    else:
-        off = ldy_off
-        for W, b in params:
-            if row_scale is not None:
-                _lib.call("dhz_linear_wgrad_rs", dy.data_ptr() + 4 * off, dy.stride(0), _p(x), x.stride(0), T, W.shape[0], K,
-                          _p(W.grad), _p(b.grad) if b is not None else None, _p(row_scale[0]), int(row_scale[1]), _stream())
-            else:
-                _lib.call("dhz_linear_wgrad", dy.data_ptr() + 4 * off, dy.stride(0), _p(x), x.stride(0), T, W.shape[0], K,
-                          _p(W.grad), _p(b.grad) if b is not None else None, _stream())
-            off += W.shape[0]
+def _grad_buf(p):
+    """Zero-initialised, contiguous .grad of a leaf parameter (the optimizer's flat-buffer view when FlatAdamW is in
+    use), or None when in-place accumulation is not possible."""
+    if not (p.is_leaf and p.requires_grad):
+        return None
+    if p.grad is None:
+        p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
+    return p.grad if p.grad.is_contiguous() else None
+
+
+def _grad_pair(w, b):
+    """(.grad of w, .grad of b or None) when the gradients of a weight and its optional bias can BOTH be accumulated in place (announce
+    them with _ready afterwards), else None: the caller hands fresh tensors to autograd."""
+    gw, gb = _grad_buf(w), _grad_buf(b) if b is not None else None
+    return (gw, gb) if gw is not None and (b is None or gb is not None) else None
+
+
+def _ready(*params):
     if GRAD_READY is not None:
-        for W, b in params:
-            GRAD_READY(W)
-            if b is not None:
-                GRAD_READY(b)
+        for p in params:
+            if p is not None:
+                GRAD_READY(p)
 
 
-def wgrad_into(dy, off, x, N, dw, db, row_scale=None):
-    """dw[N,K] += dy[:, off:off+N]^T x, db += column sums (fp32 accumulators) for fp32 or bf16 dy / x."""
+def _wgrad_launch(dy, off, x, targets, row_scale):
+    """dw[N,K] += dy[:, off:off+N]^T x, db += column sums for consecutive column blocks of dy; targets: [(N, dw, db or None)], fp32
+    accumulators.  Blocks of equal width (the Q / K / V projections) share ONE launch that reads x once."""
     T, K = x.shape
-    if SPLIT_BF16 and dy.dtype == torch.float32 and T % 64 == 0 and K % 64 == 0 and N % 64 == 0:
-        dws = (ctypes.c_void_p * 1)(dw.data_ptr())
-        dbs = (ctypes.c_void_p * 1)(db.data_ptr() if db is not None else None)
-        _lib.call("dhz_linear_wgrad_split", dy.data_ptr() + 4 * off, dy.stride(0), _p(x), x.stride(0), T, 1, N, K,
-                  ctypes.cast(dws, ctypes.c_void_p), ctypes.cast(dbs, ctypes.c_void_p),
-                  _p(row_scale[0]) if row_scale is not None else None, int(row_scale[1]) if row_scale is not None else 0, _terms(),
-                  _stream())
-        return
-    if row_scale is not None:
-        assert dy.dtype == torch.float32
-        _lib.call("dhz_linear_wgrad_rs", dy.data_ptr() + 4 * off, dy.stride(0), _p(x), x.stride(0), T, N, K, _p(dw), _p(db),
-                  _p(row_scale[0]), int(row_scale[1]), _stream())
-        return
-    if dy.dtype == BF16:
-        dws = (ctypes.c_void_p * 1)(dw.data_ptr())
-        dbs = (ctypes.c_void_p * 1)(db.data_ptr() if db is not None else None)
-        _lib.call("dhz_linear_wgrad_bf16", dy.data_ptr() + 2 * off, dy.stride(0), _p(x), x.stride(0), T, 1, N, K,
-                  ctypes.cast(dws, ctypes.c_void_p), ctypes.cast(dbs, ctypes.c_void_p), _stream())
+    bf16 = dy.dtype == BF16
+    assert row_scale is None or (not bf16 and len(targets) == 1)
+    rs = (_p(row_scale[0]), int(row_scale[1])) if row_scale is not None else (None, 0)
+    # fp32 storage: the contraction over T on the bf16 pipe with split operands (csrc/linear_split.hip) wherever its 64-tiles fit
+    split = not bf16 and SPLIT_BF16 and T % 64 == 0 and K % 64 == 0 and all(N % 64 == 0 for N, _, _ in targets)
+    same = 1 < len(targets) <= 4 and len({N for N, _, _ in targets}) == 1 and len({db is None for _, _, db in targets}) == 1
+    for grp in ([targets] if same else [[t] for t in targets]):
+        n, N = len(grp), grp[0][0]
+        lead = (dy.data_ptr() + dy.element_size() * off, dy.stride(0), _p(x), x.stride(0), T)
+        if bf16 or split or n > 1:
+            arrays = (_ptr_array([_p(dw) for _, dw, _ in grp]), _ptr_array([_p(db) for _, _, db in grp]))
+            if bf16:
+                _lib.call("dhz_linear_wgrad_bf16", *lead, n, N, K, *arrays, _stream())
+            elif split:
+                ev = _timed("dhz_linear_wgrad_split")
+                _lib.call("dhz_linear_wgrad_split", *lead, n, N, K, *arrays, *rs, _terms(), _stream())
+                _timed_end(ev, 2.0 * _terms() * T * n * N * K)
+            else:
+                _lib.call("dhz_linear_wgrad_multi", *lead, n, N, K, *arrays, _stream())
+        elif row_scale is not None:
+            _lib.call("dhz_linear_wgrad_rs", *lead, N, K, _p(grp[0][1]), _p(grp[0][2]), *rs, _stream())
+        else:
+            _lib.call("dhz_linear_wgrad", *lead, N, K, _p(grp[0][1]), _p(grp[0][2]), _stream())
+        off += n * N
+
+
+def linear_wgrad(dy, off, x, params, row_scale=None):
+    """Weight / bias gradients of the Linears [(W, b or None)] whose outputs are consecutive column blocks of dy from column `off`, from
+    dy [T, .] and their common input x [T, K].  Returns the autograd slots (dW_1, db_1, dW_2, ...): None for a frozen Linear and for
+    gradients that were accumulated in place into .grad (leaf parameters; GRAD_READY is told), fresh tensors otherwise.
+    row_scale = (scale[B], rows_per_scale): row t of dy counts as scale[t // rows_per_scale] * dy[t] (fp32, one Linear only).
+    The kernels' shape contract: bf16 storage - T, N, K in 64s; fp32 - T in 32s, N and K in 16s (the 16-wide tile forms exist for the
+    embed_dim = 16 model, csrc/linear_wgrad.hip).  There is deliberately no library fallback."""
+    T, K = x.shape
+    q, tq = (64, 64) if dy.dtype == BF16 else (16, 32)
+    slots, targets, inplace = [], [], []
+    for w, b in params:
+        pair = None
+        if not w.requires_grad and (b is None or not b.requires_grad):
+            dw = db = None                                     # frozen Linear: nothing to compute (its columns are skipped below)
+        elif T % tq or K % q or w.shape[0] % q:
+            raise RuntimeError(f"dehaze_hip: Linear weight gradient for T={T}, N={w.shape[0]}, K={K}: the HIP kernel needs T in {tq}s "
+                               f"and N, K in {q}s for {dy.dtype} (there is deliberately no library fallback)")
+        else:
+            pair = _grad_pair(w, b)
+            # handed to autograd, which may keep them: fresh tensors, never the optimizer's zeroed scratch (valid until zero_grad only)
+            dw, db = pair or (torch.zeros(w.shape, device=w.device, dtype=torch.float32),
+                              torch.zeros(b.shape, device=b.device, dtype=torch.float32) if b is not None else None)
+            inplace += [w, b] if pair else []
+        targets.append((w.shape[0], dw, db))
+        slots += [None, None] if dw is None or pair else [dw, db]
+    # one call for all of them when every gradient lands in place (equal widths then share a launch), else one per live Linear at its
+    # column offset
+    if len(inplace) == 2 * len(params):
+        _wgrad_launch(dy, off, x, targets, row_scale)
     else:
-        _lib.call("dhz_linear_wgrad", dy.data_ptr() + 4 * off, dy.stride(0), _p(x), x.stride(0), T, N, K, _p(dw), _p(db), _stream())
-
-
-_NO_CAT_VIEW = bool(__import__("os").environ.get("DHZ_NO_CAT_VIEW"))     # A/B switch: always copy
+        for N, dw, db in targets:
+            if dw is not None:
+                _wgrad_launch(dy, off, x, [(N, dw, db)], row_scale)
+            off += N
+    _ready(*inplace)
+    return tuple(slots)
 
 
 def cat_rows(ts):
@@ -679,7 +685,7 @@ def cat_rows(ts):
     t0 = ts[0]
     end = t0.data_ptr() + t0.numel() * t0.element_size()
     base = t0.untyped_storage().data_ptr()          # same allocation, not merely neighbouring ones
-    ok = t0.is_contiguous() and not t0.requires_grad and not _NO_CAT_VIEW
+    ok = t0.is_contiguous() and not t0.requires_grad
     for t in ts[1:]:
         ok = ok and t.is_contiguous() and not t.requires_grad and t.dtype == t0.dtype and t.device == t0.device \
             and t.shape[1:] == t0.shape[1:] and t.data_ptr() == end and t.untyped_storage().data_ptr() == base
@@ -694,9 +700,9 @@ def cat_rows(ts):
 
 
 class _LinearTokens(Function):
-    """y = x [W_1;..;W_n]^T + [b_1;..;b_n] for token-major x [T,K]: dhz_linear_fwd forward, dhz_linear_dgrad for the
-    input gradient, dhz_linear_wgrad for the weight/bias gradients, which are accumulated in place into the parameters'
-    .grad (the optimizer's flat gradient buffer)."""
+    """y = x [W_1;..;W_n]^T + [b_1;..;b_n] for token-major x [T,K]: gemm_fwd forward, gemm_dgrad for the input gradient,
+    linear_wgrad for the weight / bias gradients, which are accumulated in place into the parameters' .grad (the optimizer's flat
+    gradient buffer)."""
 
     @staticmethod
     def forward(ctx, x, *wb):
@@ -719,37 +725,7 @@ class _LinearTokens(Function):
         x, W = ctx.saved_tensors
         dy = dy.contiguous()
         dx = gemm_dgrad(dy, W) if ctx.needs_input_grad[0] else None
-        T, K = x.shape
-        grads = []
-        off = 0
-        q = 64 if dy.dtype == BF16 else 16          # fp32: 16-wide tile forms exist for the embed_dim = 16 model (csrc/linear_wgrad.hip)
-        tq = 64 if dy.dtype == BF16 else 32         # token rows per stage
-        if T % tq == 0 and K % q == 0 and all(w.shape[0] % q == 0 and w.is_leaf and w.requires_grad
-                                               and (b is None or (b.is_leaf and b.requires_grad)) for w, b in ctx.params):
-            _accumulate_param_grads(dy, 0, x, ctx.params)           # one launch for equal-shaped parameters (Q / K / V)
-            return (dx,) + (None, None) * len(ctx.params)
-        for w, b in ctx.params:
-            N = w.shape[0]
-            # measured on MI355X (tools/bench_wgrad.py): the split-T kernel wins 2-18x for T >= 16k tokens; on the deep
-            # stages (T <= 8k) it is within 0.9-1.2x of the library's TN GEMM and delivers the bias gradient for free
-            # (the library path pays a separate ~20 us column-sum kernel), so it is used everywhere
-            mine = T % tq == 0 and N % q == 0 and K % q == 0        # (the kernel's shape contract; always true on this model)
-            if not w.requires_grad and (b is None or not b.requires_grad):
-                grads += [None, None]                                 # frozen Linear
-            elif mine and w.is_leaf and w.requires_grad and (b is None or (b.is_leaf and b.requires_grad)):
-                _accumulate_param_grads(dy, off, x, [(w, b)])
-                grads += [None, None]
-            elif mine:
-                fp = w.dtype == torch.float32           # (accumulation targets of this backward pass: from the optimizer's zeroed scratch, no fill launch)
-                dw = zeros_f32(tuple(w.shape), w.device) if fp else torch.zeros_like(w, memory_format=torch.contiguous_format)
-                db = (zeros_f32(tuple(b.shape), b.device) if b.dtype == torch.float32 else torch.zeros_like(b)) if b is not None else None
-                wgrad_into(dy, off, x, N, dw, db)
-                grads += [dw, db]
-            else:
-                raise RuntimeError(f"dehaze_hip: Linear weight gradient for T={T}, N={N}, K={K}: the HIP kernel needs "
-                                   "multiples of 16 in fp32 and of 64 in bf16 (there is deliberately no library fallback)")
-            off += N
-        return (dx,) + tuple(grads)
+        return (dx,) + linear_wgrad(dy, 0, x, ctx.params)
 
 
 class _GeluTokens(Function):
@@ -976,23 +952,13 @@ class _ThinConv(Function):
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             _lib.call("dhz_thin_conv3x3_dgrad_dt", _p(dy), _p(wc), _p(dx), B, H, W, C, _dt(x), _stream())
-        inplace = w.is_leaf and w.requires_grad and (b is None or (b.is_leaf and b.requires_grad))
-        if inplace:
-            for p_ in (w, b):
-                if p_ is not None and p_.grad is None:
-                    p_.grad = torch.zeros_like(p_, memory_format=torch.contiguous_format)
-            inplace = w.grad.is_contiguous()
-        if inplace:
-            _lib.call("dhz_thin_conv3x3_wgrad_dt", _p(dy), _p(x), _p(w.grad), _p(b.grad) if b is not None else None, B, H, W, C,
-                      _dt(x), _stream())
-            if GRAD_READY is not None:
-                GRAD_READY(w)
-                if b is not None:
-                    GRAD_READY(b)
-            return dx, None, None, None, None
-        dw = torch.zeros((3, C, 3, 3), device=x.device, dtype=torch.float32)
-        db = torch.zeros(3, device=x.device, dtype=torch.float32) if b is not None else None
+        pair = _grad_pair(w, b)
+        dw, db = pair or (torch.zeros((3, C, 3, 3), device=x.device, dtype=torch.float32),
+                          torch.zeros(3, device=x.device, dtype=torch.float32) if b is not None else None)
         _lib.call("dhz_thin_conv3x3_wgrad_dt", _p(dy), _p(x), _p(dw), _p(db), B, H, W, C, _dt(x), _stream())
+        if pair:
+            _ready(w, b)
+            return dx, None, None, None, None
         return dx, dw, db, None, None
 
 
@@ -1010,6 +976,27 @@ def conv4s2_supported(x, H, W, need_grad):
         Ho, Wo = H // 2, W // 2
         ok = (Ho & (Ho - 1)) == 0 and (Wo & (Wo - 1)) == 0 and (x.shape[0] * Ho * Wo) % 32 == 0
     return ok
+
+
+def _conv4s2_wgrad(w, b, zeros, launch):
+    """the weight-gradient tail the fp32 and the bf16 Downsample convolution share: launch(dwp, db) accumulates into the zeroed
+    tap-major dwp [Cout, 16 Cin] (from zeros(shape)) and into the bias gradient (b.grad itself when b is a leaf); dwp goes back to
+    [co][ci][ky][kx] and is added to w.grad (leaf) or handed to autograd.  Returns the autograd slots (gw, gb)."""
+    if not (w.requires_grad or (b is not None and b.requires_grad)):
+        return None, None
+    Cout, Cin = w.shape[0], w.shape[1]
+    dwp = zeros((Cout, 16 * Cin))
+    gbuf = _grad_buf(b) if b is not None else None
+    dbv = gbuf if gbuf is not None else (torch.zeros_like(b) if b is not None else None)
+    launch(dwp, dbv)
+    dw = dwp.view(Cout, 4, 4, Cin).permute(0, 3, 1, 2)
+    wbuf = _grad_buf(w)
+    if wbuf is not None:
+        wbuf.add_(dw)
+        _ready(w)
+    if gbuf is not None:
+        _ready(b)
+    return None if wbuf is not None else dw.contiguous(), None if gbuf is not None else dbv
 
 
 class _Conv4s2(Function):
@@ -1040,28 +1027,8 @@ class _Conv4s2(Function):
             wq = w_.detach().permute(2, 3, 0, 1).contiguous()                         # [(ky, kx, co)][ci]
             dx = torch.empty_like(x)
             _lib.call("dhz_conv4s2_dgrad", _p(dy), _p(wq), _p(dx), B, H, W, Cin, Cout, _stream())
-        gw = gb = None
-        if w.requires_grad or (b is not None and b.requires_grad):
-            dwp = zeros_f32((Cout, 16 * Cin), x.device)
-            inplace_b = b is not None and b.is_leaf and b.requires_grad
-            if inplace_b and b.grad is None:
-                b.grad = torch.zeros_like(b)
-            dbv = b.grad if inplace_b else (torch.zeros_like(b) if b is not None else None)
-            _lib.call("dhz_conv4s2_wgrad", _p(dy), _p(x), _p(dwp), _p(dbv), B, H, W, Cin, Cout, _stream())
-            dw = dwp.view(Cout, 4, 4, Cin).permute(0, 3, 1, 2)                        # back to [co][ci][ky][kx]
-            if w.is_leaf and w.requires_grad:
-                if w.grad is None:
-                    w.grad = torch.zeros_like(w, memory_format=torch.contiguous_format)
-                w.grad.add_(dw)
-                if GRAD_READY is not None:
-                    GRAD_READY(w)
-            else:
-                gw = dw.contiguous()
-            if inplace_b:
-                if GRAD_READY is not None:
-                    GRAD_READY(b)
-            else:
-                gb = dbv
+        gw, gb = _conv4s2_wgrad(w, b, lambda shape: zeros_f32(shape, x.device), lambda dwp, dbv: _lib.call(
+            "dhz_conv4s2_wgrad", _p(dy), _p(x), _p(dwp), _p(dbv), B, H, W, Cin, Cout, _stream()))
         return dx, gw, gb, None, None
 
 
@@ -1095,28 +1062,8 @@ class _Conv4s2BF16(Function):
             dcol = gemm_dgrad(dy, wp)
             dx = torch.empty((B, H * W, Cin), device=dy.device, dtype=BF16)
             _lib.call("dhz_col2im_k4s2_bf16", _p(dcol), _p(dx), B, H, W, Cin, _stream())
-        gw = gb = None
-        if w.requires_grad or (b is not None and b.requires_grad):
-            dwp = torch.zeros((Cout, 16 * Cin), device=dy.device, dtype=torch.float32)
-            inplace_b = b is not None and b.is_leaf and b.requires_grad
-            if inplace_b and b.grad is None:
-                b.grad = torch.zeros_like(b)
-            dbv = b.grad if inplace_b else (torch.zeros_like(b) if b is not None else None)
-            wgrad_into(dy, 0, col, Cout, dwp, dbv)
-            dw = dwp.view(Cout, 4, 4, Cin).permute(0, 3, 1, 2)                        # back to [co][ci][ky][kx]
-            if w.is_leaf and w.requires_grad:
-                if w.grad is None:
-                    w.grad = torch.zeros_like(w, memory_format=torch.contiguous_format)
-                w.grad.add_(dw)
-                if GRAD_READY is not None:
-                    GRAD_READY(w)
-            else:
-                gw = dw.contiguous()
-            if inplace_b:
-                if GRAD_READY is not None:
-                    GRAD_READY(b)
-            else:
-                gb = dbv
+        gw, gb = _conv4s2_wgrad(w, b, lambda shape: torch.zeros(shape, device=dy.device, dtype=torch.float32),
+                                lambda dwp, dbv: _wgrad_launch(dy, 0, col, [(Cout, dwp, dbv)], None))
         return dx, gw, gb, None, None
 
 
@@ -1156,20 +1103,12 @@ class _InputProj(Function):
             raise RuntimeError("dehaze_hip: InputProj has no backward-data kernel (the image never needs a gradient on this path)")
         B, _, H, W = img.shape
         E = w.shape[0]
-        inplace = w.is_leaf and w.requires_grad and b.is_leaf and b.requires_grad
-        if inplace:
-            for p_ in (w, b):
-                if p_.grad is None:
-                    p_.grad = torch.zeros_like(p_, memory_format=torch.contiguous_format)
-            inplace = w.grad.is_contiguous()
-        gw = w.grad if inplace else torch.zeros_like(w, memory_format=torch.contiguous_format)
-        gb = b.grad if inplace else torch.zeros_like(b)
+        pair = _grad_pair(w, b)
+        gw, gb = pair or (torch.zeros_like(w, memory_format=torch.contiguous_format), torch.zeros_like(b))
         _lib.call("dhz_input_proj_bwd_dt", _p(dy.contiguous().to(y.dtype)), _p(y), _p(img), _p(gw), _p(gb), B, H, W, E, ctx.slope, _dt(y),
                   _stream())
-        if inplace:
-            if GRAD_READY is not None:
-                GRAD_READY(w)
-                GRAD_READY(b)
+        if pair:
+            _ready(w, b)
             return None, None, None, None, None
         return None, gw, gb, None, None
 

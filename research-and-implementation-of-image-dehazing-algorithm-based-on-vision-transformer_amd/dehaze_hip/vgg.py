@@ -62,23 +62,10 @@ def pool_bwd_relu(gb, actb):
     return gx
 
 
-def _timing_begin():
-    """bench.py's per-kernel HIP events (ops.KERNEL_TIMING), on the launch stream, bracketing exactly this kernel."""
-    timing = ops.KERNEL_TIMING.get("dhz_winograd_conv3x3") if ops.KERNEL_TIMING is not None else None
-    if timing is None:
-        return None
-    e0 = torch.cuda.Event(enable_timing=True)
-    e0.record()
-    return timing, e0
-
-
 def _timing_end(ev, B, H, W, Cin, Kout, f43=False):
-    if ev is not None:
-        e1 = torch.cuda.Event(enable_timing=True)
-        e1.record()
-        direct = 2.0 * 9 * B * H * W * Cin * Kout                             # direct-convolution FLOPs of this launch
-        # ISSUED matrix FLOPs: F(2x2,3x3) multiplies 16 / 4 per output and tap-sum instead of 9 (direct / 2.25), F(4x4,3x3) 36 / 16 (/ 4)
-        ev[0].append((ev[1], e1, direct, direct / (4.0 if f43 else 2.25)))
+    direct = 2.0 * 9 * B * H * W * Cin * Kout                                 # direct-convolution FLOPs of this launch
+    # ISSUED matrix FLOPs: F(2x2,3x3) multiplies 16 / 4 per output and tap-sum instead of 9 (direct / 2.25), F(4x4,3x3) 36 / 16 (/ 4)
+    ops._timed_end(ev, direct, direct / (4.0 if f43 else 2.25))
 
 
 # Which Winograd form a layer takes: F(4x4,3x3) (csrc/winograd43_conv.hip, 1.78 x fewer matrix products) or F(2x2,3x3)
@@ -154,13 +141,13 @@ class VggEngine:
         if pool and f43:
             yp = torch.empty((B, K // 8, H // 2, W // 2, 8), device=xb.device, dtype=torch.float32)
             scratch = torch.empty((B, K // 8, H, W, 8), device=xb.device, dtype=torch.float32) if C > 256 else None
-            ev = _timing_begin()
+            ev = ops._timed("dhz_winograd_conv3x3")
             _lib.call("dhz_winograd43_conv3x3_pool", _p(xb), _p(uf), _p(self.convs[i].bias), _p(yp), _p(scratch) if scratch is not None else None,
                       B, H, W, C, K, _stream())
             _timing_end(ev, B, H, W, C, K, f43)
             return yp
         yb = torch.empty((B, K // 8, H, W, 8), device=xb.device, dtype=torch.float32)
-        ev = _timing_begin()
+        ev = ops._timed("dhz_winograd_conv3x3")
         _lib.call("dhz_winograd43_conv3x3" if f43 else "dhz_winograd_conv3x3", _p(xb), _p(uf), _p(self.convs[i].bias), 1, None, None,
                   _p(yb), B, H, W, C, K, _stream())
         _timing_end(ev, B, H, W, C, K, f43)
@@ -175,7 +162,7 @@ class VggEngine:
         f43 = use_f43(B, H, W, K, C)                       # the backward-data form: K input channels, C outputs
         _, ub = self.packed43(i, gb.device) if f43 else self.packed(i, gb.device)
         dxb = torch.empty((B, C // 8, H, W, 8), device=gb.device, dtype=torch.float32)
-        ev = _timing_begin()
+        ev = ops._timed("dhz_winograd_conv3x3")
         _lib.call("dhz_winograd43_conv3x3" if f43 else "dhz_winograd_conv3x3", _p(gb), _p(ub), None, 0,
                   _p(below_act) if below_act is not None else None,
                   _p(addend.contiguous()) if addend is not None else None, _p(dxb), B, H, W, K, C, _stream())
@@ -300,21 +287,12 @@ class VggEngineBF16:
             self._packed[i] = hit
         return hit[1], hit[2]
 
-    @staticmethod
-    def _timing_begin():
-        timing = ops.KERNEL_TIMING.get("dhz_vgg_conv3x3_bf16") if ops.KERNEL_TIMING is not None else None
-        if timing is None:
-            return None
-        e0 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-        return timing, e0
-
     def conv(self, i, x):
         N, H, W, C = x.shape
         K = CONVS[i][1]
         wf, _ = self.packed(i, x.device)
         y = torch.empty((N, H, W, K), device=x.device, dtype=torch.bfloat16)
-        ev = self._timing_begin()
+        ev = ops._timed("dhz_vgg_conv3x3_bf16")
         _lib.call("dhz_vgg_conv3x3_bf16", _p(x), _p(wf), _p(self.convs[i].bias), 1, None, None, _p(y), N, H, W, C, K, _stream())
         _timing_end(ev, N, H, W, C, K)
         return y
@@ -326,7 +304,7 @@ class VggEngineBF16:
         C = CONVS[i][0]
         _, wb = self.packed(i, g.device)
         dx = torch.empty((N, H, W, C), device=g.device, dtype=torch.bfloat16)
-        ev = self._timing_begin()
+        ev = ops._timed("dhz_vgg_conv3x3_bf16")
         _lib.call("dhz_vgg_conv3x3_bf16", _p(g), _p(wb), None, 0, _p(below_act) if below_act is not None else None,
                   _p(addend.contiguous()) if addend is not None else None, _p(dx), N, H, W, K, C, _stream())
         _timing_end(ev, N, H, W, K, C)

@@ -415,3 +415,26 @@ def test_zero_scratch_allocator():
     gc.collect()
     d = ops.zeros_f32((5, 3), torch.device("cpu"))                            # owner gone: never a slice of a dead optimizer's buffer
     assert d.untyped_storage().data_ptr() != scr.untyped_storage().data_ptr()
+
+
+def test_token_linear_launches_match_the_table_of_the_parent_commit():
+    """Which entry point a token-Linear product reaches, with which scalar arguments, is host logic: ops._route (one route per product)
+    and ops.linear_wgrad (one weight-gradient entry).  The wrappers are driven without a device (tests/_launch_log.py: _lib.call
+    replaced by a recorder, torch.empty CPU operands) over forward / residual-epilogue / backward-data / row-factor products, linear_tokens
+    through autograd (leaf, frozen, non-leaf parameters; one and three packed pairs) and fused._wgrad with a row factor; fp32 and bf16;
+    SPLIT_BF16 in 6 / 0 / 3, RES_EPILOGUE and _NO_TPLANES both ways, weights with and without registered shadows; every shape of the
+    Linears of BASELINE configs 1 and 4 and of the embed_dim = 16 model plus the edges of the ladder.  The expected log
+    (tests/golden/launch_log_parent.txt.gz, 12805 lines `case | product | calls`: too long for a literal here) was written by the
+    commit BEFORE the three hand-written ladders and the five weight-gradient owners were merged: no line may differ."""
+    import gzip
+    import _launch_log
+    with gzip.open(os.path.join(ROOT, "tests", "golden", "launch_log_parent.txt.gz"), "rt") as f:
+        want = f.read().splitlines()
+    got = [f"{name} | {prod} | {calls}" for name, prods in _launch_log.grid() for prod, calls in prods.items()]
+    # three lines of the table, readable here: packed Q / K / V at C = 64, and the 2^19-token C = 64 product that stays on the fp32 pipe forward
+    assert "T131072 K64 N64 32x64x64 f32 split6 res1 notp0 shadow1 | lin3_leaf | fwd_split6(64,192,131072,192,64); " \
+           "fwd_split6(192,64,131072,64,192); wgrad_split(192,64,131072,3,64,64,0,6)" in want       # (backward-data: the forward kernel on W^T)
+    assert "T524288 K64 N64 32x128x128 f32 split6 res1 notp0 shadow1 | fwd | fwd(64,64,524288,64,64)" in want
+    assert "T524288 K64 N64 32x128x128 f32 split6 res1 notp0 shadow1 | dgrad | dgrad_split(64,64,524288,64,64,6)" in want
+    diff = [(w, g) for w, g in zip(want, got) if w != g]
+    assert len(want) == len(got) and not diff, f"{len(diff)} of {len(want)} lines differ (table, now), first: {diff[:5]}"

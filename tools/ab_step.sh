@@ -1,5 +1,5 @@
 # A/B of environment settings on the training step, same box, alternating passes:
-#   VARIANTS="DHZ_S6_ROUTE= DHZ_S6_ROUTE=old" bash tools/ab_step.sh        (an empty value = the default)
+#   VARIANTS="DHZ_NO_RES_EPILOGUE= DHZ_NO_RES_EPILOGUE=1" bash tools/ab_step.sh        (an empty value = the default)
 R=$(cd "$(dirname "$0")/.." && pwd)
 for rep in $(seq 1 ${PASSES:-2}); do
   for v in $VARIANTS; do
