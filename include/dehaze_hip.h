@@ -49,6 +49,23 @@ const char* dhz_build_id(void);
 int dhz_set_reserved_cus(int k);
 int dhz_get_reserved_cus(void);
 int dhz_grid_cus(void);
+/* Deterministic mode (process-global like the reservation; default 0 = off: nothing changes).  With it on, every entry that ACCUMULATES a
+ * parameter gradient or a loss sum - the token-Linear / convolution / depthwise / input-projection weight gradients, LayerNorm dgamma / dbeta,
+ * the relative-position table gradient, the Charbonnier and L1-pair sums - runs a second instance of its kernel: work item i (token slab, tile
+ * slot, workgroup) STORES its partial in slot i of the workspace, and one reduction kernel (csrc/det_reduce.hip) sums the slots in ascending
+ * order, one owner thread per element, and adds the sum to the target.  No fp32 atomic, global or LDS, contributes; the cut into items is a
+ * function of the problem shape alone (slab counts and tile choices otherwise derived from the CU count use the constant 256; the size of a
+ * persistent grid whose workgroups walk the tiles still follows the CU count: it moves no bit), so results are bit-identical from
+ * run to run, under any dhz_set_reserved_cus and on any device.  "Caller zeroes, kernel accumulates" holds in both modes.
+ * Scope: fp32 storage, one process.  The bf16-storage accumulating entries (dhz_linear_wgrad_bf16, dhz_l1_pair_fwd_bf16, the DHZ_BF16 forms of
+ * the LayerNorm / depthwise / thin-convolution / input-projection backward) and dhz_fused_window_attn_bwd return DHZ_EINVAL while the mode is
+ * on (the Python side routes C = 32 attention to its backward chain).
+ * dhz_set_det_workspace: device memory the mode may use (16-byte aligned; NULL, 0 takes it away); used in stream order, so all calls that
+ * accumulate must be on ONE stream.  An entry that needs more than `bytes` returns DHZ_EINVAL and names the bytes it needs - never a
+ * fall-back to atomics. */
+int dhz_set_deterministic(int on);
+int dhz_get_deterministic(void);
+int dhz_set_det_workspace(float* ws, size_t bytes);
 
 /* ---------------------------------------------------------------------------------------------
  * K3  ProbSparse window attention core.   Replaces ProbAttention.forward  ATT:287-342
@@ -351,7 +368,8 @@ int dhz_ps_attn_bwd_dt(const void* q, const void* k, const void* v, int ld, cons
  *     dw[N,K] += dy^T[N,T] . x[T,K]        db[N] += sum_t dy[t,:]        (ACCUMULATED: caller zeroes,
  *     which lets the gradients land directly in the optimizer's flat gradient buffer).
  *     dy: [T,N] with row stride ldy, x: [T,K] with row stride ldx; T % 32 == 0, N % 32 == 0, K % 32 == 0.
- *     db may be NULL.  Summation order over T is not deterministic (fp32 atomics). */
+ *     db may be NULL.  Default mode: the token slabs meet in fp32 atomics, the summation order over T is not deterministic and the slab count
+ *     follows the CU count.  Deterministic mode (dhz_set_deterministic): slabs cut by the shape alone, stored and summed in slab order. */
 int dhz_linear_wgrad(const float* dy, int ldy, const float* x, int ldx, int T, int N, int K,
                      float* dw, float* db, void* stream);
 /*      Same contraction for nmat (1..4) parameters that share the input x - the Q / K / V projections of

@@ -49,6 +49,8 @@ def main():
     parser = options.Options().init(argparse.ArgumentParser(description='remove the haze'))
     parser.add_argument('--synthetic', type=int, default=0, help='train on N synthetic pairs per epoch (HBM resident)')
     parser.add_argument('--val_synthetic', type=int, default=8)
+    parser.add_argument('--deterministic', action='store_true',
+                        help='bit-reproducible steps: fixed-order reductions instead of fp32 atomics (fp32 storage, per process; slower)')
     parser.add_argument('--log_every', type=int, default=10, help='host sync cadence for the progress line')
     opt = parser.parse_args()
     torch.backends.cudnn.benchmark = True      # TR:35 - on ROCm: MIOpen measures its convolution algorithms at first use
@@ -58,6 +60,9 @@ def main():
     local = int(os.environ.get("LOCAL_RANK", "0"))
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
+    if opt.deterministic:
+        from dehaze_hip import ops
+        ops.set_deterministic(True)
     if world > 1:
         dist.init_process_group("nccl", device_id=dev)
     is_main = rank == 0

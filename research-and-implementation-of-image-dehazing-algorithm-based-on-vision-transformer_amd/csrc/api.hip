@@ -44,6 +44,38 @@ extern "C" int dhz_set_reserved_cus(int k) {
 extern "C" int dhz_get_reserved_cus(void) { return g_reserved_cus.load(std::memory_order_relaxed); }
 extern "C" int dhz_grid_cus(void) { return dhz_num_cus(); }
 
+// Deterministic mode: process-global like the reservation.  The workspace belongs to the caller (dehaze_hip.ops owns a torch tensor); it is
+// used in stream order, so every call that uses it must be on one stream.
+static std::atomic<int> g_det{0};
+static std::atomic<float*> g_det_ws{nullptr};
+static std::atomic<size_t> g_det_ws_bytes{0};
+
+bool dhz_det() { return g_det.load(std::memory_order_relaxed) != 0; }
+int dhz_part_cus() { return dhz_det() ? 256 : dhz_num_cus(); }
+float* dhz_det_ws(const char* who, long items, long slot) {
+    const size_t need = (size_t)items * (size_t)slot * sizeof(float), have = g_det_ws_bytes.load(std::memory_order_relaxed);
+    float* ws = g_det_ws.load(std::memory_order_relaxed);
+    if (!ws || need > have) {
+        dhz_set_error("%s: deterministic mode needs a workspace of %zu bytes (%ld items x %ld floats), dhz_set_det_workspace gave %zu",
+                      who, need, items, slot, ws ? have : (size_t)0);
+        return nullptr;
+    }
+    return ws;
+}
+
+extern "C" int dhz_set_deterministic(int on) {
+    g_det.store(on ? 1 : 0, std::memory_order_relaxed);
+    return DHZ_OK;
+}
+extern "C" int dhz_get_deterministic(void) { return g_det.load(std::memory_order_relaxed); }
+extern "C" int dhz_set_det_workspace(float* ws, size_t bytes) {
+    DHZ_REQUIRE((ws != nullptr) == (bytes != 0), "dhz_set_det_workspace: ws=%p with %zu bytes", (void*)ws, bytes);
+    DHZ_REQUIRE(((uintptr_t)ws & 15) == 0, "dhz_set_det_workspace: the workspace must be 16-byte aligned");
+    g_det_ws.store(ws, std::memory_order_relaxed);
+    g_det_ws_bytes.store(bytes, std::memory_order_relaxed);
+    return DHZ_OK;
+}
+
 extern "C" const char* dhz_last_error(void) { return g_err; }
 extern "C" int dhz_abi_version(void) { return 1; }
 #ifdef DHZ_VARIANT_TAG          // diagnostic builds (tools/variants.sh, tools/abl_fused.sh) link variant kernels: their id must not be the product's

@@ -52,6 +52,27 @@ void dhz_set_error(const char* fmt, ...);
 // Persistent-grid sizes are "resident workgroups per CU x dhz_num_cus()", never a literal.
 int dhz_num_cus();
 
+// ---- deterministic mode (dhz_set_deterministic; csrc/det_reduce.hip).  An accumulating kernel has a DET instance that STORES the partial
+// of work item i to ws[i * slot + ...] instead of adding it to the target with fp32 atomics; dhz_det_reduce then sums the items in
+// ascending order, one owner thread per element, and adds the sum to the target.  The cut into items is a function of the problem
+// shape only: sizes that the default mode derives from dhz_num_cus() come from dhz_part_cus().
+bool dhz_det();
+int dhz_part_cus();                      // dhz_num_cus(), or the constant 256 in deterministic mode
+constexpr int DHZ_DET_MAXSEG = 8;
+struct DetSegs {                         // a slot holds up to 8 targets: dst[s][e] += sum_i ws[i * slot + off[s] + e],  e < len[s]
+    int n;
+    long off[DHZ_DET_MAXSEG], len[DHZ_DET_MAXSEG];
+    float* dst[DHZ_DET_MAXSEG];
+};
+float* dhz_det_ws(const char* who, long items, long slot);      // the workspace (items x slot floats), or nullptr with the error set
+int dhz_det_reduce(const char* who, const float* ws, int items, long slot, const DetSegs& segs, hipStream_t s);
+// the one line that differs between the two instances of a kernel's epilogue
+template <bool DET>
+__device__ __forceinline__ void dhz_accum(float* p, float v) {
+    if constexpr (DET) *p = v;
+    else atomicAdd(p, v);
+}
+
 #define DHZ_REQUIRE(cond, ...)            \
     do {                                  \
         if (!(cond)) {                    \
@@ -68,6 +89,31 @@ int dhz_num_cus();
             return DHZ_ELAUNCH;                                                  \
         }                                                                        \
     } while (0)
+
+// Weight-gradient launches (dW of up to 4 parameters of nper rows each, + db): o2 is `out` with its targets moved to slot 0 of the
+// workspace, layout [dw 0 .. nmat) | db 0 .. nmat)]; the DET kernel adds item * o2.det_stride.  Every (tile, item) workgroup stores its
+// whole tile, empty slabs store zeros: the slots need no clearing.
+template <class Out>
+int dhz_det_wgrad_begin(const char* who, const Out& out, int nmat, int K, int items, Out& o2, DetSegs& segs, float*& ws, long& slot) {
+    const long wlen = (long)out.nper * K;
+    const bool bias = out.db[0] != nullptr;
+    slot = nmat * (wlen + (bias ? out.nper : 0));
+    ws = dhz_det_ws(who, items, slot);
+    if (!ws) return DHZ_EINVAL;
+    o2 = out;
+    o2.det_stride = slot;
+    segs = DetSegs{};
+    for (int m = 0; m < nmat; ++m) {
+        DHZ_REQUIRE((out.db[m] != nullptr) == bias, "%s: deterministic mode: bias gradients must be all set or all null", who);
+        segs.off[segs.n] = m * wlen; segs.len[segs.n] = wlen; segs.dst[segs.n++] = out.dw[m];
+        o2.dw[m] = ws + m * wlen;
+        if (bias) {
+            segs.off[segs.n] = nmat * wlen + (long)m * out.nper; segs.len[segs.n] = out.nper; segs.dst[segs.n++] = out.db[m];
+            o2.db[m] = ws + nmat * wlen + (long)m * out.nper;
+        }
+    }
+    return DHZ_OK;
+}
 
 // v_mfma_f32_16x16x4_f32: D[16x16] += A[16x4] * B[4x16].  lane l: a = A[l&15][l>>4], b = B[l>>4][l&15];
 // acc[j] = D[4*(l>>4)+j][l&15].

@@ -250,7 +250,7 @@ void dispatch(const float* A, const float* Wt, const float* bias, float* Y, cons
     int wm = 2, wn = 1;
     static const int cand[8][2] = {{4, 4}, {4, 3}, {4, 2}, {2, 4}, {2, 3}, {2, 2}, {4, 1}, {2, 1}};
     long best = -1;
-    const long slots = 2 * dhz_num_cus();
+    const long slots = 2 * dhz_part_cus();                        // (a tile choice: a function of the shape in deterministic mode)
     for (int i = 0; i < 8; ++i) {
         const int a = cand[i][0], b = cand[i][1];
         if (N % (32 * b)) continue;
@@ -267,11 +267,12 @@ void dispatch(const float* A, const float* Wt, const float* bias, float* Y, cons
 // ------------------------------------------------------------------------------------------------ weight gradient
 // dwp[n, k] += sum_m dy[m, n] xcol[m, k],  k = (tap, ci): the split-T kernel of csrc/linear_wgrad.hip (one token group) with a
 // gathered x operand; a K tile (32 WN columns, WN | Cin / 32) lies inside one tap.
+// DET (deterministic mode, common.h): token slab `split` STORES its tile at dw / db + split * det_stride (both point into the workspace)
 constexpr int TK = 32;
-template <int WM, int WN>
+template <int WM, int WN, bool DET = false>
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                          float* __restrict__ dw, float* __restrict__ db, ConvGeom G, int T, int N,
-                                                         int K, int nsplit, int lgWo, int lgHW) {
+                                                         int K, int nsplit, int lgWo, int lgHW, long det_stride) {
     constexpr int BM = 32 * WM, BN = 32 * WN;
     constexpr int SA = BM + 16, SB = BN + 16;
     constexpr int A4 = BM / 4, B4 = BN / 4;
@@ -286,6 +287,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const float* __restrict
     const int split = bid % nsplit; bid /= nsplit;
     const int tn = bid % tiles_n, tm = bid / tiles_n;
     const int n0 = tm * BM, k0 = tn * BN;
+    if constexpr (DET) { dw += (size_t)split * det_stride; if (db) db += (size_t)split * det_stride; }
     const int tap = k0 / G.Cin, c0 = k0 - tap * G.Cin, ky = tap >> 2, kx = tap & 3;
     const int nst = T / TK;
     const int st0 = (int)((long long)nst * split / nsplit), st1 = (int)((long long)nst * (split + 1) / nsplit);
@@ -367,7 +369,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const float* __restrict
 #pragma unroll
             for (int j = 0; j < 4; ++j) Cs[(wm * WM * 16 + a * 16 + 4 * g + j) * BN + wn * WN * 16 + b * 16 + i16] = acc[a][b][j];
     __syncthreads();
-    for (int e = t; e < BM * BN; e += 256) atomicAdd(dw + (size_t)(n0 + e / BN) * K + k0 + e % BN, Cs[e]);
+    for (int e = t; e < BM * BN; e += 256) dhz_accum<DET>(dw + (size_t)(n0 + e / BN) * K + k0 + e % BN, Cs[e]);
     if (do_db) {
         __syncthreads();
         float* red = smem;                                 // [TK*A4][4]
@@ -379,27 +381,45 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const float* __restrict
             const int c4 = t / 4, comp = t % 4;
             float tot = 0.f;
             for (int r = 0; r < TK; ++r) tot += smem[(r * A4 + c4) * 4 + comp];
-            atomicAdd(db + n0 + t, tot);
+            dhz_accum<DET>(db + n0 + t, tot);
         }
     }
 }
 
 template <int WM, int WN>
-void launch_wgrad(const float* dy, const float* x, float* dw, float* db, const ConvGeom& G, int T, int N, int K, int lgWo, int lgHW,
+int launch_wgrad(const float* dy, const float* x, float* dw, float* db, const ConvGeom& G, int T, int N, int K, int lgWo, int lgHW,
                   hipStream_t s) {
     constexpr int BM = 32 * WM, BN = 32 * WN;
     constexpr size_t stage = (size_t)TK * (BM + 16 + BN + 16) * sizeof(float);
     constexpr size_t smem = 2 * stage > (size_t)BM * BN * 4 ? 2 * stage : (size_t)BM * BN * 4;
     const int tiles = (N / BM) * (K / BN);
-    int nsplit = 2 * dhz_num_cus() / tiles;
+    int nsplit = 2 * dhz_part_cus() / tiles;
     const int max_split = T / (TK * 4) > 0 ? T / (TK * 4) : 1;
     if (nsplit > max_split) nsplit = max_split;
     if (nsplit < 1) nsplit = 1;
     if (smem > 48 * 1024)
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<WM, WN>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)smem);
+    if (dhz_det()) {                     // one item per token slab; slot = [dw N x K | db N]
+        const char* who = "dhz_conv4s2_wgrad";
+        const long wlen = (long)N * K, slot = wlen + (db ? N : 0);
+        float* ws = dhz_det_ws(who, nsplit, slot);
+        if (!ws) return DHZ_EINVAL;
+        if (smem > 48 * 1024)
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<WM, WN, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)smem);
+        hipLaunchKernelGGL((conv_wgrad_kernel<WM, WN, true>), dim3(tiles * nsplit), dim3(256), smem, s, dy, x, ws, db ? ws + wlen : nullptr, G, T, N, K,
+                           nsplit, lgWo, lgHW, slot);
+        DHZ_CHECK_LAUNCH(who);
+        DetSegs segs{};
+        segs.n = db ? 2 : 1;
+        segs.off[0] = 0; segs.len[0] = wlen; segs.dst[0] = dw;
+        segs.off[1] = wlen; segs.len[1] = N; segs.dst[1] = db;
+        return dhz_det_reduce(who, ws, nsplit, slot, segs, s);
+    }
     hipLaunchKernelGGL((conv_wgrad_kernel<WM, WN>), dim3(tiles * nsplit), dim3(256), smem, s, dy, x, dw, db, G, T, N, K, nsplit, lgWo,
-                       lgHW);
+                       lgHW, 0L);
+    return DHZ_OK;
 }
 
 int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return (1 << l) == v ? l : -1; }
@@ -444,9 +464,11 @@ extern "C" int dhz_conv4s2_wgrad(const float* dy, const float* x, float* dwp, fl
     const int wm = (N % 128 == 0) ? 4 : (N % 96 == 0) ? 3 : (N % 64 == 0) ? 2 : 1;
     const int wn = (Cin % 128 == 0) ? 4 : (Cin % 64 == 0) ? 2 : 1;               // a K tile stays inside one tap
 #define CASE(a, b) \
-    if (wm == a && wn == b) launch_wgrad<a, b>(dy, x, dwp, db, G, T, N, K, lgWo, lgHW, (hipStream_t)stream);
+    if (wm == a && wn == b) rc = launch_wgrad<a, b>(dy, x, dwp, db, G, T, N, K, lgWo, lgHW, (hipStream_t)stream);
+    int rc = DHZ_OK;
     CASE(1, 1) CASE(1, 2) CASE(1, 4) CASE(2, 1) CASE(2, 2) CASE(2, 4) CASE(3, 1) CASE(3, 2) CASE(3, 4) CASE(4, 1) CASE(4, 2) CASE(4, 4)
 #undef CASE
+    if (rc) return rc;
     DHZ_CHECK_LAUNCH("dhz_conv4s2_wgrad");
     return DHZ_OK;
 }

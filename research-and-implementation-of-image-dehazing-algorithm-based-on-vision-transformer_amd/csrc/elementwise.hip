@@ -73,7 +73,9 @@ __global__ __launch_bounds__(256) void ln_partition_fwd_kernel(const T* __restri
     }
 }
 
-template <int VPL, typename T, bool WIDE = false>
+// DET (deterministic mode, common.h): the four waves meet in LDS through their own rows, summed in wave order, and the workgroup STORES its
+// 2C sums at dgamma[blockIdx.x * 2C ...] (dgamma is then the workspace, dbeta unused); the grid is a function of the shape.
+template <int VPL, typename T, bool WIDE = false, bool DET = false>
 __global__ __launch_bounds__(256) void ln_partition_bwd_kernel(const T* __restrict__ dxw,
                                                                const T* __restrict__ x,
                                                                const float* __restrict__ gamma,
@@ -87,7 +89,7 @@ __global__ __launch_bounds__(256) void ln_partition_bwd_kernel(const T* __restri
     // the window order of shift (lay >> 8) on the same map: the layout the consumer (the attention branch's backward) reads.
     // dx2 (optional): a SECOND copy of dx in that window order, times scale2[image] - the scaled, window-ordered d(out) operand of the
     // out-projection's backward products where their kernels take no row factor (bf16 storage)
-    __shared__ float red[2 * 1024];                            // dgamma | dbeta  (C <= 1024)
+    __shared__ float red[(DET ? 4 : 1) * 2 * 1024];            // dgamma | dbeta  (C <= 1024); DET: one row per wave
     const int tpw = 64 / lpt;
     const int lane = threadIdx.x & 63;
     const int sub = lane / lpt, li = lane % lpt;
@@ -95,8 +97,10 @@ __global__ __launch_bounds__(256) void ln_partition_bwd_kernel(const T* __restri
     const int nwaves = (gridDim.x * blockDim.x) >> 6;
     const int HW = Hres * Wres;
     const float invC = 1.0f / (float)C;
-    for (int e = threadIdx.x; e < 2 * C; e += blockDim.x) red[e] = 0.f;
-    __syncthreads();
+    if (!DET) {
+        for (int e = threadIdx.x; e < 2 * C; e += blockDim.x) red[e] = 0.f;
+        __syncthreads();
+    }
     float4 gm[VPL], dg[VPL], db[VPL];
 #pragma unroll
     for (int v = 0; v < VPL; ++v) {
@@ -193,16 +197,27 @@ __global__ __launch_bounds__(256) void ln_partition_bwd_kernel(const T* __restri
         }
         if (sub == 0) {
             const int c = quad_col<WIDE>(li, v, lpt);
+            if constexpr (DET) {
+                float* r = red + (threadIdx.x >> 6) * 2 * C;
+                *reinterpret_cast<float4*>(r + c) = dg[v];
+                *reinterpret_cast<float4*>(r + C + c) = db[v];
+            } else {
             atomicAdd(&red[c + 0], dg[v].x); atomicAdd(&red[c + 1], dg[v].y);
             atomicAdd(&red[c + 2], dg[v].z); atomicAdd(&red[c + 3], dg[v].w);
             atomicAdd(&red[C + c + 0], db[v].x); atomicAdd(&red[C + c + 1], db[v].y);
             atomicAdd(&red[C + c + 2], db[v].z); atomicAdd(&red[C + c + 3], db[v].w);
+            }
         }
     }
     __syncthreads();
+    if constexpr (DET) {
+        for (int e = threadIdx.x; e < 2 * C; e += blockDim.x)
+            dgamma[(size_t)blockIdx.x * 2 * C + e] = ((red[e] + red[2 * C + e]) + red[4 * C + e]) + red[6 * C + e];
+    } else {
     for (int e = threadIdx.x; e < C; e += blockDim.x) {
         atomicAdd(dgamma + e, red[e]);
         atomicAdd(dbeta + e, red[C + e]);
+    }
     }
 }
 
@@ -342,7 +357,9 @@ __global__ __launch_bounds__(32 * LPP) void leff_dwconv_fwd_kernel(const T* __re
 // Written over p, BOTH sums use the same nine dt neighbours of a position and only its own u: the tile stages dt (with a
 // one-pixel halo) in LDS, u is read once per position straight into registers and one GELU evaluation yields g and g'.
 // (The earlier form staged gelu(u) with a halo as well: 19 LDS reads and 2.4 GELU evaluations per element, 3.6 TB/s.)
-template <typename T, int LPP>
+// DET (deterministic mode, common.h): workgroup slot `wslot` STORES its sums at dw / db + wslot * 10 Ch (both point into the workspace);
+// wg_per_cg is then a function of the shape
+template <typename T, int LPP, bool DET = false>
 __global__ __launch_bounds__(32 * LPP, LPP == 8 ? DWB_WAVES : 4) void leff_dwconv_bwd_kernel(const T* __restrict__ dz, const T* __restrict__ u,
                                                               const T* __restrict__ tpre, const float* __restrict__ w,
                                                               T* __restrict__ du, float* __restrict__ dw,
@@ -467,13 +484,15 @@ __global__ __launch_bounds__(32 * LPP, LPP == 8 ? DWB_WAVES : 4) void leff_dwcon
             float sum = 0.f;
 #pragma unroll
             for (int p = 0; p < 32; ++p) sum += red5[(q * 32 + p) * CT + c];
-            if (kk < 9) atomicAdd(dw + (cg * CT + c) * 9 + kk, sum);
-            else atomicAdd(db + cg * CT + c, sum);
+            const size_t det_off = DET ? (size_t)wslot * 10 * Ch : 0;
+            if (kk < 9) dhz_accum<DET>(dw + det_off + (cg * CT + c) * 9 + kk, sum);
+            else dhz_accum<DET>(db + det_off + cg * CT + c, sum);
         }
     }
 }
 
 // ------------------------------------------------------------------------------------------------ K10
+template <bool DET>          // deterministic mode: the workgroup stores its sum at loss_sum[blockIdx.x] (the workspace)
 __global__ __launch_bounds__(256) void charbonnier_fwd_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                               float* __restrict__ clampd, float* __restrict__ loss_sum,
                                                               int64_t n4, float eps2, int clamp01) {
@@ -493,7 +512,7 @@ __global__ __launch_bounds__(256) void charbonnier_fwd_kernel(const float* __res
     s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(loss_sum, part[0] + part[1] + part[2] + part[3]);
+    if (threadIdx.x == 0) dhz_accum<DET>(loss_sum + (DET ? blockIdx.x : 0), part[0] + part[1] + part[2] + part[3]);
 }
 
 __global__ __launch_bounds__(256) void charbonnier_bwd_kernel(const float* __restrict__ x, const float* __restrict__ y,
@@ -518,6 +537,7 @@ __global__ __launch_bounds__(256) void charbonnier_bwd_kernel(const float* __res
 // The two L1 distances of one ContrastLoss feature tap (My_CR.py:108-112) in one pass over (a, p, n), and their joint
 // backward  da = c_p sign(a - p) + c_n sign(a - n)  (c_* = upstream gradient / N, read from device memory) in another -
 // instead of sub / abs / mean / sign / mul chains over feature maps of up to 134 MB each.
+template <bool DET>          // deterministic mode: the workgroup stores its two sums at sums[2 blockIdx.x ...] (the workspace)
 __global__ __launch_bounds__(256) void l1_pair_fwd_kernel(const float* __restrict__ a, const float* __restrict__ p,
                                                           const float* __restrict__ n, float* __restrict__ sums, int64_t n4) {
     __shared__ float part[2][4];
@@ -535,8 +555,9 @@ __global__ __launch_bounds__(256) void l1_pair_fwd_kernel(const float* __restric
     if ((threadIdx.x & 63) == 0) { part[0][threadIdx.x >> 6] = sp; part[1][threadIdx.x >> 6] = sn; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        atomicAdd(sums, part[0][0] + part[0][1] + part[0][2] + part[0][3]);
-        if (n) atomicAdd(sums + 1, part[1][0] + part[1][1] + part[1][2] + part[1][3]);
+        float* o = sums + (DET ? 2 * blockIdx.x : 0);
+        dhz_accum<DET>(o, part[0][0] + part[0][1] + part[0][2] + part[0][3]);
+        if (n) dhz_accum<DET>(o + 1, part[1][0] + part[1][1] + part[1][2] + part[1][3]);
     }
 }
 
@@ -741,9 +762,24 @@ extern "C" int dhz_ln_partition_bwd_lay2(const void* dxw, const void* x, const f
     const bool wide = dtype == DHZ_BF16 && wide_geometry(C, &lpw, &vpw) == 0;   // bf16: 8 channels (16 bytes) per lane
     if (wide) lpt = lpw;
     int grid = (int)(((int64_t)ntok * lpt + 256 * 8 - 1) / (256 * 8));
-    const int cap = 2 * dhz_num_cus();
+    const int cap = 2 * dhz_part_cus();
     grid = grid < 64 ? 64 : (grid > cap ? cap : grid);
     hipStream_t s = (hipStream_t)stream;
+    if (dhz_det()) {                     // one item per workgroup: the grid above is a function of the shape in this mode
+        const char* who = "dhz_ln_partition_bwd";
+        DHZ_REQUIRE(dtype == DHZ_F32, "%s: the deterministic mode covers fp32 storage only", who);
+        float* ws = dhz_det_ws(who, grid, 2 * C);
+        if (!ws) return DHZ_EINVAL;
+#define LAUNCHD(V) hipLaunchKernelGGL((ln_partition_bwd_kernel<V, float, false, true>), dim3(grid), dim3(256), 0, s, (const float*)dxw, (const float*)x, gamma, stats, (const float*)dres, (float*)dx, ws, nullptr, ntok, Hres, Wres, C, shift, lpt, partition, lay, (float*)dx2, scale2)
+        switch (vpl) { case 1: LAUNCHD(1); break; case 2: LAUNCHD(2); break; case 3: LAUNCHD(3); break; default: LAUNCHD(4); }
+#undef LAUNCHD
+        DHZ_CHECK_LAUNCH(who);
+        DetSegs segs{};
+        segs.n = 2;
+        segs.off[0] = 0; segs.len[0] = C; segs.dst[0] = dgamma;
+        segs.off[1] = C; segs.len[1] = C; segs.dst[1] = dbeta;
+        return dhz_det_reduce(who, ws, grid, 2 * C, segs, s);
+    }
     if (wide) {
 #define LAUNCHW(V) hipLaunchKernelGGL((ln_partition_bwd_kernel<V, bf16s, true>), dim3(grid), dim3(256), 0, s, (const bf16s*)dxw, (const bf16s*)x, gamma, stats, (const bf16s*)dres, (bf16s*)dx, dgamma, dbeta, ntok, Hres, Wres, C, shift, lpt, partition, lay, (bf16s*)dx2, scale2)
         if (vpw == 2) LAUNCHW(2); else LAUNCHW(4);
@@ -860,12 +896,29 @@ extern "C" int dhz_leff_dwconv_bwd_scaled_dt(const void* dz, const void* u, cons
     const int tiles_x = (Wres + TW - 1) / TW, tiles_y = (Hres + TH - 1) / TH;
     const int lpp = dw_lanes_per_position(DW_BWD_LPP, Ch);
     const int ntiles = B * tiles_x * tiles_y, ncg = Ch / (4 * lpp);
-    int wg_per_cg = (lpp == 16 ? 2 : DWB_WAVES) * dhz_num_cus() / ncg;   // one resident round: 3 (2 at 512 threads) workgroups per CU, persistent over tiles
+    int wg_per_cg = (lpp == 16 ? 2 : DWB_WAVES) * dhz_part_cus() / ncg;   // one resident round: 3 (2 at 512 threads) workgroups per CU, persistent over tiles
     if (wg_per_cg < 1) wg_per_cg = 1;
     if (wg_per_cg > ntiles) wg_per_cg = ntiles;
 #define DW_BWD(LPP_) hipLaunchKernelGGL((leff_dwconv_bwd_kernel<T, LPP_>), dim3(wg_per_cg * ncg), dim3(32 * LPP_), 0, (hipStream_t)stream,   \
                                         (const T*)dz, (const T*)u, (const T*)t, w, (T*)du, dw, db, dz_scale, B, Hres, Wres, Ch, tiles_x,      \
                                         tiles_y, wg_per_cg)
+    if (dhz_det()) {                     // one item per workgroup slot
+        const char* who = "dhz_leff_dwconv_bwd";
+        DHZ_REQUIRE(dtype == DHZ_F32, "%s: the deterministic mode covers fp32 storage only", who);
+        float* ws = dhz_det_ws(who, wg_per_cg, 10L * Ch);
+        if (!ws) return DHZ_EINVAL;
+#define DW_BWDD(LPP_) hipLaunchKernelGGL((leff_dwconv_bwd_kernel<float, LPP_, true>), dim3(wg_per_cg * ncg), dim3(32 * LPP_), 0, (hipStream_t)stream, \
+                                         (const float*)dz, (const float*)u, (const float*)t, w, (float*)du, ws, ws + 9L * Ch, dz_scale, B, Hres, Wres, \
+                                         Ch, tiles_x, tiles_y, wg_per_cg)
+        if (lpp == 16) DW_BWDD(16); else DW_BWDD(8);
+#undef DW_BWDD
+        DHZ_CHECK_LAUNCH(who);
+        DetSegs segs{};
+        segs.n = 2;
+        segs.off[0] = 0; segs.len[0] = 9L * Ch; segs.dst[0] = dw;
+        segs.off[1] = 9L * Ch; segs.len[1] = Ch; segs.dst[1] = db;
+        return dhz_det_reduce(who, ws, wg_per_cg, 10L * Ch, segs, (hipStream_t)stream);
+    }
     DT_SWITCH(dtype, "dhz_leff_dwconv_bwd", if (lpp == 16) DW_BWD(16); else DW_BWD(8));
 #undef DW_BWD
     DHZ_CHECK_LAUNCH("dhz_leff_dwconv_bwd");
@@ -883,7 +936,17 @@ extern "C" int dhz_leff_dwconv_bwd(const float* dz, const float* u, const float*
 extern "C" int dhz_charbonnier_fwd(const float* x, const float* y, float* clampd, float* loss_sum, int64_t n, float eps,
                                    int clamp01, void* stream) {
     DHZ_REQUIRE(x && y && loss_sum && n > 0 && n % 4 == 0, "dhz_charbonnier_fwd: bad arguments (n must be a multiple of 4)");
-    hipLaunchKernelGGL(charbonnier_fwd_kernel, dim3(grid_for(n / 4, 256, 1024)), dim3(256), 0, (hipStream_t)stream, x, y,
+    const int grid = grid_for(n / 4, 256, 1024);          // a function of n
+    if (dhz_det()) {                                      // one item per workgroup
+        float* ws = dhz_det_ws("dhz_charbonnier_fwd", grid, 1);
+        if (!ws) return DHZ_EINVAL;
+        hipLaunchKernelGGL(charbonnier_fwd_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, y, clampd, ws, n / 4, eps * eps, clamp01);
+        DHZ_CHECK_LAUNCH("dhz_charbonnier_fwd");
+        DetSegs segs{};
+        segs.n = 1; segs.off[0] = 0; segs.len[0] = 1; segs.dst[0] = loss_sum;
+        return dhz_det_reduce("dhz_charbonnier_fwd", ws, grid, 1, segs, (hipStream_t)stream);
+    }
+    hipLaunchKernelGGL(charbonnier_fwd_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, y,
                        clampd, loss_sum, n / 4, eps * eps, clamp01);
     DHZ_CHECK_LAUNCH("dhz_charbonnier_fwd");
     return DHZ_OK;
@@ -934,7 +997,17 @@ extern "C" int dhz_contrast_combine_bwd(const float* d, const float* w, int k, i
 
 extern "C" int dhz_l1_pair_fwd(const float* a, const float* p, const float* n, float* sums, int64_t count, void* stream) {
     DHZ_REQUIRE(a && p && sums && count > 0 && count % 4 == 0, "dhz_l1_pair_fwd: bad arguments (count must be a multiple of 4)");
-    hipLaunchKernelGGL(l1_pair_fwd_kernel, dim3(grid_for(count / 4, 256, 768)), dim3(256), 0, (hipStream_t)stream, a, p, n, sums,
+    const int grid = grid_for(count / 4, 256, 768);       // a function of count
+    if (dhz_det()) {                                      // one item per workgroup
+        float* ws = dhz_det_ws("dhz_l1_pair_fwd", grid, 2);
+        if (!ws) return DHZ_EINVAL;
+        hipLaunchKernelGGL(l1_pair_fwd_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a, p, n, ws, count / 4);
+        DHZ_CHECK_LAUNCH("dhz_l1_pair_fwd");
+        DetSegs segs{};
+        segs.n = 1; segs.off[0] = 0; segs.len[0] = n ? 2 : 1; segs.dst[0] = sums;
+        return dhz_det_reduce("dhz_l1_pair_fwd", ws, grid, 2, segs, (hipStream_t)stream);
+    }
+    hipLaunchKernelGGL(l1_pair_fwd_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a, p, n, sums,
                        count / 4);
     DHZ_CHECK_LAUNCH("dhz_l1_pair_fwd");
     return DHZ_OK;

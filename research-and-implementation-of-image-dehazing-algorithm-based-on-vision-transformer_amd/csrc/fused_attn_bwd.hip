@@ -561,6 +561,8 @@ extern "C" int dhz_fused_window_attn_bwd(const float* x, const float* dout, cons
     DHZ_REQUIRE(x && dout && gamma && beta && wqkv_p && bqkv && wt && rank && dx && dwq && dwk && dwv && dwo && dgamma && dbeta,
                 "dhz_fused_window_attn_bwd: null pointer");
     DHZ_REQUIRE(C_ == 32, "dhz_fused_window_attn_bwd: C=%d unsupported (32)", C_);
+    DHZ_REQUIRE(!dhz_det(), "dhz_fused_window_attn_bwd: not available in deterministic mode (its parameter gradients are fp32 atomics): "
+                            "use the backward chain, as dehaze_hip.fused does");
     DHZ_REQUIRE(B > 0 && Hres % 8 == 0 && Wres % 8 == 0 && Hres >= 8 && Wres >= 8 && shift >= 0 && shift < 8,
                 "dhz_fused_window_attn_bwd: bad geometry %dx%d shift %d", Hres, Wres, shift);
     DHZ_REQUIRE((bias != nullptr) == (dbias_part != nullptr), "dhz_fused_window_attn_bwd: bias and dbias_part go together");

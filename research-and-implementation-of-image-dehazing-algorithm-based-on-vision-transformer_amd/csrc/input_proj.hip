@@ -58,7 +58,9 @@ __global__ __launch_bounds__(256) void input_proj_fwd_kernel(const float* __rest
 // read straight out of the halo tile,
 // wave w contracts pixels 64 w .. 64 w + 63, accumulators live across the tiles of a persistent workgroup, one cross-wave
 // reduction and one atomic per output and workgroup at the end.
-template <int E, typename T>
+// DET (deterministic mode, common.h): the workgroup STORES its 28 E sums at dw / db + blockIdx.x * 28 E (both point into the workspace); the
+// grid is then a function of the shape
+template <int E, typename T, bool DET = false>
 __global__ __launch_bounds__(256) void input_proj_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ y,
                                                              const float* __restrict__ img, float* __restrict__ dw,
                                                              float* __restrict__ db, int H, int W, float slope, int tiles_x,
@@ -128,8 +130,9 @@ __global__ __launch_bounds__(256) void input_proj_bwd_kernel(const T* __restrict
     for (int o = t; o < E * 28; o += 256) {
         const int co = o / 28, tap = o % 28;
         const float v = red[co * 32 + tap] + red[(E + co) * 32 + tap] + red[(2 * E + co) * 32 + tap] + red[(3 * E + co) * 32 + tap];
-        if (tap < 27) atomicAdd(dw + co * 27 + tap, v);
-        else atomicAdd(db + co, v);
+        const size_t det_off = DET ? (size_t)blockIdx.x * 28 * E : 0;
+        if (tap < 27) dhz_accum<DET>(dw + det_off + co * 27 + tap, v);
+        else dhz_accum<DET>(db + det_off + co, v);
     }
 }
 
@@ -165,9 +168,24 @@ extern "C" int dhz_input_proj_bwd_dt(const void* dy, const void* y, const float*
     DHZ_REQUIRE(B > 0 && H > 0 && W > 0 && (E == 16 || E == 32 || E == 64), "dhz_input_proj_bwd: E=%d (supported: 16, 32, 64)", E);
     const int tiles_x = (W + TS - 1) / TS, tiles_y = (H + 8 - 1) / 8;
     const int ntiles = B * tiles_x * tiles_y;
-    const int ncu = dhz_num_cus();
+    const int ncu = dhz_part_cus();
     const int grid = ntiles < ncu ? ntiles : ncu;      // every workgroup ends with 28 E same-address atomics: keep them few
     hipStream_t s = (hipStream_t)stream;
+    if (dhz_det()) {                                   // one item per workgroup; slot = [dw 27 E | db E]
+        const char* who = "dhz_input_proj_bwd";
+        DHZ_REQUIRE(dtype == DHZ_F32, "%s: the deterministic mode covers fp32 storage only", who);
+        float* ws = dhz_det_ws(who, grid, 28L * E);
+        if (!ws) return DHZ_EINVAL;
+#define LAUNCHD(EE) hipLaunchKernelGGL((input_proj_bwd_kernel<EE, float, true>), dim3(grid), dim3(256), 0, s, (const float*)dy, (const float*)y, img, ws, ws + 27 * EE, H, W, slope, tiles_x, tiles_y, ntiles)
+        if (E == 16) LAUNCHD(16); else if (E == 32) LAUNCHD(32); else LAUNCHD(64);
+#undef LAUNCHD
+        DHZ_CHECK_LAUNCH(who);
+        DetSegs segs{};
+        segs.n = 2;
+        segs.off[0] = 0; segs.len[0] = 27L * E; segs.dst[0] = dw;
+        segs.off[1] = 27L * E; segs.len[1] = E; segs.dst[1] = db;
+        return dhz_det_reduce(who, ws, grid, 28L * E, segs, s);
+    }
 #define LAUNCH(EE) hipLaunchKernelGGL((input_proj_bwd_kernel<EE, T>), dim3(grid), dim3(256), 0, s, (const T*)dy, (const T*)y, img, dw, db, H, W, slope, tiles_x, tiles_y, ntiles)
     DT_SWITCH(dtype, "dhz_input_proj_bwd", if (E == 16) LAUNCH(16); else if (E == 32) LAUNCH(32); else LAUNCH(64));
 #undef LAUNCH

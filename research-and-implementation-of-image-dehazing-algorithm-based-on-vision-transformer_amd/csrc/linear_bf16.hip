@@ -537,6 +537,7 @@ extern "C" int dhz_linear_dgrad_bf16(const void* dy, int ldy, const void* w, voi
 extern "C" int dhz_linear_wgrad_bf16(const void* dy, int ldy, const void* x, int ldx, int T, int nmat, int nper, int K,
                                      float* const* dw, float* const* db, void* stream) {
     DHZ_REQUIRE(dy && x && dw, "dhz_linear_wgrad_bf16: null pointer");
+    DHZ_REQUIRE(!dhz_det(), "dhz_linear_wgrad_bf16: not available in deterministic mode (fp32 storage only)");
     DHZ_REQUIRE(nmat >= 1 && nmat <= MAXMAT, "dhz_linear_wgrad_bf16: nmat=%d must be 1..%d", nmat, MAXMAT);
     WgradOut out = {};
     for (int i = 0; i < nmat; ++i) {

@@ -467,7 +467,7 @@ int dispatch(const char* who, const float* A, int lda, const float* W, int ldw, 
     {
         static const int cand[6][2] = {{4, 4}, {4, 2}, {2, 4}, {2, 2}, {4, 1}, {2, 1}};
         long best_blocks = -1;
-        const long slots = 2 * dhz_num_cus();
+        const long slots = 2 * dhz_part_cus();               // (a tile choice: a function of the shape in deterministic mode)
         for (int i = 0; i < 6; ++i) {
             const int a = cand[i][0], b = cand[i][1];
             if (N % (32 * b)) continue;

@@ -336,7 +336,7 @@ int dispatch_split(const char* who, const float* A, int lda, const float* B, int
     }
     const int wn = (NF % 128 == 0 && terms == 3) ? 4 : 2;      // (128-column tiles at 96 KB / one workgroup per CU: slower, measured)
     const long blocks128 = (long)((M + 127) / 128) * (NF / (32 * wn));
-    const int wm = blocks128 >= dhz_num_cus() ? 4 : 2;
+    const int wm = blocks128 >= dhz_part_cus() ? 4 : 2;       // (a tile choice: a function of the shape in deterministic mode)
 #define CASE(a, b) \
     if (wm == a && wn == b) {                                                                              \
         if (terms == 3) launch_split<a, b, BTR, false>(A, lda, B, ldb, bias, C, ldc, M, NF, KC, epi, epi_on, s);        \
@@ -357,9 +357,10 @@ struct WgradOut {
     float* dw[MAXMAT];
     float* db[MAXMAT];
     int nper;
+    long det_stride;      // DET instances: floats between the workspace slots of two token slabs (common.h)
 };
 
-template <int WM, int WN, bool SIX>
+template <int WM, int WN, bool SIX, bool DET = false>
 __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(const float* __restrict__ dy, int ldy, const float* __restrict__ x,
                                                              int ldx, int T, int N, int K, WgradOut out, int nsplit,
                                                              const float* __restrict__ row_scale, int rows_per_scale) {
@@ -383,8 +384,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(const float* __rest
     const int tn = bid % tiles_n, tm = bid / tiles_n;
     const int n0 = tm * FM, k0 = tn * FN;
     const int mat = n0 / out.nper, nloc = n0 - mat * out.nper;
-    float* __restrict__ const dw = out.dw[mat];
-    float* __restrict__ const db = out.db[mat];
+    const size_t det_off = DET ? (size_t)split * out.det_stride : 0;          // deterministic mode: this slab's slot of the workspace
+    float* __restrict__ const dw = out.dw[mat] + det_off;
+    float* __restrict__ const db = out.db[mat] ? out.db[mat] + det_off : nullptr;
     const int nst = T / BK;
     const int st0 = (int)((long long)nst * split / nsplit), st1 = (int)((long long)nst * (split + 1) / nsplit);
 
@@ -499,7 +501,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(const float* __rest
 #pragma unroll
             for (int j = 0; j < 4; ++j) Cs[(wm * WM * 16 + a * 16 + 4 * g + j) * FN + wn * WN * 16 + b * 16 + i16] = acc[a][b][j];
     __syncthreads();
-    for (int e = t; e < FM * FN; e += 256) atomicAdd(dw + (size_t)(nloc + e / FN) * K + k0 + e % FN, Cs[e]);
+    for (int e = t; e < FM * FN; e += 256) dhz_accum<DET>(dw + (size_t)(nloc + e / FN) * K + k0 + e % FN, Cs[e]);
     if (do_db) {
         __syncthreads();
         float* red = reinterpret_cast<float*>(smem);          // [256 / (FM/8)][FM]
@@ -510,7 +512,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(const float* __rest
         if (t < FM) {
             float tot = 0.f;
             for (int r = 0; r < 256 / CPR; ++r) tot += red[r * FM + t];
-            atomicAdd(db + nloc + t, tot);
+            dhz_accum<DET>(db + nloc + t, tot);
         }
     }
 }
@@ -531,7 +533,7 @@ constexpr int BK2 = 32;
 // atomics: half the fp32 atomics of the launch (2 x 256 workgroups x FM x FN floats, ~2.7 ps each whatever the shape: 6 - 12 us of the
 // launches below 50 us, tools/variants.sh with DHZ_W6_ABL = 32).  The groups share the one barrier per stage; the group with the
 // shorter slab (by at most one stage) pays the difference with bare barriers.
-template <int WM, int WN, int WAVES_M, int WAVES_N, int G = 1>
+template <int WM, int WN, int WAVES_M, int WAVES_N, int G = 1, bool DET = false>
 __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * G, WAVES_M * WAVES_N == 4 ? 2 : 1) void wgrad_split6_kernel(const float* __restrict__ dy, int ldy, const float* __restrict__ x,
                                                               int ldx, int T, int N, int K, WgradOut out, int nsplit,
                                                               const float* __restrict__ row_scale, int rows_per_scale) {
@@ -554,8 +556,9 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * G, WAVES_M * WAVES_N == 4 
     const int tn = bid % tiles_n, tm = bid / tiles_n;
     const int n0 = tm * FM, k0 = tn * FN;
     const int mat = n0 / out.nper, nloc = n0 - mat * out.nper;
-    float* __restrict__ const dw = out.dw[mat];
-    float* __restrict__ const db = out.db[mat];
+    const size_t det_off = DET ? (size_t)split * out.det_stride : 0;          // deterministic mode: this slab's slot of the workspace
+    float* __restrict__ const dw = out.dw[mat] + det_off;
+    float* __restrict__ const db = out.db[mat] ? out.db[mat] + det_off : nullptr;
     const int nst = T / BK2, nslab = nsplit * G, slab = split * G + grp;
     const int st0 = (int)((long long)nst * slab / nslab), st1 = (int)((long long)nst * (slab + 1) / nslab);
     int idle = 0;                                                           // stages the OTHER group of the pair runs beyond this one's
@@ -741,7 +744,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * G, WAVES_M * WAVES_N == 4 
     const int tt = threadIdx.x;
     if constexpr (DHZ_W6_ABL & 32) { if (Cs[tt] == 123.456f) dw[tt] = 1.f; }
     else
-    for (int e = tt; e < FM * FN; e += NT * G) atomicAdd(dw + (size_t)(nloc + e / FN) * K + k0 + e % FN, Cs[e]);
+    for (int e = tt; e < FM * FN; e += NT * G) dhz_accum<DET>(dw + (size_t)(nloc + e / FN) * K + k0 + e % FN, Cs[e]);
     if (do_db) {
         __syncthreads();
         float* red = reinterpret_cast<float*>(smem_all);      // [rows of chunks][FM]
@@ -756,7 +759,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * G, WAVES_M * WAVES_N == 4 
         if (tt < FM) {
             float tot = 0.f;
             for (int r = 0; r < G * NT * NA / CPR; ++r) tot += red[r * FM + tt];
-            atomicAdd(db + nloc + tt, tot);
+            dhz_accum<DET>(db + nloc + tt, tot);
         }
     }
 }
@@ -769,8 +772,8 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * G, WAVES_M * WAVES_N == 4 
                                        // stages pairing measured +3 % (T = 32768, N = 1024, K = 256: 106.9 -> 110.7 us)
 #endif
 template <int WM, int WN, int WAVES_M, int WAVES_N, int G>
-void launch_wgrad_split6_g(const float* dy, int ldy, const float* x, int ldx, int T, int N, int K, const WgradOut& out,
-                           const float* row_scale, int rows_per_scale, int tiles, int nwg, hipStream_t s) {
+int launch_wgrad_split6_g(const float* dy, int ldy, const float* x, int ldx, int T, int N, int K, const WgradOut& out,
+                          const float* row_scale, int rows_per_scale, int tiles, int nwg, hipStream_t s) {
     constexpr int FM = 16 * WM * WAVES_M, FN = 16 * WN * WAVES_N, NT = 64 * WAVES_M * WAVES_N;
     constexpr size_t stage = (size_t)BK2 * (FM + FN) * 2 * 3;
     constexpr size_t ring = 2 * G * stage;
@@ -778,44 +781,69 @@ void launch_wgrad_split6_g(const float* dy, int ldy, const float* x, int ldx, in
     if (smem > 48 * 1024)
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_split6_kernel<WM, WN, WAVES_M, WAVES_N, G>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if (dhz_det()) {                 // one item per workgroup of a tile (G = 2: its two slabs meet in LDS in a fixed order)
+        const char* who = "dhz_linear_wgrad_split";
+        WgradOut o2; DetSegs segs; float* ws; long slot;
+        if (int rc = dhz_det_wgrad_begin(who, out, N / out.nper, K, nwg, o2, segs, ws, slot)) return rc;
+        if (smem > 48 * 1024)
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_split6_kernel<WM, WN, WAVES_M, WAVES_N, G, true>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        hipLaunchKernelGGL((wgrad_split6_kernel<WM, WN, WAVES_M, WAVES_N, G, true>), dim3(tiles * nwg), dim3(NT * G), smem, s, dy, ldy, x, ldx, T, N,
+                           K, o2, nwg, row_scale, rows_per_scale);
+        DHZ_CHECK_LAUNCH(who);
+        return dhz_det_reduce(who, ws, nwg, slot, segs, s);
+    }
     hipLaunchKernelGGL((wgrad_split6_kernel<WM, WN, WAVES_M, WAVES_N, G>), dim3(tiles * nwg), dim3(NT * G), smem, s, dy, ldy, x, ldx, T, N, K,
                        out, nwg, row_scale, rows_per_scale);
+    return DHZ_OK;
 }
 
 template <int WM, int WN, int WAVES_M, int WAVES_N>
-void launch_wgrad_split6(const float* dy, int ldy, const float* x, int ldx, int T, int N, int K, const WgradOut& out,
+int launch_wgrad_split6(const float* dy, int ldy, const float* x, int ldx, int T, int N, int K, const WgradOut& out,
                          const float* row_scale, int rows_per_scale, hipStream_t s) {
     constexpr int FM = 16 * WM * WAVES_M, FN = 16 * WN * WAVES_N, NT = 64 * WAVES_M * WAVES_N;
     const int tiles = (N / FM) * (K / FN);
-    int nsplit = (NT == 256 ? 2 : 1) * dhz_num_cus() / tiles;            // token slabs per tile
+    int nsplit = (NT == 256 ? 2 : 1) * dhz_part_cus() / tiles;           // token slabs per tile
     const int max_split = T / (BK2 * 8) > 0 ? T / (BK2 * 8) : 1;          // at least 8 stages per slab
     if (nsplit > max_split) nsplit = max_split;
     if (nsplit < 1) nsplit = 1;
     if constexpr (NT == 256) {
         if (DHZ_W6_PAIR && nsplit >= 2 && (nsplit % 2 == 0 || nsplit >= 16) && T / BK2 / nsplit <= DHZ_W6_PAIR_MAX_STAGES) {      // (an odd count loses a slab)
-            launch_wgrad_split6_g<WM, WN, WAVES_M, WAVES_N, 2>(dy, ldy, x, ldx, T, N, K, out, row_scale, rows_per_scale, tiles, nsplit / 2, s);
-            return;
+            return launch_wgrad_split6_g<WM, WN, WAVES_M, WAVES_N, 2>(dy, ldy, x, ldx, T, N, K, out, row_scale, rows_per_scale, tiles, nsplit / 2, s);
         }
     }
-    launch_wgrad_split6_g<WM, WN, WAVES_M, WAVES_N, 1>(dy, ldy, x, ldx, T, N, K, out, row_scale, rows_per_scale, tiles, nsplit, s);
+    return launch_wgrad_split6_g<WM, WN, WAVES_M, WAVES_N, 1>(dy, ldy, x, ldx, T, N, K, out, row_scale, rows_per_scale, tiles, nsplit, s);
 }
 
 template <int WM, int WN, bool SIX>
-void launch_wgrad_split(const float* dy, int ldy, const float* x, int ldx, int T, int N, int K, const WgradOut& out,
+int launch_wgrad_split(const float* dy, int ldy, const float* x, int ldx, int T, int N, int K, const WgradOut& out,
                         const float* row_scale, int rows_per_scale, hipStream_t s) {
     constexpr int FM = 32 * WM, FN = 32 * WN;
     constexpr size_t stage = (size_t)BK * (FM + FN) * 2 * (SIX ? 3 : 2);     // hi, (mid,) lo images of both operands
     constexpr size_t smem = stage > (size_t)FM * FN * 4 ? stage : (size_t)FM * FN * 4;
     const int tiles = (N / FM) * (K / FN);
-    int nsplit = 2 * dhz_num_cus() / tiles;
+    int nsplit = 2 * dhz_part_cus() / tiles;
     const int max_split = T / (BK * 4) > 0 ? T / (BK * 4) : 1;           // at least 4 stages per workgroup
     if (nsplit > max_split) nsplit = max_split;
     if (nsplit < 1) nsplit = 1;
     if (smem > 48 * 1024)
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_split_kernel<WM, WN, SIX>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)smem);
+    if (dhz_det()) {
+        const char* who = "dhz_linear_wgrad_split";
+        WgradOut o2; DetSegs segs; float* ws; long slot;
+        if (int rc = dhz_det_wgrad_begin(who, out, N / out.nper, K, nsplit, o2, segs, ws, slot)) return rc;
+        if (smem > 48 * 1024)
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_split_kernel<WM, WN, SIX, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)smem);
+        hipLaunchKernelGGL((wgrad_split_kernel<WM, WN, SIX, true>), dim3(tiles * nsplit), dim3(256), smem, s, dy, ldy, x, ldx, T, N, K, o2, nsplit,
+                           row_scale, rows_per_scale);
+        DHZ_CHECK_LAUNCH(who);
+        return dhz_det_reduce(who, ws, nsplit, slot, segs, s);
+    }
     hipLaunchKernelGGL((wgrad_split_kernel<WM, WN, SIX>), dim3(tiles * nsplit), dim3(256), smem, s, dy, ldy, x, ldx, T, N, K, out, nsplit,
                        row_scale, rows_per_scale);
+    return DHZ_OK;
 }
 
 }  // namespace
@@ -875,22 +903,26 @@ extern "C" int dhz_linear_wgrad_split(const float* dy, int ldy, const float* x, 
         // per product, and measured -3..-7 % on the four largest shapes of the step, +25..50 % on the small ones
         // (profiles/r04_wgrad6_ablation.txt): not dispatched; DHZ_WGRAD6_TILE=1 / 2 selects them for measurements.
         static const int big = getenv("DHZ_WGRAD6_TILE") ? atoi(getenv("DHZ_WGRAD6_TILE")) : 0;
-        if (big && nper % 256 == 0 && K % 128 == 0) launch_wgrad_split6<4, 4, 4, 2>(dy, ldy, x, ldx, T, N, K, out, row_scale, rps, s);
-        else if (big && nper % 128 == 0 && K % 256 == 0) launch_wgrad_split6<4, 4, 2, 4>(dy, ldy, x, ldx, T, N, K, out, row_scale, rps, s);
-        else if (big == 2 && nper % 128 == 0 && K % 128 == 0) launch_wgrad_split6<2, 4, 4, 2>(dy, ldy, x, ldx, T, N, K, out, row_scale, rps, s);
-        else if (wm6 == 4) launch_wgrad_split6<4, 2, 2, 2>(dy, ldy, x, ldx, T, N, K, out, row_scale, rps, s);
-        else if (wn6 == 4) launch_wgrad_split6<2, 4, 2, 2>(dy, ldy, x, ldx, T, N, K, out, row_scale, rps, s);
-        else launch_wgrad_split6<2, 2, 2, 2>(dy, ldy, x, ldx, T, N, K, out, row_scale, rps, s);
+        int rc;
+        if (big && nper % 256 == 0 && K % 128 == 0) rc = launch_wgrad_split6<4, 4, 4, 2>(dy, ldy, x, ldx, T, N, K, out, row_scale, rps, s);
+        else if (big && nper % 128 == 0 && K % 256 == 0) rc = launch_wgrad_split6<4, 4, 2, 4>(dy, ldy, x, ldx, T, N, K, out, row_scale, rps, s);
+        else if (big == 2 && nper % 128 == 0 && K % 128 == 0) rc = launch_wgrad_split6<2, 4, 4, 2>(dy, ldy, x, ldx, T, N, K, out, row_scale, rps, s);
+        else if (wm6 == 4) rc = launch_wgrad_split6<4, 2, 2, 2>(dy, ldy, x, ldx, T, N, K, out, row_scale, rps, s);
+        else if (wn6 == 4) rc = launch_wgrad_split6<2, 4, 2, 2>(dy, ldy, x, ldx, T, N, K, out, row_scale, rps, s);
+        else rc = launch_wgrad_split6<2, 2, 2, 2>(dy, ldy, x, ldx, T, N, K, out, row_scale, rps, s);
+        if (rc) return rc;
         DHZ_CHECK_LAUNCH(who);
         return DHZ_OK;
     }
 #define CASE(a, b) \
     if (wm == a && wn == b) {                                                                                  \
-        if (terms == 3) launch_wgrad_split<a, b, false>(dy, ldy, x, ldx, T, N, K, out, row_scale, rps, s);     \
-        else launch_wgrad_split<a, b, true>(dy, ldy, x, ldx, T, N, K, out, row_scale, rps, s);                 \
+        if (terms == 3) rc = launch_wgrad_split<a, b, false>(dy, ldy, x, ldx, T, N, K, out, row_scale, rps, s);     \
+        else rc = launch_wgrad_split<a, b, true>(dy, ldy, x, ldx, T, N, K, out, row_scale, rps, s);                 \
     }
+    int rc = DHZ_OK;
     CASE(4, 4) CASE(4, 2) CASE(2, 4) CASE(2, 2)
 #undef CASE
+    if (rc) return rc;
     DHZ_CHECK_LAUNCH(who);
     return DHZ_OK;
 }

@@ -32,11 +32,12 @@ struct WgradOut {
     int nper;
     const float* rs;    // optional row scale of dy: row t is multiplied by rs[t / rps] (DropPath scale of its image); rps % TK == 0
     int rps;
+    long det_stride;    // DET instances: floats between the workspace slots of two token slabs (common.h)
 };
 
 // WM, WN: 16x16 tiles per wave along N (rows of dW) and K (cols of dW); waves are NWM x 2 (NWM = 2: 256 threads,
 // NWM = 4: 512 threads and a 256-row tile - twice the FLOP per staged byte for the compute-bound shapes)
-template <int WM, int WN, int NWM, int TG>
+template <int WM, int WN, int NWM, int TG, bool DET = false>
 __global__ __launch_bounds__(128 * NWM * TG) void linear_wgrad_kernel(const float* __restrict__ dy, int ldy,
                                                                 const float* __restrict__ x, int ldx, int T, int N,
                                                                 int K, WgradOut out, int nsplit) {
@@ -70,8 +71,9 @@ __global__ __launch_bounds__(128 * NWM * TG) void linear_wgrad_kernel(const floa
     const int tn = bid % tiles_n, tm = bid / tiles_n;
     const int n0 = tm * BM, k0 = tn * BN;
     const int mat = n0 / out.nper, nloc = n0 - mat * out.nper;       // BM divides nper: a tile never straddles two parameters
-    float* __restrict__ const dw = out.dw[mat];
-    float* __restrict__ const db = out.db[mat];
+    const size_t det_off = DET ? (size_t)split * out.det_stride : 0;          // deterministic mode: this slab's slot of the workspace
+    float* __restrict__ const dw = out.dw[mat] + det_off;
+    float* __restrict__ const db = out.db[mat] ? out.db[mat] + det_off : nullptr;
     // token slab of this workgroup (multiples of TK); its stages are dealt round-robin to the TG token groups
     const int nst = T / TK;
     const int st0 = (int)((long long)nst * split / nsplit), st1 = (int)((long long)nst * (split + 1) / nsplit);
@@ -208,7 +210,7 @@ __global__ __launch_bounds__(128 * NWM * TG) void linear_wgrad_kernel(const floa
         int e = i + rot;
         if (e >= BM * BN) e -= BM * BN;
         const int r = e / BN, c = e % BN;
-        if (!(WG_ABL & 1) || Cs[e] == 12345.678f) atomicAdd(dw + (size_t)(nloc + r) * K + k0 + c, Cs[e]);
+        if (!(WG_ABL & 1) || Cs[e] == 12345.678f) dhz_accum<DET>(dw + (size_t)(nloc + r) * K + k0 + c, Cs[e]);
     }
     if (do_db) {
         // staged element e = tl + GT i sits at (row e / A4, float4-column e % A4) of every stage: dump the
@@ -223,7 +225,7 @@ __global__ __launch_bounds__(128 * NWM * TG) void linear_wgrad_kernel(const floa
             const int c4 = t / 4, comp = t % 4;
             float tot = 0.f;
             for (int r = 0; r < TG * TK; ++r) tot += smem[(r * A4 + c4) * 4 + comp];
-            atomicAdd(db + nloc + t, tot);
+            dhz_accum<DET>(db + nloc + t, tot);
         }
     }
 }
@@ -244,7 +246,7 @@ int launch(const float* dy, int ldy, const float* x, int ldx, int T, int N, int 
     // Workgroups are dealt in whole rounds over the 256 CUs: the count must not exceed the resident slots (a 257th
     // 512-thread workgroup, or a 513th 256-thread one, runs alone after the others: measured 198 -> 130 us at
     // T=8192, N=1536, K=512 with 12 tiles x 43 splits = 516 workgroups), so the split count is rounded DOWN.
-    const int ncu = dhz_num_cus();
+    const int ncu = dhz_part_cus();
     int target = env_target > 0 ? env_target : (NWM * TG == 4 ? ncu : 2 * ncu);   // 2 (1 for 512 threads) workgroups per CU
     if (2 * smem > 160 * 1024 && target > ncu) target = ncu;
     int nsplit = target / tiles;
@@ -262,6 +264,18 @@ int launch(const float* dy, int ldy, const float* x, int ldx, int T, int N, int 
     if (smem > 48 * 1024)
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_wgrad_kernel<WM, WN, NWM, TG>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if (dhz_det()) {
+        const char* who = "dhz_linear_wgrad";
+        WgradOut o2; DetSegs segs; float* ws; long slot;
+        if (int rc = dhz_det_wgrad_begin(who, out, N / out.nper, K, nsplit, o2, segs, ws, slot)) return rc;
+        if (smem > 48 * 1024)
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_wgrad_kernel<WM, WN, NWM, TG, true>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        hipLaunchKernelGGL((linear_wgrad_kernel<WM, WN, NWM, TG, true>), dim3(tiles * nsplit), dim3(128 * NWM * TG), smem, s, dy, ldy, x,
+                           ldx, T, N, K, o2, nsplit);
+        DHZ_CHECK_LAUNCH(who);
+        return dhz_det_reduce(who, ws, nsplit, slot, segs, s);
+    }
     hipLaunchKernelGGL((linear_wgrad_kernel<WM, WN, NWM, TG>), dim3(tiles * nsplit), dim3(128 * NWM * TG), smem, s, dy, ldy, x,
                        ldx, T, N, K, out, nsplit);
     return 0;
@@ -269,6 +283,7 @@ int launch(const float* dy, int ldy, const float* x, int ldx, int T, int N, int 
 
 // Narrow shapes (parameter rows or columns a multiple of 16 but not of 32: the embed_dim = 16 model): 16 x 16 tiles of dW, one wave per
 // tile and token slab, operands straight from global memory (lanes along the features: 64-byte runs), fp32 atomics at the end.
+template <bool DET>
 __global__ __launch_bounds__(256) void narrow_wgrad_kernel(const float* __restrict__ dy, int ldy, const float* __restrict__ x, int ldx,
                                                            int T, int N, int K, WgradOut out, int nslab) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, i16 = lane & 15, g = lane >> 4;
@@ -291,12 +306,13 @@ __global__ __launch_bounds__(256) void narrow_wgrad_kernel(const float* __restri
             acc = mfma16(a, x[tk * ldx + k0 + i16], acc);
         }
     }
+    const long det_off = DET ? slab * out.det_stride : 0;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) atomicAdd(out.dw[mat] + (long)(nloc + 4 * g + j) * K + k0 + i16, acc[j]);
+    for (int j = 0; j < 4; ++j) dhz_accum<DET>(out.dw[mat] + det_off + (long)(nloc + 4 * g + j) * K + k0 + i16, acc[j]);
     if (out.db[mat] && k0 == 0) {
         bsum += __shfl_xor(bsum, 16);
         bsum += __shfl_xor(bsum, 32);
-        if (g == 0) atomicAdd(out.db[mat] + nloc + i16, bsum);
+        if (g == 0) dhz_accum<DET>(out.db[mat] + det_off + nloc + i16, bsum);
     }
 }
 
@@ -312,7 +328,14 @@ static int wgrad_dispatch(const char* who, const float* dy, int ldy, const float
         int nslab = 2048 / groups;                                                             // ~2048 workgroups, slabs of >= 64 tokens
         if (nslab > T / 64) nslab = T / 64;
         if (nslab < 1) nslab = 1;
-        hipLaunchKernelGGL(narrow_wgrad_kernel, dim3(groups * nslab), dim3(256), 0, s, dy, ldy, x, ldx, T, N, K, out, nslab);
+        if (dhz_det()) {                       // (the slab count is a function of the shape already)
+            WgradOut o2; DetSegs segs; float* ws; long slot;
+            if (int rc = dhz_det_wgrad_begin(who, out, nmat, K, nslab, o2, segs, ws, slot)) return rc;
+            hipLaunchKernelGGL(narrow_wgrad_kernel<true>, dim3(groups * nslab), dim3(256), 0, s, dy, ldy, x, ldx, T, N, K, o2, nslab);
+            DHZ_CHECK_LAUNCH(who);
+            return dhz_det_reduce(who, ws, nslab, slot, segs, s);
+        }
+        hipLaunchKernelGGL(narrow_wgrad_kernel<false>, dim3(groups * nslab), dim3(256), 0, s, dy, ldy, x, ldx, T, N, K, out, nslab);
         DHZ_CHECK_LAUNCH(who);
         return DHZ_OK;
     }
@@ -330,16 +353,18 @@ static int wgrad_dispatch(const char* who, const float* dy, int ldy, const float
 #endif
     const int bm = 32 * wm, bn = 32 * wn;
     const int tiles = (N / bm) * (K / bn);
-    const int splits2 = dhz_num_cus() / tiles > 0 ? dhz_num_cus() / tiles : 1;
+    const int splits2 = dhz_part_cus() / tiles > 0 ? dhz_part_cus() / tiles : 1;
     const bool two = tg_env ? tg_env == 2 : (T / TK) / splits2 >= 8;
 #define CASE(a, b)                                                               \
     if (wm == a && wn == b) {                                                    \
-        if (two) launch<a, b, 2, 2>(dy, ldy, x, ldx, T, N, K, out, s);           \
-        else launch<a, b>(dy, ldy, x, ldx, T, N, K, out, s);                     \
+        if (two) rc = launch<a, b, 2, 2>(dy, ldy, x, ldx, T, N, K, out, s);      \
+        else rc = launch<a, b>(dy, ldy, x, ldx, T, N, K, out, s);                \
     }
+    int rc = DHZ_OK;
     CASE(1, 1) CASE(1, 2) CASE(1, 4) CASE(2, 1) CASE(2, 2) CASE(2, 4) CASE(3, 1) CASE(3, 2) CASE(3, 4)
     CASE(4, 1) CASE(4, 2) CASE(4, 4)
 #undef CASE
+    if (rc) return rc;
     DHZ_CHECK_LAUNCH(who);
     return DHZ_OK;
 }

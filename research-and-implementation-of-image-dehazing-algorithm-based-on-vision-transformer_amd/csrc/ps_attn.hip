@@ -613,6 +613,8 @@ __global__ void bias_gather_multi_kernel(const BiasMulti d) {
 // a workgroup's slice of the partial tiles p0, p0 + stride, ...: thread t sums float4 elements t, 256 + t, 512 + t, 768 + t of the tiles -
 // the four loads of a tile (and of the next one: unrolled by two) in flight together; one load per iteration was a chain of dependent
 // latencies, 96 us for the step's 18 tables - and folds its 16 (i, j) sums onto the 225 table rows in LDS.
+// DET (deterministic mode, common.h): tab holds the whole 64 x 64 sum instead (plain stores); the caller folds it in a fixed order.
+template <bool DET = false>
 __device__ __forceinline__ void table_grad_fold(const float* __restrict__ part, int parts, int p0, int stride, float* tab, int t) {
     float4 s[4];
 #pragma unroll
@@ -629,6 +631,7 @@ __device__ __forceinline__ void table_grad_fold(const float* __restrict__ part, 
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int e = (q * 256 + t) * 4, i = e >> 6, j = e & 63;      // 4 consecutive j in the same row i
+        if constexpr (DET) { *reinterpret_cast<float4*>(&tab[e]) = s[q]; continue; }
         const int rel = ((i >> 3) - (j >> 3) + 7) * 15 + ((i & 7) - (j & 7) + 7);
         atomicAdd(&tab[rel], s[q].x); atomicAdd(&tab[rel - 1], s[q].y); atomicAdd(&tab[rel - 2], s[q].z); atomicAdd(&tab[rel - 3], s[q].w);
     }
@@ -639,15 +642,36 @@ __device__ __forceinline__ void table_grad_fold(const float* __restrict__ part, 
 // the per-workgroup partials (coalesced across the 256 threads) and adds it onto the table row rel(i,j).
 // grid = (Z part-slices, H heads): a workgroup sums its slice of the per-workgroup partials (coalesced float4
 // reads), folds the 4096 (i,j) elements onto the 225 table rows with LDS atomics and issues 225 global atomics.
+// DET: table row t = (di, dj) is owned by thread t, which adds its up to 64 (i, j) pairs in a fixed order and STORES the sum of part-slice
+// blockIdx.x at dtable[blockIdx.x * 225 H ...] (the workspace); the slice count is a function of `parts`, itself a function of the shape
+template <bool DET>
 __global__ __launch_bounds__(256) void bias_table_grad_kernel(const float* __restrict__ part, int parts,
                                                               float* __restrict__ dtable, int H) {
-    __shared__ float tab[225];
+    __shared__ __attribute__((aligned(16))) float tab[DET ? NT * NT : 225];
     const int h = blockIdx.y, t = threadIdx.x;
-    if (t < 225) tab[t] = 0.f;
+    if (!DET) {
+        if (t < 225) tab[t] = 0.f;
+        __syncthreads();
+    }
+    table_grad_fold<DET>(part, parts, h + H * blockIdx.x, H * gridDim.x, tab, t);
     __syncthreads();
-    table_grad_fold(part, parts, h + H * blockIdx.x, H * gridDim.x, tab, t);
-    __syncthreads();
+    if constexpr (DET) {
+        if (t < 225) {
+            const int di = t / 15 - 7, dj = t % 15 - 7;
+            float sum = 0.f;
+            for (int jh = 0; jh < 8; ++jh) {
+                const int ih = jh + di;
+                if ((unsigned)ih >= 8u) continue;
+                for (int jw = 0; jw < 8; ++jw) {
+                    const int iw = jw + dj;
+                    if ((unsigned)iw < 8u) sum += tab[(ih * 8 + iw) * NT + jh * 8 + jw];
+                }
+            }
+            dtable[(size_t)blockIdx.x * 225 * H + t * H + h] = sum;
+        }
+    } else {
     if (t < 225) atomicAdd(dtable + t * H + h, tab[t]);
+    }
 }
 
 // every block's table gradient of one backward pass in ONE launch (single-process runs: fused.py defers them to the end of backward)
@@ -747,7 +771,7 @@ extern "C" int dhz_ps_attn_fwd_dt(const void* q, const void* k, const void* v, i
 extern "C" int dhz_ps_attn_bwd_parts_d(int B_, int H, int d) {
     if (B_ <= 0 || H <= 0) return 0;
     (void)d;
-    const int cap = 2 * dhz_num_cus();
+    const int cap = 2 * dhz_part_cus();                        // (deterministic mode: a function of the shape)
     int per_head = cap / H;
     if (per_head < 1) per_head = 1;
     if (per_head > B_) per_head = B_;
@@ -839,7 +863,16 @@ extern "C" int dhz_bias_table_grad(const float* dbias_part, int parts, float* dt
     int z = parts / H / 4;            // >= 4 partials (64 KiB) per workgroup
     if (z < 1) z = 1;
     if (z > 128) z = 128;
-    hipLaunchKernelGGL(bias_table_grad_kernel, dim3(z, H), dim3(256), 0, s, dbias_part, parts, dtable, H);
+    if (dhz_det()) {                                           // one item per part-slice
+        float* ws = dhz_det_ws("dhz_bias_table_grad", z, 225L * H);
+        if (!ws) return DHZ_EINVAL;
+        hipLaunchKernelGGL(bias_table_grad_kernel<true>, dim3(z, H), dim3(256), 0, s, dbias_part, parts, ws, H);
+        DHZ_CHECK_LAUNCH("dhz_bias_table_grad");
+        DetSegs segs{};
+        segs.n = 1; segs.off[0] = 0; segs.len[0] = 225L * H; segs.dst[0] = dtable;
+        return dhz_det_reduce("dhz_bias_table_grad", ws, z, 225L * H, segs, s);
+    }
+    hipLaunchKernelGGL(bias_table_grad_kernel<false>, dim3(z, H), dim3(256), 0, s, dbias_part, parts, dtable, H);
     DHZ_CHECK_LAUNCH("dhz_bias_table_grad");
     return DHZ_OK;
 }
@@ -848,6 +881,11 @@ extern "C" int dhz_bias_table_grad_multi(const float* const* dbias_part, const i
                                          void* stream) {
     DHZ_REQUIRE(dbias_part && parts && dtable && heads && n > 0 && n <= TGRAD_MULTI_MAX, "dhz_bias_table_grad_multi: null pointer or n=%d outside 1..%d",
                 n, TGRAD_MULTI_MAX);
+    if (dhz_det()) {                                           // entry after entry through the two-stage form
+        for (int i = 0; i < n; ++i)
+            if (int rc = dhz_bias_table_grad(dbias_part[i], parts[i], dtable[i], heads[i], 1, stream)) return rc;
+        return DHZ_OK;
+    }
     TableGradMulti d = {};
     for (int i = 0; i < n; ++i) {
         DHZ_REQUIRE(dbias_part[i] && dtable[i] && heads[i] > 0 && parts[i] > 0 && parts[i] % heads[i] == 0,

@@ -771,7 +771,7 @@ int dispatch(const char* who, const float* A, int lda, const uint16_t* Bh, const
     DHZ_REQUIRE(NF <= 2048, "%s: %d output features (at most 2048: the bias vector is staged in LDS)", who, NF);
     // tile: the widest feature block that divides NF (the pre-split weight side costs no vector work: wide tiles re-split the
     // activations fewer times); 128 tokens (three ring slots of both operands fit the LDS)
-    const int cus = dhz_num_cus();
+    const int cus = dhz_part_cus();                               // (tile choices: a function of the shape in deterministic mode)
     int bn = NF % 128 == 0 ? 128 : NF % 64 == 0 ? 64 : 32;
     if (bn == 128 && (long)((M + 127) / 128) * (NF / 128) < cus && (long)((M + 127) / 128) * (NF / 64) >= cus / 2) bn = 64;
     if (EPI) {

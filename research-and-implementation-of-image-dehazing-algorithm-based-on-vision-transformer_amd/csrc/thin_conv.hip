@@ -251,7 +251,9 @@ __global__ __launch_bounds__(256) void thin_conv_dgrad_kernel(const float* __res
 }
 
 // dw[o][c][ky][kx] += sum_p dy[o][p] x[p + (ky - 1, kx - 1)][c] ; db[o] += sum_p dy[o][p]
-template <int C, typename T = float>
+// DET (deterministic mode, common.h): the workgroup STORES its sums at dw / db + blockIdx.x * (27 C + 4) (both point into the workspace) and
+// folds db with a shuffle tree per wave and a fixed sum over the waves; the grid is then a function of the shape
+template <int C, typename T = float, bool DET = false>
 __global__ __launch_bounds__(256, 2) void thin_conv_wgrad_kernel(const float* __restrict__ dy, const T* __restrict__ x,
                                                                  float* __restrict__ dw, float* __restrict__ db, int B, int H,
                                                                  int W, int tiles_x, int tiles_y) {
@@ -266,6 +268,7 @@ __global__ __launch_bounds__(256, 2) void thin_conv_wgrad_kernel(const float* __
     for (int ch = 0; ch < NCH; ++ch)
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) acc[ch][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (DET) { dw += (size_t)blockIdx.x * (27 * C + 4); if (db) db += (size_t)blockIdx.x * (27 * C + 4); }
     float accb0 = 0.f, accb1 = 0.f;                                           // db: dy sums of output t / 128, and (t < 128) of output 2
     for (int e = t; e < NPOS * GS; e += 256) sm.g[e] = 0.f;                   // columns 27 .. 32 stay zero
     const int ntiles = B * tiles_x * tiles_y;
@@ -361,11 +364,17 @@ __global__ __launch_bounds__(256, 2) void thin_conv_wgrad_kernel(const float* __
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int c = CC * ch + 16 * wv + 4 * g + r;
-                    atomicAdd(dw + ((n / 9) * C + c) * 9 + n % 9, acc[ch][nb][r]);
+                    dhz_accum<DET>(dw + ((n / 9) * C + c) * 9 + n % 9, acc[ch][nb][r]);
                 }
             }
         }
-    if (db) {
+    if (db && DET) {                                                          // waves 0, 1: output 0; 2, 3: output 1; accb1 (waves 0, 1): output 2
+        const float a = wave_sum(accb0), b = wave_sum(accb1);
+        __syncthreads();
+        if (lane == 0) { sm.dy[wv] = a; sm.dy[4 + wv] = b; }
+        __syncthreads();
+        if (t < 3) db[t] = sm.dy[2 * t] + sm.dy[2 * t + 1];
+    } else if (db) {
         __syncthreads();
         if (t < 4) sm.red[t] = 0.f;
         __syncthreads();
@@ -437,8 +446,23 @@ int launch_all(int which, const void* a, const float* b, const float* c, void* d
     } else {                     // a = dy (float), b -> tokens x (T) passed through c's slot: see dispatch
         const size_t smem = sizeof(ThinWgradSmem);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&thin_conv_wgrad_kernel<C, T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        const int cap = 2 * dhz_num_cus();                   // two resident workgroups per CU (LDS)
+        const int cap = 2 * dhz_part_cus();                  // two resident workgroups per CU (LDS)
         const int grid = ntiles < cap ? ntiles : cap;
+        if (dhz_det()) {                                     // one item per workgroup; slot = [dw 27 C | db 3 (+ 1)]
+            const char* who = "dhz_thin_conv3x3_wgrad";
+            if (sizeof(T) != 4) { dhz_set_error("%s: the deterministic mode covers fp32 storage only", who); return DHZ_EINVAL; }
+            const long slot = 27 * C + 4;
+            float* ws = dhz_det_ws(who, grid, slot);
+            if (!ws) return DHZ_EINVAL;
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&thin_conv_wgrad_kernel<C, T, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+            hipLaunchKernelGGL((thin_conv_wgrad_kernel<C, T, true>), dim3(grid), dim3(256), smem, s, (const float*)a, (const T*)c, ws, e ? ws + 27 * C : nullptr, B, H, W, tiles_x, tiles_y);
+            DHZ_CHECK_LAUNCH(who);
+            DetSegs segs{};
+            segs.n = e ? 2 : 1;
+            segs.off[0] = 0; segs.len[0] = 27 * C; segs.dst[0] = (float*)d;
+            segs.off[1] = 27 * C; segs.len[1] = 3; segs.dst[1] = e;
+            return dhz_det_reduce(who, ws, grid, slot, segs, s);
+        }
         hipLaunchKernelGGL((thin_conv_wgrad_kernel<C, T>), dim3(grid), dim3(256), smem, s, (const float*)a, (const T*)c, (float*)d, e, B, H, W, tiles_x, tiles_y);
     }
     return 0;
@@ -490,7 +514,7 @@ extern "C" int dhz_thin_conv3x3_wgrad_dt(const float* dy, const void* x, float* 
     DHZ_REQUIRE(dy && x && dw && B > 0 && H > 0 && W > 0, "dhz_thin_conv3x3_wgrad: bad arguments");
     DHZ_REQUIRE(C == 64 || C == 128, "dhz_thin_conv3x3_wgrad: C=%d unsupported (64, 128)", C);
     DHZ_REQUIRE(dtype == DHZ_F32 || dtype == DHZ_BF16, "dhz_thin_conv3x3_wgrad: unknown dtype %d", dtype);
-    dispatch(2, C, dtype, dy, nullptr, x, dw, db, B, H, W, (hipStream_t)stream);
+    if (int rc = dispatch(2, C, dtype, dy, nullptr, x, dw, db, B, H, W, (hipStream_t)stream)) return rc;
     DHZ_CHECK_LAUNCH("dhz_thin_conv3x3_wgrad");
     return DHZ_OK;
 }

@@ -447,6 +447,7 @@ extern "C" int dhz_maxpool2x2_nhwc_bf16_bwd(const void* gy, const void* act, voi
 
 extern "C" int dhz_l1_pair_fwd_bf16(const void* a, const void* p, const void* n, float* sums, int64_t count, void* stream) {
     DHZ_REQUIRE(a && p && sums && count > 0 && count % 8 == 0, "dhz_l1_pair_fwd_bf16: bad arguments (count must be a multiple of 8)");
+    DHZ_REQUIRE(!dhz_det(), "dhz_l1_pair_fwd_bf16: not available in deterministic mode (fp32 storage only)");
     hipLaunchKernelGGL(l1_pair_bf16_fwd_kernel, dim3(grid_for8(count / 8, 3 * dhz_num_cus())), dim3(256), 0, (hipStream_t)stream,
                        (const uint16_t*)a, (const uint16_t*)p, (const uint16_t*)n, sums, count / 8);
     DHZ_CHECK_LAUNCH("dhz_l1_pair_fwd_bf16");

@@ -24,6 +24,9 @@ SIGNATURES = {
     "dhz_gelu_fwd_dt": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p],
     "dhz_gelu_bwd_dt": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p],
     "dhz_get_reserved_cus": [],
+    "dhz_set_deterministic": [ctypes.c_int],
+    "dhz_get_deterministic": [],
+    "dhz_set_det_workspace": [ctypes.c_void_p, ctypes.c_size_t],
     "dhz_grid_cus": [],
     "dhz_ps_attn_fwd": [c_f, c_f, c_f, c_i, c_p, c_f, c_f, c_f, c_i, c_p, c_i, c_i, c_i, c_i, c_p],
     "dhz_ps_attn_bwd_parts": [c_i, c_i],

@@ -30,6 +30,11 @@ ATTN_FUSED_C128_MAX_HW = int(__import__("os").environ.get("DHZ_FUSED_C128_MAX_HW
 # Fused attention BACKWARD (csrc/fused_attn_bwd.hip, C = 32): the forward then saves only the selection ranks.  A/B against the
 # backward kernel chain: tools/bench_fused.py, profiles/r03_fused_attn_bwd_ab.txt.
 ATTN_FUSED_BWD_C = (32,)
+
+
+def _fused_bwd_widths():
+    """the fused backward accumulates its parameter gradients with fp32 atomics: the deterministic mode sends every width to the chain"""
+    return () if ops.DETERMINISTIC else ATTN_FUSED_BWD_C
 # Six-term QKV projections inside the fused forward (csrc/fused_attn.hip, P6): weight planes brought once per workgroup by LDS-DMA into
 # the dead Q / K / V / S tiles.  DHZ_FUSED_P6=0 selects the fp32-pipe projections (A/B: tools/bench_fused.py).
 ATTN_FUSED_P6 = __import__("os").environ.get("DHZ_FUSED_P6", "1") != "0"
@@ -223,7 +228,7 @@ def _attn_fused_fwd(train, x, gamma, beta, wq, bq, wk, bk, wv, bv, wo, bo, table
     use6 = ATTN_FUSED_P6 and C in ATTN_FUSED_P6_C
     n6 = _n6(C)
     wqkv_p = wo_p = None
-    will_fuse_bwd = train and C in ATTN_FUSED_BWD_C and x.dtype == torch.float32      # (the fused backward reads the fp32 fragment pack)
+    will_fuse_bwd = train and C in _fused_bwd_widths() and x.dtype == torch.float32      # (the fused backward reads the fp32 fragment pack)
     if not use6 or C == 128 or will_fuse_bwd:                  # fp32 fragment packs (C = 128 with six-term Q / K / V: the out-projection's only)
         hit = STAGED_PREPACK.pop(id(wq), None)
         if hit is not None and hit[0] is wq and hit[1][0].numel() == 3 * C * C and hit[1][0].device == dev:
@@ -246,7 +251,7 @@ def _attn_fused_fwd(train, x, gamma, beta, wq, bq, wk, bk, wv, bv, wo, bo, table
     bqkv = ops.cat_rows([bq.detach(), bk.detach(), bv.detach()])
     bias = _bias_tile(table, H, dev)
     out = torch.empty_like(x)
-    fused_bwd = train and C in ATTN_FUSED_BWD_C and x.dtype == torch.float32
+    fused_bwd = train and C in _fused_bwd_widths() and x.dtype == torch.float32
     xn = qkv = cx = stats = rank = None
     if train:
         if not fused_bwd:

@@ -25,7 +25,54 @@ KERNEL_TIMING = None
 
 
 def _stream():
+    if DETERMINISTIC and _DET_WS is None:
+        _det_workspace()
     return torch.cuda.current_stream().cuda_stream
+
+
+# Deterministic mode (include/dehaze_hip.h, dhz_set_deterministic): every accumulating kernel stores per-work-item partials in a
+# workspace and a fixed-order reduction adds them to the target - no fp32 atomics, a cut into work items that depends on the shapes alone:
+# the same step gives the same bits from run to run, under any CU reservation.  fp32 storage, one process; off by default.
+# DHZ_DETERMINISTIC=1 in the environment turns it on at import; DHZ_DET_WORKSPACE_MB sizes the workspace (default 256: the largest need of
+# the E = 32 model's step at 256 x 256 is 17 MB; a call that needs more fails and names the bytes).
+DETERMINISTIC = False
+_DET_WS = None
+
+
+def _det_workspace(nbytes=None):
+    """allocate the workspace on the current device and hand it to the library (on the first launch after the switch: importing with
+    DHZ_DETERMINISTIC=1 must not initialise the GPU)"""
+    global _DET_WS
+    if nbytes is None:
+        nbytes = int(float(os.environ.get("DHZ_DET_WORKSPACE_MB", "256")) * (1 << 20))
+    _DET_WS = torch.empty(max(nbytes // 4, 1), device="cuda", dtype=torch.float32)
+    _lib.call("dhz_set_det_workspace", _DET_WS.data_ptr(), _DET_WS.numel() * 4)
+
+
+def set_deterministic(on, workspace_bytes=None):
+    """switch the deterministic mode of the library (process-global) and own its workspace.  workspace_bytes: a size other than
+    DHZ_DET_WORKSPACE_MB's (allocated at once; needs the GPU).  A process that launches through the raw C-ABI only, before any ops.* call
+    and before the GPU is initialised, hands a workspace over itself (dhz_set_det_workspace) or calls ops._stream() once."""
+    global DETERMINISTIC, _DET_WS
+    on = bool(on)
+    if _DET_WS is not None:                              # give the old workspace back (stream order: its last reader is enqueued already)
+        _lib.call("dhz_set_det_workspace", None, 0)
+        _DET_WS = None
+    _lib.call("dhz_set_deterministic", int(on))
+    DETERMINISTIC = on
+    # at once where the GPU is up already, so that raw C-ABI calls which never pass ops._stream() find it; else on the first launch
+    if on and (workspace_bytes is not None or torch.cuda.is_initialized()):
+        _det_workspace(None if workspace_bytes is None else int(workspace_bytes))
+
+
+if os.environ.get("DHZ_DETERMINISTIC", "0") == "1":
+    set_deterministic(True)
+
+
+def _refuse_bf16_deterministic(what):
+    if DETERMINISTIC:
+        raise NotImplementedError(f"{what}: bf16 storage is outside the deterministic mode (DHZ_DETERMINISTIC / ops.set_deterministic): "
+                                  "it covers fp32 storage only")
 
 
 # The last tensors whose device pointers were handed to a launch: a pointer argument is often taken from a temporary
@@ -626,6 +673,7 @@ def _wgrad_launch(dy, off, x, targets, row_scale):
         if bf16 or split or n > 1:
             arrays = (_ptr_array([_p(dw) for _, dw, _ in grp]), _ptr_array([_p(db) for _, _, db in grp]))
             if bf16:
+                _refuse_bf16_deterministic("linear weight gradient")
                 _lib.call("dhz_linear_wgrad_bf16", *lead, n, N, K, *arrays, _stream())
             elif split:
                 ev = _timed("dhz_linear_wgrad_split")

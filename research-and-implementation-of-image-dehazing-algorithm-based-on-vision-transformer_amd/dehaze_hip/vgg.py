@@ -414,7 +414,9 @@ def to_plain_tap(t):
 
 def _sfx(t):
     """entry-point suffix for the storage type of a feature map (the fp32 and the bf16 L1 kernels)"""
-    return "_bf16" if t.dtype == torch.bfloat16 else ""
+    if t.dtype == torch.bfloat16:
+        return "_bf16"
+    return ""
 
 
 class _L1Pair(Function):
@@ -425,6 +427,8 @@ class _L1Pair(Function):
         a, p = a.contiguous(), p.contiguous()
         n = n.contiguous() if n is not None else None
         sums = torch.zeros(2, device=a.device, dtype=torch.float32)
+        if a.dtype == torch.bfloat16:
+            ops._refuse_bf16_deterministic("contrast sums")
         _lib.call("dhz_l1_pair_fwd" + _sfx(a), _p(a), _p(p), _p(n) if n is not None else None, _p(sums), a.numel(), _stream())
         ctx.save_for_backward(a, p, n) if n is not None else ctx.save_for_backward(a, p)
         ctx.has_n = n is not None
@@ -470,6 +474,8 @@ class _ContrastTaps(Function):
         for i in range(k):
             p = feats[k + i][:B].contiguous()
             n = None if ablation else feats[k + i][B:].contiguous()
+            if a[i].dtype == torch.bfloat16:
+                ops._refuse_bf16_deterministic("contrast sums")
             _lib.call("dhz_l1_pair_fwd" + _sfx(a[i]), _p(a[i]), _p(p), _p(n) if n is not None else None, sums.data_ptr() + 8 * i,
                       a[i].numel(), _stream())
             ps.append(p)
