@@ -511,6 +511,54 @@ int dhz_reverse_residual_bwd(const float* dout, const float* scale, float* dyw, 
                              int Wres, int C, int shift, int partition, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Windows of win x win tokens, win = 4 or 8 (`_w` entries).  The block clamps its window to the map (M1:764-766): four down-samplings
+ *     of a 64 x 64 patch leave a 4 x 4 map whose block runs ONE 4 x 4 window without shift; `--win_size 4` (options.py) runs 4 x 4
+ *     windows at every level.  A 4 x 4 window has N = 16 tokens, u = n_top(16) = 15 sampled keys per query and 15 selected queries
+ *     (ATT:310-315).  Every entry below is the entry of the same name without `_w` plus `win`; win = 8 RUNS that entry (same kernel,
+ *     same bits), win = 4 the 16-token kernels (csrc/ps_attn16.hip: one wave per window-head), any other win returns DHZ_EINVAL - and so
+ *     do a head_dim outside {16, 32, 64}, a map that is no multiple of win and a shift outside [0, win).
+ *
+ * K3  dhz_ps_attn_fwd_w / _bwd_w replace ProbAttention.forward ATT:287-342 and its autograd for N = win^2: q, k, v [B_, N, H, d] with
+ *     token stride ld, idx [N, u] uint8, bias [H, N, N] or NULL, mask [nW, N, N] or NULL (window id b mod nW), out stride ldo, rank
+ *     [B_, H, N] uint8 (0 .. u-1 by descending sparsity measure, 255 = not selected; at N = 16 exactly one query per window-head).
+ *     dtype = DHZ_F32 / DHZ_BF16 storage.  Backward: dq (zero rows for unselected queries), dk, dv with every element written;
+ *     dbias_part [dhz_ps_attn_bwd_parts_w(B_, H, d, win), N, N] written, not accumulated, row p belongs to head p % H (NULL iff
+ *     bias == NULL).  The 16-token kernels use no float atomics: deterministic in every mode.
+ * K3-dense  dhz_dense_attn_fwd_w / _bwd_w replace WindowAttention.forward M0:428-492 and its autograd; dbias_part has
+ *     dhz_ps_attn_bwd_parts_w(B_, H, d, win) rows at win = 4 and dhz_ps_attn_bwd_parts(B_, H) rows at win = 8. */
+#define DHZ_NTOK16 16 /* tokens per 4x4 window */
+#define DHZ_NTOP16 15 /* u = 5*ceil(ln 16) */
+int dhz_ps_attn_fwd_w(const void* q, const void* k, const void* v, int ld, const uint8_t* idx, const float* bias, const float* mask,
+                      void* out, int ldo, uint8_t* rank, int B_, int H, int nW, int d, int win, int dtype, void* stream);
+int dhz_ps_attn_bwd_parts_w(int B_, int H, int d, int win);
+int dhz_ps_attn_bwd_w(const void* q, const void* k, const void* v, int ld, const float* bias, const float* mask, const uint8_t* rank,
+                      const void* dout, int ldo, void* dq, void* dk, void* dv, int ldg, float* dbias_part, int B_, int H, int nW, int d,
+                      int win, int dtype, void* stream);
+int dhz_dense_attn_fwd_w(const float* q, const float* k, const float* v, int ld, const float* bias, const float* mask, float* out,
+                         int ldo, int B_, int H, int nW, int d, float scale, int win, void* stream);
+int dhz_dense_attn_bwd_w(const float* q, const float* k, const float* v, int ld, const float* bias, const float* mask, const float* dout,
+                         int ldo, float* dq, float* dk, float* dv, int ldg, float* dbias_part, int B_, int H, int nW, int d, float scale,
+                         int win, void* stream);
+/* K1 / K4 (tail) for win x win windows: LayerNorm + roll + window_partition M1:839-852, 550-574 and window_reverse + roll + residual
+ *     M1:577-601, 866, 872 (arguments of the `_dt` entries plus win; xw / yw / dyw rows in the order [B * nW, win^2, C]). */
+int dhz_ln_partition_fwd_w(const void* x, const float* gamma, const float* beta, void* xw, float* stats, int B, int Hres, int Wres, int C,
+                           int shift, int partition, int win, int dtype, void* stream);
+int dhz_ln_partition_bwd_w(const void* dxw, const void* x, const float* gamma, const float* stats, const void* dres, void* dx,
+                           float* dgamma, float* dbeta, int B, int Hres, int Wres, int C, int shift, int partition, int win, int dtype,
+                           void* stream);
+int dhz_reverse_residual_fwd_w(const void* yw, const void* shortcut, const float* scale, void* out, int B, int Hres, int Wres, int C,
+                               int shift, int partition, int win, int dtype, void* stream);
+int dhz_reverse_residual_bwd_w(const void* dout, const float* scale, void* dyw, int B, int Hres, int Wres, int C, int shift, int partition,
+                               int win, int dtype, void* stream);
+/* K6  shift mask builder M1:803-836 for win x win windows: mask [nW, win^2, win^2] in {0, -100}; 0 < shift < win, maps larger than win. */
+int dhz_shift_mask_w(float* mask, int Hres, int Wres, int shift, int win, void* stream);
+/* K7  relative-position bias M1:408-410 for win x win windows: table [(2 win - 1)^2, H] -> bias [H, win^2, win^2], and the table gradient
+ *     from the partial tiles of the backward kernels (dtable [(2 win - 1)^2, H], overwritten when accumulate == 0).  At win = 4 the
+ *     gradient is a fixed-order sum without atomics. */
+int dhz_bias_gather_w(const float* table, float* bias, int H, int win, void* stream);
+int dhz_bias_table_grad_w(const float* dbias_part, int parts, float* dtable, int H, int accumulate, int win, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * K5 (middle)  LeFF depthwise stage in token (NHWC) layout.  Replaces the NHWC<->NCHW rearranges,
  *     the GELU after linear1, the depthwise 3x3 conv and its GELU  (M1:488,514-520).
  *     u: [B, Hres*Wres, Ch] = linear1 output BEFORE GELU.  w: [Ch,1,3,3] (PyTorch layout), b: [Ch].

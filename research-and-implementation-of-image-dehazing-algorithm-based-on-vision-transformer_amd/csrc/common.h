@@ -219,9 +219,12 @@ __device__ __forceinline__ int dhz_off64(int row, int ch) { return row * 64 + 16
 
 // position of token (hh,ww) of an Hres x Wres map inside the (shifted) window layout:
 // shifted map coords h' = (hh - shift) mod H  (torch.roll(x, -shift): shifted[h'] = x[(h'+shift)%H]),
-// window id = (h'/8)*(W/8) + w'/8, token in window = (h'%8)*8 + w'%8.
+// window id = (h'/8)*(W/8) + w'/8, token in window = (h'%8)*8 + w'%8.  LW = log2 of the window side: 3 (8 x 8, the default - every
+// existing instance) or 2 (4 x 4).
+template <int LW = 3>
 __device__ __forceinline__ int window_slot(int hh, int ww, int Hres, int Wres, int shift) {
+    constexpr int M = (1 << LW) - 1;
     int hs = hh - shift; if (hs < 0) hs += Hres;
     int ws = ww - shift; if (ws < 0) ws += Wres;
-    return ((hs >> 3) * (Wres >> 3) + (ws >> 3)) * 64 + (hs & 7) * 8 + (ws & 7);
+    return ((hs >> LW) * (Wres >> LW) + (ws >> LW)) * (1 << (2 * LW)) + (hs & M) * (1 << LW) + (ws & M);
 }

@@ -17,7 +17,7 @@ __device__ __forceinline__ int quad_col(int li, int v, int lpt) {
 }
 
 // One token = C floats.  LPT lanes cooperate on a token (C/4 float4, up to 4 per lane).
-template <int VPL, typename T, bool WIDE = false>   // float4 per lane; T = storage type of x / xw
+template <int VPL, typename T, bool WIDE = false, int LW = 3>   // float4 per lane; T = storage type of x / xw; LW: log2 window side
 __global__ __launch_bounds__(256) void ln_partition_fwd_kernel(const T* __restrict__ x,
                                                                const float* __restrict__ gamma,
                                                                const float* __restrict__ beta, T* __restrict__ xw,
@@ -58,7 +58,7 @@ __global__ __launch_bounds__(256) void ln_partition_fwd_kernel(const T* __restri
         const float rstd = rsqrtf(var * invC + 1e-5f);
         if (ok) {
             const int bimg = tok / HW, p = tok % HW;
-            const size_t dst = partition ? (size_t)bimg * HW + window_slot(p / Wres, p % Wres, Hres, Wres, shift) : (size_t)tok;
+            const size_t dst = partition ? (size_t)bimg * HW + window_slot<LW>(p / Wres, p % Wres, Hres, Wres, shift) : (size_t)tok;
 #pragma unroll
             for (int v = 0; v < VPL; ++v) {
                 float4 y;
@@ -75,7 +75,7 @@ __global__ __launch_bounds__(256) void ln_partition_fwd_kernel(const T* __restri
 
 // DET (deterministic mode, common.h): the four waves meet in LDS through their own rows, summed in wave order, and the workgroup STORES its
 // 2C sums at dgamma[blockIdx.x * 2C ...] (dgamma is then the workspace, dbeta unused); the grid is a function of the shape.
-template <int VPL, typename T, bool WIDE = false, bool DET = false>
+template <int VPL, typename T, bool WIDE = false, bool DET = false, int LW = 3>
 __global__ __launch_bounds__(256) void ln_partition_bwd_kernel(const T* __restrict__ dxw,
                                                                const T* __restrict__ x,
                                                                const float* __restrict__ gamma,
@@ -123,11 +123,11 @@ __global__ __launch_bounds__(256) void ln_partition_bwd_kernel(const T* __restri
         if (G.ok) {
             const int bimg = G.tok / HW, p = G.tok % HW;
             const int hh = p / Wres, ww = p - hh * Wres;
-            const size_t src = partition ? (size_t)bimg * HW + window_slot(hh, ww, Hres, Wres, shift) : (size_t)G.tok;
+            const size_t src = partition ? (size_t)bimg * HW + window_slot<LW>(hh, ww, Hres, Wres, shift) : (size_t)G.tok;
             const size_t rsrc = (lay & 1) ? src : (size_t)G.tok;
-            G.drow = (lay & 2) ? bimg * HW + window_slot(hh, ww, Hres, Wres, lay >> 8) : G.tok;
+            G.drow = (lay & 2) ? bimg * HW + window_slot<LW>(hh, ww, Hres, Wres, lay >> 8) : G.tok;
             if (dx2) {
-                G.drow2 = bimg * HW + window_slot(hh, ww, Hres, Wres, lay >> 8);
+                G.drow2 = bimg * HW + window_slot<LW>(hh, ww, Hres, Wres, lay >> 8);
                 G.sc2 = scale2 ? scale2[bimg] : 1.f;
             }
 #pragma unroll
@@ -222,7 +222,7 @@ __global__ __launch_bounds__(256) void ln_partition_bwd_kernel(const T* __restri
 }
 
 // ------------------------------------------------------------------------------------------------ K4 tail
-template <bool BWD, typename T>
+template <bool BWD, typename T, int LW = 3>
 __global__ __launch_bounds__(256) void reverse_residual_kernel(const T* __restrict__ a,        // yw (fwd) / dout (bwd)
                                                                const T* __restrict__ shortcut,
                                                                const float* __restrict__ scale, T* __restrict__ o,
@@ -232,7 +232,7 @@ __global__ __launch_bounds__(256) void reverse_residual_kernel(const T* __restri
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
         const int tok = (int)(e / C4), c = (int)(e % C4);
         const int bimg = tok / HW, p = tok % HW;
-        const size_t slot = partition ? (size_t)bimg * HW + window_slot(p / Wres, p % Wres, Hres, Wres, shift) : (size_t)tok;
+        const size_t slot = partition ? (size_t)bimg * HW + window_slot<LW>(p / Wres, p % Wres, Hres, Wres, shift) : (size_t)tok;
         const float sc = scale ? scale[bimg] : 1.0f;
         if (!BWD) {
             const float4 y = ld4(a + 4 * (slot * C4 + c));
@@ -709,10 +709,13 @@ static int wide_geometry(int C, int* lpt, int* vpl) {
         else { dhz_set_error("%s: unknown dtype %d", who, (int)(dtype)); return DHZ_EINVAL; } \
     } while (0)
 
-extern "C" int dhz_ln_partition_fwd_dt(const void* x, const float* gamma, const float* beta, void* xw, float* stats,
-                                       int B, int Hres, int Wres, int C, int shift, int partition, int dtype, void* stream) {
+// LW = log2 of the window side: 3 is every existing entry, 2 the 4 x 4 windows of the `_w` entries
+template <int LW>
+static int ln_partition_fwd_lw(const void* x, const float* gamma, const float* beta, void* xw, float* stats,
+                               int B, int Hres, int Wres, int C, int shift, int partition, int dtype, void* stream) {
+    constexpr int WIN = 1 << LW;
     DHZ_REQUIRE(x && gamma && beta && xw, "dhz_ln_partition_fwd: null pointer");
-    DHZ_REQUIRE(B > 0 && Hres > 0 && Wres > 0 && (!partition || (Hres % 8 == 0 && Wres % 8 == 0 && shift >= 0 && shift < 8)),
+    DHZ_REQUIRE(B > 0 && Hres > 0 && Wres > 0 && (!partition || (Hres % WIN == 0 && Wres % WIN == 0 && shift >= 0 && shift < WIN)),
                 "dhz_ln_partition_fwd: bad shape");
     int lpt, vpl;
     DHZ_REQUIRE(ln_geometry(C, &lpt, &vpl) == 0, "dhz_ln_partition_fwd: unsupported C=%d", C);
@@ -721,36 +724,55 @@ extern "C" int dhz_ln_partition_fwd_dt(const void* x, const float* gamma, const 
     int lpw, vpw;
     if (dtype == DHZ_BF16 && wide_geometry(C, &lpw, &vpw) == 0) {            // bf16: 8 channels (16 bytes) per lane
         const int grid = grid_for((int64_t)ntok * lpw);
-#define LAUNCHW(V) hipLaunchKernelGGL((ln_partition_fwd_kernel<V, bf16s, true>), dim3(grid), dim3(256), 0, s, (const bf16s*)x, gamma, beta, (bf16s*)xw, stats, ntok, Hres, Wres, C, shift, lpw, partition)
+#define LAUNCHW(V) hipLaunchKernelGGL((ln_partition_fwd_kernel<V, bf16s, true, LW>), dim3(grid), dim3(256), 0, s, (const bf16s*)x, gamma, beta, (bf16s*)xw, stats, ntok, Hres, Wres, C, shift, lpw, partition)
         if (vpw == 2) LAUNCHW(2); else LAUNCHW(4);
 #undef LAUNCHW
         DHZ_CHECK_LAUNCH("dhz_ln_partition_fwd");
         return DHZ_OK;
     }
     const int grid = grid_for((int64_t)ntok * lpt);
-#define LAUNCH(V) hipLaunchKernelGGL((ln_partition_fwd_kernel<V, T>), dim3(grid), dim3(256), 0, s, (const T*)x, gamma, beta, (T*)xw, stats, ntok, Hres, Wres, C, shift, lpt, partition)
+#define LAUNCH(V) hipLaunchKernelGGL((ln_partition_fwd_kernel<V, T, false, LW>), dim3(grid), dim3(256), 0, s, (const T*)x, gamma, beta, (T*)xw, stats, ntok, Hres, Wres, C, shift, lpt, partition)
     DT_SWITCH(dtype, "dhz_ln_partition_fwd",
               switch (vpl) { case 1: LAUNCH(1); break; case 2: LAUNCH(2); break; case 3: LAUNCH(3); break; default: LAUNCH(4); });
 #undef LAUNCH
     DHZ_CHECK_LAUNCH("dhz_ln_partition_fwd");
     return DHZ_OK;
 }
+extern "C" int dhz_ln_partition_fwd_dt(const void* x, const float* gamma, const float* beta, void* xw, float* stats,
+                                       int B, int Hres, int Wres, int C, int shift, int partition, int dtype, void* stream) {
+    return ln_partition_fwd_lw<3>(x, gamma, beta, xw, stats, B, Hres, Wres, C, shift, partition, dtype, stream);
+}
+#define DHZ_WIN_SWITCH(who, win, CALL8, CALL4)                                                       \
+    do {                                                                                             \
+        if ((win) == 8) return CALL8;                                                                \
+        if ((win) == 4) return CALL4;                                                                \
+        dhz_set_error("%s: window %d unsupported (4 or 8)", who, (int)(win));                        \
+        return DHZ_EINVAL;                                                                           \
+    } while (0)
+extern "C" int dhz_ln_partition_fwd_w(const void* x, const float* gamma, const float* beta, void* xw, float* stats, int B, int Hres,
+                                      int Wres, int C, int shift, int partition, int win, int dtype, void* stream) {
+    DHZ_WIN_SWITCH("dhz_ln_partition_fwd_w", win,
+                   ln_partition_fwd_lw<3>(x, gamma, beta, xw, stats, B, Hres, Wres, C, shift, partition, dtype, stream),
+                   ln_partition_fwd_lw<2>(x, gamma, beta, xw, stats, B, Hres, Wres, C, shift, partition, dtype, stream));
+}
 extern "C" int dhz_ln_partition_fwd(const float* x, const float* gamma, const float* beta, float* xw, float* stats,
                                     int B, int Hres, int Wres, int C, int shift, int partition, void* stream) {
     return dhz_ln_partition_fwd_dt(x, gamma, beta, xw, stats, B, Hres, Wres, C, shift, partition, DHZ_F32, stream);
 }
 
-extern "C" int dhz_ln_partition_bwd_lay2(const void* dxw, const void* x, const float* gamma, const float* stats,
-                                         const void* dres, void* dx, float* dgamma, float* dbeta, int B, int Hres, int Wres,
-                                         int C, int shift, int partition, int dres_windowed, int dx_windowed, int dx_shift, void* dx2,
-                                         const float* scale2, int dtype, void* stream) {
-    DHZ_REQUIRE(!dx2 || (Hres % 8 == 0 && Wres % 8 == 0 && dx_shift >= 0 && dx_shift < 8 && dx2 != dres && dx2 != dx),
+template <int LW>
+static int ln_partition_bwd_lw(const void* dxw, const void* x, const float* gamma, const float* stats,
+                               const void* dres, void* dx, float* dgamma, float* dbeta, int B, int Hres, int Wres,
+                               int C, int shift, int partition, int dres_windowed, int dx_windowed, int dx_shift, void* dx2,
+                               const float* scale2, int dtype, void* stream) {
+    constexpr int WIN = 1 << LW;
+    DHZ_REQUIRE(!dx2 || (Hres % WIN == 0 && Wres % WIN == 0 && dx_shift >= 0 && dx_shift < WIN && dx2 != dres && dx2 != dx),
                 "dhz_ln_partition_bwd_lay2: the second (window-ordered) output needs an Hres x Wres map of multiples of 8, a shift in [0, 8) and its own buffer");
     DHZ_REQUIRE(dxw && x && gamma && stats && dx && dgamma && dbeta, "dhz_ln_partition_bwd: null pointer");
-    DHZ_REQUIRE(B > 0 && Hres > 0 && Wres > 0 && (!partition || (Hres % 8 == 0 && Wres % 8 == 0 && shift >= 0 && shift < 8)),
+    DHZ_REQUIRE(B > 0 && Hres > 0 && Wres > 0 && (!partition || (Hres % WIN == 0 && Wres % WIN == 0 && shift >= 0 && shift < WIN)),
                 "dhz_ln_partition_bwd: bad shape");
     DHZ_REQUIRE(!dres_windowed || partition, "dhz_ln_partition_bwd_lay: a window-ordered dres needs partition = 1");
-    DHZ_REQUIRE(!dx_windowed || (Hres % 8 == 0 && Wres % 8 == 0 && dx_shift >= 0 && dx_shift < 8 && dx != dres),
+    DHZ_REQUIRE(!dx_windowed || (Hres % WIN == 0 && Wres % WIN == 0 && dx_shift >= 0 && dx_shift < WIN && dx != dres),
                 "dhz_ln_partition_bwd_lay: a window-ordered dx needs an Hres x Wres map of multiples of 8, a shift in [0, 8) and dx != dres");
     const int lay = (dres_windowed ? 1 : 0) | (dx_windowed ? 2 : 0) | ((dx_windowed || dx2) ? (dx_shift << 8) : 0);
     int lpt, vpl;
@@ -770,7 +792,7 @@ extern "C" int dhz_ln_partition_bwd_lay2(const void* dxw, const void* x, const f
         DHZ_REQUIRE(dtype == DHZ_F32, "%s: the deterministic mode covers fp32 storage only", who);
         float* ws = dhz_det_ws(who, grid, 2 * C);
         if (!ws) return DHZ_EINVAL;
-#define LAUNCHD(V) hipLaunchKernelGGL((ln_partition_bwd_kernel<V, float, false, true>), dim3(grid), dim3(256), 0, s, (const float*)dxw, (const float*)x, gamma, stats, (const float*)dres, (float*)dx, ws, nullptr, ntok, Hres, Wres, C, shift, lpt, partition, lay, (float*)dx2, scale2)
+#define LAUNCHD(V) hipLaunchKernelGGL((ln_partition_bwd_kernel<V, float, false, true, LW>), dim3(grid), dim3(256), 0, s, (const float*)dxw, (const float*)x, gamma, stats, (const float*)dres, (float*)dx, ws, nullptr, ntok, Hres, Wres, C, shift, lpt, partition, lay, (float*)dx2, scale2)
         switch (vpl) { case 1: LAUNCHD(1); break; case 2: LAUNCHD(2); break; case 3: LAUNCHD(3); break; default: LAUNCHD(4); }
 #undef LAUNCHD
         DHZ_CHECK_LAUNCH(who);
@@ -781,18 +803,34 @@ extern "C" int dhz_ln_partition_bwd_lay2(const void* dxw, const void* x, const f
         return dhz_det_reduce(who, ws, grid, 2 * C, segs, s);
     }
     if (wide) {
-#define LAUNCHW(V) hipLaunchKernelGGL((ln_partition_bwd_kernel<V, bf16s, true>), dim3(grid), dim3(256), 0, s, (const bf16s*)dxw, (const bf16s*)x, gamma, stats, (const bf16s*)dres, (bf16s*)dx, dgamma, dbeta, ntok, Hres, Wres, C, shift, lpt, partition, lay, (bf16s*)dx2, scale2)
+#define LAUNCHW(V) hipLaunchKernelGGL((ln_partition_bwd_kernel<V, bf16s, true, false, LW>), dim3(grid), dim3(256), 0, s, (const bf16s*)dxw, (const bf16s*)x, gamma, stats, (const bf16s*)dres, (bf16s*)dx, dgamma, dbeta, ntok, Hres, Wres, C, shift, lpt, partition, lay, (bf16s*)dx2, scale2)
         if (vpw == 2) LAUNCHW(2); else LAUNCHW(4);
 #undef LAUNCHW
         DHZ_CHECK_LAUNCH("dhz_ln_partition_bwd");
         return DHZ_OK;
     }
-#define LAUNCH(V) hipLaunchKernelGGL((ln_partition_bwd_kernel<V, T>), dim3(grid), dim3(256), 0, s, (const T*)dxw, (const T*)x, gamma, stats, (const T*)dres, (T*)dx, dgamma, dbeta, ntok, Hres, Wres, C, shift, lpt, partition, lay, (T*)dx2, scale2)
+#define LAUNCH(V) hipLaunchKernelGGL((ln_partition_bwd_kernel<V, T, false, false, LW>), dim3(grid), dim3(256), 0, s, (const T*)dxw, (const T*)x, gamma, stats, (const T*)dres, (T*)dx, dgamma, dbeta, ntok, Hres, Wres, C, shift, lpt, partition, lay, (T*)dx2, scale2)
     DT_SWITCH(dtype, "dhz_ln_partition_bwd",
               switch (vpl) { case 1: LAUNCH(1); break; case 2: LAUNCH(2); break; case 3: LAUNCH(3); break; default: LAUNCH(4); });
 #undef LAUNCH
     DHZ_CHECK_LAUNCH("dhz_ln_partition_bwd");
     return DHZ_OK;
+}
+extern "C" int dhz_ln_partition_bwd_lay2(const void* dxw, const void* x, const float* gamma, const float* stats,
+                                         const void* dres, void* dx, float* dgamma, float* dbeta, int B, int Hres, int Wres,
+                                         int C, int shift, int partition, int dres_windowed, int dx_windowed, int dx_shift, void* dx2,
+                                         const float* scale2, int dtype, void* stream) {
+    return ln_partition_bwd_lw<3>(dxw, x, gamma, stats, dres, dx, dgamma, dbeta, B, Hres, Wres, C, shift, partition, dres_windowed, dx_windowed,
+                                  dx_shift, dx2, scale2, dtype, stream);
+}
+extern "C" int dhz_ln_partition_bwd_w(const void* dxw, const void* x, const float* gamma, const float* stats, const void* dres, void* dx,
+                                      float* dgamma, float* dbeta, int B, int Hres, int Wres, int C, int shift, int partition, int win,
+                                      int dtype, void* stream) {
+    DHZ_WIN_SWITCH("dhz_ln_partition_bwd_w", win,
+                   ln_partition_bwd_lw<3>(dxw, x, gamma, stats, dres, dx, dgamma, dbeta, B, Hres, Wres, C, shift, partition, 0, 0, 0, nullptr,
+                                          nullptr, dtype, stream),
+                   ln_partition_bwd_lw<2>(dxw, x, gamma, stats, dres, dx, dgamma, dbeta, B, Hres, Wres, C, shift, partition, 0, 0, 0, nullptr,
+                                          nullptr, dtype, stream));
 }
 extern "C" int dhz_ln_partition_bwd_lay(const void* dxw, const void* x, const float* gamma, const float* stats,
                                         const void* dres, void* dx, float* dgamma, float* dbeta, int B, int Hres, int Wres,
@@ -812,36 +850,60 @@ extern "C" int dhz_ln_partition_bwd(const float* dxw, const float* x, const floa
     return dhz_ln_partition_bwd_dt(dxw, x, gamma, stats, dres, dx, dgamma, dbeta, B, Hres, Wres, C, shift, partition, DHZ_F32, stream);
 }
 
-extern "C" int dhz_reverse_residual_fwd_dt(const void* yw, const void* shortcut, const float* scale, void* out, int B,
-                                           int Hres, int Wres, int C, int shift, int partition, int dtype, void* stream) {
+template <int LW>
+static int reverse_residual_fwd_lw(const void* yw, const void* shortcut, const float* scale, void* out, int B,
+                                   int Hres, int Wres, int C, int shift, int partition, int dtype, void* stream) {
+    constexpr int WIN = 1 << LW;
     DHZ_REQUIRE(yw && shortcut && out, "dhz_reverse_residual_fwd: null pointer");
-    DHZ_REQUIRE(B > 0 && C % 4 == 0 && (!partition || (Hres % 8 == 0 && Wres % 8 == 0 && shift >= 0 && shift < 8)),
+    DHZ_REQUIRE(B > 0 && C % 4 == 0 && (!partition || (Hres % WIN == 0 && Wres % WIN == 0 && shift >= 0 && shift < WIN)),
                 "dhz_reverse_residual_fwd: bad shape");
     const int ntok = B * Hres * Wres;
     DT_SWITCH(dtype, "dhz_reverse_residual_fwd",
-              hipLaunchKernelGGL((reverse_residual_kernel<false, T>), dim3(grid_for((int64_t)ntok * (C / 4))), dim3(256), 0,
+              hipLaunchKernelGGL((reverse_residual_kernel<false, T, LW>), dim3(grid_for((int64_t)ntok * (C / 4))), dim3(256), 0,
                                  (hipStream_t)stream, (const T*)yw, (const T*)shortcut, scale, (T*)out, ntok, Hres, Wres, C / 4, shift,
                                  partition));
     DHZ_CHECK_LAUNCH("dhz_reverse_residual_fwd");
     return DHZ_OK;
+}
+extern "C" int dhz_reverse_residual_fwd_dt(const void* yw, const void* shortcut, const float* scale, void* out, int B,
+                                           int Hres, int Wres, int C, int shift, int partition, int dtype, void* stream) {
+    return reverse_residual_fwd_lw<3>(yw, shortcut, scale, out, B, Hres, Wres, C, shift, partition, dtype, stream);
+}
+extern "C" int dhz_reverse_residual_fwd_w(const void* yw, const void* shortcut, const float* scale, void* out, int B, int Hres, int Wres,
+                                          int C, int shift, int partition, int win, int dtype, void* stream) {
+    DHZ_WIN_SWITCH("dhz_reverse_residual_fwd_w", win,
+                   reverse_residual_fwd_lw<3>(yw, shortcut, scale, out, B, Hres, Wres, C, shift, partition, dtype, stream),
+                   reverse_residual_fwd_lw<2>(yw, shortcut, scale, out, B, Hres, Wres, C, shift, partition, dtype, stream));
 }
 extern "C" int dhz_reverse_residual_fwd(const float* yw, const float* shortcut, const float* scale, float* out, int B,
                                         int Hres, int Wres, int C, int shift, int partition, void* stream) {
     return dhz_reverse_residual_fwd_dt(yw, shortcut, scale, out, B, Hres, Wres, C, shift, partition, DHZ_F32, stream);
 }
 
-extern "C" int dhz_reverse_residual_bwd_dt(const void* dout, const float* scale, void* dyw, int B, int Hres, int Wres,
-                                           int C, int shift, int partition, int dtype, void* stream) {
+template <int LW>
+static int reverse_residual_bwd_lw(const void* dout, const float* scale, void* dyw, int B, int Hres, int Wres,
+                                   int C, int shift, int partition, int dtype, void* stream) {
+    constexpr int WIN = 1 << LW;
     DHZ_REQUIRE(dout && dyw, "dhz_reverse_residual_bwd: null pointer");
-    DHZ_REQUIRE(B > 0 && C % 4 == 0 && (!partition || (Hres % 8 == 0 && Wres % 8 == 0 && shift >= 0 && shift < 8)),
+    DHZ_REQUIRE(B > 0 && C % 4 == 0 && (!partition || (Hres % WIN == 0 && Wres % WIN == 0 && shift >= 0 && shift < WIN)),
                 "dhz_reverse_residual_bwd: bad shape");
     const int ntok = B * Hres * Wres;
     DT_SWITCH(dtype, "dhz_reverse_residual_bwd",
-              hipLaunchKernelGGL((reverse_residual_kernel<true, T>), dim3(grid_for((int64_t)ntok * (C / 4))), dim3(256), 0,
+              hipLaunchKernelGGL((reverse_residual_kernel<true, T, LW>), dim3(grid_for((int64_t)ntok * (C / 4))), dim3(256), 0,
                                  (hipStream_t)stream, (const T*)dout, (const T*)nullptr, scale, (T*)dyw, ntok, Hres, Wres, C / 4, shift,
                                  partition));
     DHZ_CHECK_LAUNCH("dhz_reverse_residual_bwd");
     return DHZ_OK;
+}
+extern "C" int dhz_reverse_residual_bwd_dt(const void* dout, const float* scale, void* dyw, int B, int Hres, int Wres,
+                                           int C, int shift, int partition, int dtype, void* stream) {
+    return reverse_residual_bwd_lw<3>(dout, scale, dyw, B, Hres, Wres, C, shift, partition, dtype, stream);
+}
+extern "C" int dhz_reverse_residual_bwd_w(const void* dout, const float* scale, void* dyw, int B, int Hres, int Wres, int C, int shift,
+                                          int partition, int win, int dtype, void* stream) {
+    DHZ_WIN_SWITCH("dhz_reverse_residual_bwd_w", win,
+                   reverse_residual_bwd_lw<3>(dout, scale, dyw, B, Hres, Wres, C, shift, partition, dtype, stream),
+                   reverse_residual_bwd_lw<2>(dout, scale, dyw, B, Hres, Wres, C, shift, partition, dtype, stream));
 }
 extern "C" int dhz_reverse_residual_bwd(const float* dout, const float* scale, float* dyw, int B, int Hres, int Wres,
                                         int C, int shift, int partition, void* stream) {

@@ -134,6 +134,19 @@ SIGNATURES = {
     "dhz_comm_allreduce_sum_f32": [c_p, c_f, c_l, c_p],
     "dhz_comm_destroy": [c_p],
     "dhz_adamw_step_shadow": [c_f, c_f, c_f, c_f, c_f, c_l, c_fl, c_fl, c_fl, c_fl, c_fl, c_i, c_fl, c_p],
+    # win x win windows (win = 4 or 8): the entry of the same name without `_w` plus `win`
+    "dhz_ps_attn_fwd_w": [c_f, c_f, c_f, c_i, c_p, c_f, c_f, c_f, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p],
+    "dhz_ps_attn_bwd_parts_w": [c_i, c_i, c_i, c_i],
+    "dhz_ps_attn_bwd_w": [c_f, c_f, c_f, c_i, c_f, c_f, c_p, c_f, c_i, c_f, c_f, c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_p],
+    "dhz_dense_attn_fwd_w": [c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_fl, c_i, c_p],
+    "dhz_dense_attn_bwd_w": [c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_fl, c_i, c_p],
+    "dhz_ln_partition_fwd_w": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p],
+    "dhz_ln_partition_bwd_w": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p],
+    "dhz_reverse_residual_fwd_w": [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p],
+    "dhz_reverse_residual_bwd_w": [c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p],
+    "dhz_shift_mask_w": [c_f, c_i, c_i, c_i, c_i, c_p],
+    "dhz_bias_gather_w": [c_f, c_f, c_i, c_i, c_p],
+    "dhz_bias_table_grad_w": [c_f, c_i, c_f, c_i, c_i, c_i, c_p],
 }
 _RESTYPE = {"dhz_last_error": ctypes.c_char_p, "dhz_build_id": ctypes.c_char_p}
 

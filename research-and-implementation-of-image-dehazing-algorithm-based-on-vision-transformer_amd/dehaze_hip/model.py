@@ -66,6 +66,23 @@ def draw_sample_index(n_blocks=1, L=ops.NTOK):
     return torch.randint(L, (n_blocks, L, n_top(L)))
 
 
+class _Run(list):
+    """block positions of one run; L = tokens per window of its blocks"""
+    L = 0
+
+
+def sample_runs(Ls):
+    """[L of block 0, L of block 1, ...] -> maximal runs of consecutive blocks with equal L: a batched draw_sample_index per run consumes
+    the global generator like the per-block draws in block order."""
+    runs = []
+    for j, L in enumerate(Ls):
+        if not runs or runs[-1].L != L:
+            runs.append(_Run())
+            runs[-1].L = L
+        runs[-1].append(j)
+    return runs
+
+
 def window_partition(x, win_size, dilation_rate=1):
     """[B,H,W,C] -> [B*nW, win, win, C]  (reference helper M1:550-574; kept for API parity - the model
     itself never materialises this, the partition is folded into the LN kernel's store addresses)."""
@@ -111,8 +128,8 @@ class AttentionLayer(nn.Module):
         self.mix = mix
 
     def forward(self, queries, keys, values, table, SW_mask, attn_mask=None, idx=None):
-        """queries (= keys = values): [B_, 64, C] window tokens.  `table` is the [225,H] bias table (or
-        None when options.is_relative_position_bias is False); returns ([B_,64,C], None)."""
+        """queries (= keys = values): [B_, N, C] window tokens, N = 64 (8 x 8 windows) or 16 (4 x 4).  `table` is the
+        [(2 win - 1)^2, H] bias table (or None when options.is_relative_position_bias is False); returns ([B_,N,C], None)."""
         assert keys is queries and values is queries, "self-attention only (M1:413 passes x, x, x)"
         B_, N, C = queries.shape
         H = self.n_heads
@@ -230,6 +247,14 @@ def relative_position_index(win):
     return rel[0] * (2 * win - 1) + rel[1]
 
 
+def check_window(win_size):
+    """The kernels exist for 4 x 4 and 8 x 8 windows (csrc/ps_attn16.hip, csrc/ps_attn.hip); every other size - 16 x 16, or the 2 x 2 that
+    a 32-pixel model's bottleneck clamps to (M1:764-766) - is refused."""
+    w = to_2tuple(win_size)
+    if w[0] != w[1] or w[0] not in ops.WINDOWS.values():
+        raise NotImplementedError(f"window {w[0]}x{w[1]}: the HIP kernels exist for 4x4 and 8x8 windows only")
+
+
 class WindowAttention(nn.Module):
     """M1:336-415 (variant='probsparse') / M0:428-518 (variant='dense')."""
 
@@ -262,8 +287,7 @@ class WindowAttention(nn.Module):
         self.softmax = nn.Softmax(dim=-1)
 
     def forward(self, x, attn_kv=None, mask=None, idx=None):
-        if self.win_size[0] * self.win_size[1] != ops.NTOK:
-            raise NotImplementedError("the HIP kernels are specialised to 8x8 windows")
+        check_window(self.win_size)
         if self.variant == "probsparse":
             import options                                         # read at call time, like ATT:227
             table = self.relative_position_bias_table if options.is_relative_position_bias else None
@@ -277,7 +301,7 @@ class WindowAttention(nn.Module):
         H = self.num_heads
         qkv = ops.linear_tokens(x.reshape(B_ * N, C), self.qkv.to_q.weight, self.qkv.to_q.bias,
                                 self.qkv.to_kv.weight, self.qkv.to_kv.bias)
-        ctx = ops.dense_window_attention(qkv, self.relative_position_bias_table, mask, H, C // H, self.scale)
+        ctx = ops.dense_window_attention(qkv, self.relative_position_bias_table, mask, H, C // H, self.scale, N)
         return ops.linear_tokens(ctx, self.proj.weight, self.proj.bias).view(B_, N, C)
 
     def extra_repr(self):
@@ -370,7 +394,7 @@ class LeWinTransformerBlock(nn.Module):
         key = (H, W, str(device))
         m = self._mask_cache.get(key)
         if m is None:
-            m = ops.shift_mask(H, W, self.shift_size, device)
+            m = ops.shift_mask(H, W, self.shift_size, device, self.win_size)
             self._mask_cache[key] = m
         return m
 
@@ -380,6 +404,7 @@ class LeWinTransformerBlock(nn.Module):
         return self.drop_path.sample_scale(x) if isinstance(self.drop_path, DropPath) else None
 
     def forward(self, x, mask=None):
+        check_window(self.win_size)
         B, L, C = x.shape
         H = W = int(math.sqrt(L))
         attn_mask = None
@@ -409,9 +434,10 @@ class LeWinTransformerBlock(nn.Module):
             x = fused.attn_branch(x, self.norm1, self.attn.ProbSpare, table, idx.contiguous(), attn_mask,
                                   self._scale(x), H, W, self.shift_size, self.num_heads)
         else:
-            xw = ops.ln_partition(x, self.norm1.weight, self.norm1.bias, H, W, self.shift_size)   # LN+roll+partition
+            # the kernel chain under autograd, for either window (the fused single-kernel paths above are 8 x 8 only)
+            xw = ops.ln_partition(x, self.norm1.weight, self.norm1.bias, H, W, self.shift_size, self.win_size)   # LN+roll+partition
             aw = self.attn(xw.view(-1, self.win_size * self.win_size, C), mask=attn_mask, idx=idx)
-            x = ops.reverse_residual(aw.reshape(-1, C), x, self._scale(x), H, W, self.shift_size)  # reverse+unroll+res
+            x = ops.reverse_residual(aw.reshape(-1, C), x, self._scale(x), H, W, self.shift_size, self.win_size)  # reverse+unroll+res
         if self.token_mlp == 'ffn':
             # Mlp branch (norm2 -> fc1 -> GELU -> fc2 -> residual) as one autograd node
             return fused.ffn_branch(x, self.norm2, self.mlp, self._scale(x))
@@ -705,15 +731,18 @@ class Uformer(nn.Module):
         return [(n, p) for n, p in self.named_parameters() if not any(d in n for d in dead)]
 
     def _stage_sample_indices(self, device):
-        """One host draw for all ProbSparse blocks of this forward (same CPU-generator stream as the
-        reference's 18 per-block draws), one H2D copy, handed to the blocks in execution order."""
+        """One host draw per run of consecutive ProbSparse blocks with the same window (same CPU-generator stream as the reference's 18
+        per-block draws `torch.randint(L, (L, u))`, each with its block's own L = win^2), one H2D copy per run, handed to the blocks in
+        execution order.  All windows 8 x 8: one draw.  A 64-pixel model: 8 blocks of L = 64, the two bottleneck blocks of L = 16, 8 of
+        L = 64."""
         blocks = [b for st in self.stages() for b in st.blocks]
         if self.variant != "probsparse":
             return
-        idx = draw_sample_index(len(blocks)).to(torch.uint8)
-        idx = idx.pin_memory().to(device, non_blocking=True) if device.type == "cuda" else idx
-        for i, b in enumerate(blocks):
-            b._staged_idx = idx[i]
+        for run in sample_runs([b.win_size * b.win_size for b in blocks]):
+            idx = draw_sample_index(len(run), run.L).to(torch.uint8)
+            idx = idx.pin_memory().to(device, non_blocking=True) if device.type == "cuda" else idx
+            for i, j in enumerate(run):
+                blocks[j]._staged_idx = idx[i]
 
     def _stage_drop_path(self, x):
         """All DropPath keep/keep_prob vectors of one training forward (two per block with drop_prob > 0) from ONE
@@ -764,6 +793,9 @@ class Uformer(nn.Module):
             fused.stage_block_operands(entries, x.device)
 
     def forward(self, x, mask=None):
+        for st in self.stages():     # before anything runs: a window the kernels do not have is an error, not a late surprise
+            for b in st.blocks:
+                check_window(b.win_size)
         ops.sync_shadows()          # derived weight copies (bf16 / split planes) follow parameters written outside the optimizer
         self._stage_sample_indices(x.device)
         self._stage_drop_path(x)

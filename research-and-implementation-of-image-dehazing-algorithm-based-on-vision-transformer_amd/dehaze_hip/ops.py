@@ -17,7 +17,17 @@ from torch.autograd import Function
 
 from . import _lib
 
-NTOK, NTOP = 64, 25
+NTOK, NTOP = 64, 25            # 8 x 8 windows
+NTOK16, NTOP16 = 16, 15        # 4 x 4 windows: u = n_top(16) = 15
+WINDOWS = {NTOK: 8, NTOK16: 4}  # tokens per window -> window side of the kernels that exist
+
+
+def _win_of(N):
+    """window side for N tokens per window; the kernels exist for 8 x 8 and 4 x 4 windows only"""
+    try:
+        return WINDOWS[int(N)]
+    except KeyError:
+        raise NotImplementedError(f"windows of {N} tokens: the HIP kernels exist for 4x4 and 8x8 windows (16 or 64 tokens) only") from None
 
 # bench.py sets this to {"<entry point>": []} to collect (start_event, end_event, units) per launch of
 # that kernel, recorded on the stream the kernel is launched on (torch's current stream).
@@ -478,28 +488,62 @@ def gemm_dgrad(dy, W, row_scale=None):
 
 
 # ----------------------------------------------------------------------------- K3 / K7
-def ps_attn_fwd_launch(qkv, idx, bias, mask, out, rank, B_, H, d):
-    """dhz_ps_attn_fwd_dt on a packed [T, 3C] buffer (columns [Q | K | V]), inside bench.py's timing bracket"""
+def ps_attn_fwd_launch(qkv, idx, bias, mask, out, rank, B_, H, d, N=NTOK):
+    """dhz_ps_attn_fwd_dt (N = 64) / dhz_ps_attn_fwd_w (N = 16) on a packed [T, 3C] buffer (columns [Q | K | V]), inside bench.py's
+    timing bracket"""
     C, es, base = H * d, qkv.element_size(), qkv.data_ptr()
+    nW = mask.shape[0] if mask is not None else 1
     ev = _timed("dhz_ps_attn_fwd")
-    _lib.call("dhz_ps_attn_fwd_dt", base, base + es * C, base + 2 * es * C, 3 * C, _p(idx), _p(bias), _p(mask), _p(out), C, _p(rank), B_, H,
-              mask.shape[0] if mask is not None else 1, d, _dt(qkv), _stream())
-    _timed_end(ev, B_ * H * 4 * NTOK * d * es)
+    if N == NTOK:
+        _lib.call("dhz_ps_attn_fwd_dt", base, base + es * C, base + 2 * es * C, 3 * C, _p(idx), _p(bias), _p(mask), _p(out), C, _p(rank), B_, H,
+                  nW, d, _dt(qkv), _stream())
+    else:
+        _lib.call("dhz_ps_attn_fwd_w", base, base + es * C, base + 2 * es * C, 3 * C, _p(idx), _p(bias), _p(mask), _p(out), C, _p(rank), B_, H,
+                  nW, d, _win_of(N), _dt(qkv), _stream())
+    _timed_end(ev, B_ * H * 4 * N * d * es)
 
 
-def ps_attn_bwd_launch(qkv, dqkv, bias, mask, rank, dout, dpart, B_, H, d):
-    """dhz_ps_attn_bwd_dt: packed qkv / dqkv [T, 3C]"""
+def ps_attn_bwd_launch(qkv, dqkv, bias, mask, rank, dout, dpart, B_, H, d, N=NTOK):
+    """dhz_ps_attn_bwd_dt (N = 64) / dhz_ps_attn_bwd_w (N = 16): packed qkv / dqkv [T, 3C]"""
     C, es, base, gb = H * d, qkv.element_size(), qkv.data_ptr(), dqkv.data_ptr()
-    _lib.call("dhz_ps_attn_bwd_dt", base, base + es * C, base + 2 * es * C, 3 * C, _p(bias), _p(mask), _p(rank), _p(dout), C,
-              gb, gb + es * C, gb + 2 * es * C, 3 * C, _p(dpart), B_, H, mask.shape[0] if mask is not None else 1, d, _dt(qkv), _stream())
+    nW = mask.shape[0] if mask is not None else 1
+    if N == NTOK:
+        _lib.call("dhz_ps_attn_bwd_dt", base, base + es * C, base + 2 * es * C, 3 * C, _p(bias), _p(mask), _p(rank), _p(dout), C,
+                  gb, gb + es * C, gb + 2 * es * C, 3 * C, _p(dpart), B_, H, nW, d, _dt(qkv), _stream())
+    else:
+        _lib.call("dhz_ps_attn_bwd_w", base, base + es * C, base + 2 * es * C, 3 * C, _p(bias), _p(mask), _p(rank), _p(dout), C,
+                  gb, gb + es * C, gb + 2 * es * C, 3 * C, _p(dpart), B_, H, nW, d, _win_of(N), _dt(qkv), _stream())
+
+
+def bias_tile(table, H, N=NTOK):
+    """[H, N, N] relative-position bias of a [(2 win - 1)^2, H] table (M1:408-410)"""
+    win = _win_of(N)
+    assert tuple(table.shape) == ((2 * win - 1) ** 2, H), f"bias table {tuple(table.shape)} for {win}x{win} windows, {H} heads"
+    bias = torch.empty((H, N, N), device=table.device, dtype=torch.float32)
+    if N == NTOK:
+        _lib.call("dhz_bias_gather", _p(table.contiguous()), _p(bias), H, _stream())
+    else:
+        _lib.call("dhz_bias_gather_w", _p(table.contiguous()), _p(bias), H, win, _stream())
+    return bias
+
+
+def bias_table_grad(dpart, parts, H, N=NTOK):
+    """[(2 win - 1)^2, H] table gradient from the partial [parts, N, N] tiles of a backward kernel"""
+    win = _win_of(N)
+    dtable = torch.empty(((2 * win - 1) ** 2, H), device=dpart.device, dtype=torch.float32)
+    if N == NTOK:
+        _lib.call("dhz_bias_table_grad", _p(dpart), parts, _p(dtable), H, 0, _stream())
+    else:
+        _lib.call("dhz_bias_table_grad_w", _p(dpart), parts, _p(dtable), H, 0, win, _stream())
+    return dtable
 
 
 class _PSWindowAttention(Function):
     """ProbAttention.forward (ATT:287-342) on a packed QKV buffer.
 
-    qkv   : [T, 3C] (T = B_*64 window-ordered tokens; columns [Q | K | V], each [H, d])
-    table : [225, H] relative position bias table, or None (options.is_relative_position_bias False)
-    idx   : [64, 25] uint8 sampled keys;  mask: [nW, 64, 64] or None
+    qkv   : [T, 3C] (T = B_*N window-ordered tokens; columns [Q | K | V], each [H, d])
+    table : [(2 win - 1)^2, H] relative position bias table, or None (options.is_relative_position_bias False)
+    idx   : [N, u] uint8 sampled keys ([64, 25] for 8 x 8 windows, [16, 15] for 4 x 4: N is taken from it);  mask: [nW, N, N] or None
     """
 
     @staticmethod
@@ -507,33 +551,31 @@ class _PSWindowAttention(Function):
         _require_gpu(qkv, table, idx, mask)
         T, C3 = qkv.shape
         C = H * d
-        assert C3 == 3 * C and T % NTOK == 0 and qkv.is_contiguous()
-        B_ = T // NTOK
+        N = idx.shape[0]
+        assert tuple(idx.shape) == ((NTOK, NTOP) if _win_of(N) == 8 else (NTOK16, NTOP16)), f"sample table {tuple(idx.shape)}"
+        assert C3 == 3 * C and T % N == 0 and qkv.is_contiguous() and (mask is None or tuple(mask.shape[1:]) == (N, N))
+        B_ = T // N
         out = torch.empty((T, C), device=qkv.device, dtype=qkv.dtype)
-        rank = torch.empty((B_ * H * NTOK,), device=qkv.device, dtype=torch.uint8)
-        bias = None
-        if table is not None:
-            bias = torch.empty((H, NTOK, NTOK), device=qkv.device, dtype=torch.float32)
-            _lib.call("dhz_bias_gather", _p(table.contiguous()), _p(bias), H, _stream())
-        ps_attn_fwd_launch(qkv, idx, bias, mask, out, rank, B_, H, d)
+        rank = torch.empty((B_ * H * N,), device=qkv.device, dtype=torch.uint8)
+        bias = bias_tile(table, H, N) if table is not None else None
+        ps_attn_fwd_launch(qkv, idx, bias, mask, out, rank, B_, H, d, N)
         ctx.save_for_backward(qkv, bias, mask, rank)
-        ctx.dims = (B_, H, d)
+        ctx.dims = (B_, H, d, N)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         qkv, bias, mask, rank = ctx.saved_tensors
-        B_, H, d = ctx.dims
+        B_, H, d, N = ctx.dims
         dout = dout.contiguous()
         dqkv = torch.empty_like(qkv)
         dpart, dtable = None, None
-        parts = _lib.load().dhz_ps_attn_bwd_parts_d(B_, H, d)
+        parts = _lib.load().dhz_ps_attn_bwd_parts_d(B_, H, d) if N == NTOK else _lib.load().dhz_ps_attn_bwd_parts_w(B_, H, d, _win_of(N))
         if bias is not None:
-            dpart = torch.empty((parts, NTOK, NTOK), device=qkv.device, dtype=torch.float32)
-        ps_attn_bwd_launch(qkv, dqkv, bias, mask, rank, dout, dpart, B_, H, d)
+            dpart = torch.empty((parts, N, N), device=qkv.device, dtype=torch.float32)
+        ps_attn_bwd_launch(qkv, dqkv, bias, mask, rank, dout, dpart, B_, H, d, N)
         if bias is not None:
-            dtable = torch.empty((225, H), device=qkv.device, dtype=torch.float32)
-            _lib.call("dhz_bias_table_grad", _p(dpart), parts, _p(dtable), H, 0, _stream())
+            dtable = bias_table_grad(dpart, parts, H, N)
         return dqkv, dtable, None, None, None, None
 
 
@@ -542,20 +584,22 @@ def ps_window_attention(qkv, table, idx, mask, H, d):
 
 
 def ps_window_attention_rank(qkv, table, idx, mask, H, d):
-    """Forward only; also returns the saved selection ranks [B_,H,64] (tests / diagnostics)."""
+    """Forward only; also returns the saved selection ranks [B_,H,N] (tests / diagnostics)."""
     T = qkv.shape[0]
     C = H * d
-    B_ = T // NTOK
+    N = idx.shape[0]
+    B_ = T // N
     out = torch.empty((T, C), device=qkv.device, dtype=torch.float32)
-    rank = torch.empty((B_, H, NTOK), device=qkv.device, dtype=torch.uint8)
-    bias = None
-    if table is not None:
-        bias = torch.empty((H, NTOK, NTOK), device=qkv.device, dtype=torch.float32)
-        _lib.call("dhz_bias_gather", _p(table.contiguous()), _p(bias), H, _stream())
+    rank = torch.empty((B_, H, N), device=qkv.device, dtype=torch.uint8)
+    bias = bias_tile(table, H, N) if table is not None else None
     nW = mask.shape[0] if mask is not None else 1
     base = qkv.data_ptr()
-    _lib.call("dhz_ps_attn_fwd", base, base + 4 * C, base + 8 * C, 3 * C, _p(idx), _p(bias), _p(mask), _p(out), C,
-              _p(rank), B_, H, nW, d, _stream())
+    if N == NTOK:
+        _lib.call("dhz_ps_attn_fwd", base, base + 4 * C, base + 8 * C, 3 * C, _p(idx), _p(bias), _p(mask), _p(out), C,
+                  _p(rank), B_, H, nW, d, _stream())
+    else:
+        _lib.call("dhz_ps_attn_fwd_w", base, base + 4 * C, base + 8 * C, 3 * C, _p(idx), _p(bias), _p(mask), _p(out), C,
+                  _p(rank), B_, H, nW, d, _win_of(N), 0, _stream())
     return out, rank
 
 
@@ -563,48 +607,60 @@ class _DenseWindowAttention(Function):
     """Dense window attention (My_model twin, M0:428-492) on a packed [T,3C] QKV buffer."""
 
     @staticmethod
-    def forward(ctx, qkv, table, mask, H, d, scale):
+    def forward(ctx, qkv, table, mask, H, d, scale, N):
         _require_gpu(qkv, table, mask)
         T, C3 = qkv.shape
         C = H * d
-        assert C3 == 3 * C and T % NTOK == 0 and qkv.is_contiguous()
-        B_ = T // NTOK
+        assert C3 == 3 * C and T % N == 0 and qkv.is_contiguous() and (mask is None or tuple(mask.shape[1:]) == (N, N))
+        B_ = T // N
         out = torch.empty((T, C), device=qkv.device, dtype=torch.float32)
-        bias = torch.empty((H, NTOK, NTOK), device=qkv.device, dtype=torch.float32)
-        _lib.call("dhz_bias_gather", _p(table.contiguous()), _p(bias), H, _stream())
+        bias = bias_tile(table, H, N)
         nW = mask.shape[0] if mask is not None else 1
         base = qkv.data_ptr()
-        _lib.call("dhz_dense_attn_fwd", base, base + 4 * C, base + 8 * C, 3 * C, _p(bias), _p(mask), _p(out), C, B_, H,
-                  nW, d, float(scale), _stream())
+        if N == NTOK:
+            _lib.call("dhz_dense_attn_fwd", base, base + 4 * C, base + 8 * C, 3 * C, _p(bias), _p(mask), _p(out), C, B_, H,
+                      nW, d, float(scale), _stream())
+        else:
+            _lib.call("dhz_dense_attn_fwd_w", base, base + 4 * C, base + 8 * C, 3 * C, _p(bias), _p(mask), _p(out), C, B_, H,
+                      nW, d, float(scale), _win_of(N), _stream())
         ctx.save_for_backward(qkv, bias, mask)
-        ctx.dims = (B_, H, d, nW, float(scale))
+        ctx.dims = (B_, H, d, nW, float(scale), N)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         qkv, bias, mask = ctx.saved_tensors
-        B_, H, d, nW, scale = ctx.dims
+        B_, H, d, nW, scale, N = ctx.dims
         C = H * d
         dout = dout.contiguous()
         dqkv = torch.empty_like(qkv)
-        parts = _lib.load().dhz_ps_attn_bwd_parts(B_, H)
-        dpart = torch.empty((parts, NTOK, NTOK), device=qkv.device, dtype=torch.float32)
+        parts = _lib.load().dhz_ps_attn_bwd_parts(B_, H) if N == NTOK else _lib.load().dhz_ps_attn_bwd_parts_w(B_, H, d, _win_of(N))
+        dpart = torch.empty((parts, N, N), device=qkv.device, dtype=torch.float32)
         base, gb = qkv.data_ptr(), dqkv.data_ptr()
-        _lib.call("dhz_dense_attn_bwd", base, base + 4 * C, base + 8 * C, 3 * C, _p(bias), _p(mask), _p(dout), C,
-                  gb, gb + 4 * C, gb + 8 * C, 3 * C, _p(dpart), B_, H, nW, d, scale, _stream())
-        dtable = torch.empty((225, H), device=qkv.device, dtype=torch.float32)
-        _lib.call("dhz_bias_table_grad", _p(dpart), parts, _p(dtable), H, 0, _stream())
-        return dqkv, dtable, None, None, None, None
+        if N == NTOK:
+            _lib.call("dhz_dense_attn_bwd", base, base + 4 * C, base + 8 * C, 3 * C, _p(bias), _p(mask), _p(dout), C,
+                      gb, gb + 4 * C, gb + 8 * C, 3 * C, _p(dpart), B_, H, nW, d, scale, _stream())
+        else:
+            _lib.call("dhz_dense_attn_bwd_w", base, base + 4 * C, base + 8 * C, 3 * C, _p(bias), _p(mask), _p(dout), C,
+                      gb, gb + 4 * C, gb + 8 * C, 3 * C, _p(dpart), B_, H, nW, d, scale, _win_of(N), _stream())
+        return dqkv, bias_table_grad(dpart, parts, H, N), None, None, None, None, None
 
 
-def dense_window_attention(qkv, table, mask, H, d, scale):
-    return _DenseWindowAttention.apply(qkv, table, mask, H, d, scale)
+def dense_window_attention(qkv, table, mask, H, d, scale, N=NTOK):
+    """N: tokens per window (64 or 16)"""
+    _win_of(N)
+    return _DenseWindowAttention.apply(qkv, table, mask, H, d, scale, N)
 
 
-def shift_mask(Hres, Wres, shift, device):
-    """[nW,64,64] 0/-100 mask of M1:803-836 (cached by callers; depends only on the geometry)."""
-    m = torch.empty(((Hres // 8) * (Wres // 8), NTOK, NTOK), device=device, dtype=torch.float32)
-    _lib.call("dhz_shift_mask", _p(m), Hres, Wres, shift, _stream())
+def shift_mask(Hres, Wres, shift, device, win=8):
+    """[nW, win^2, win^2] 0/-100 mask of M1:803-836 (cached by callers; depends only on the geometry)."""
+    N = win * win
+    _win_of(N)
+    m = torch.empty(((Hres // win) * (Wres // win), N, N), device=device, dtype=torch.float32)
+    if win == 8:
+        _lib.call("dhz_shift_mask", _p(m), Hres, Wres, shift, _stream())
+    else:
+        _lib.call("dhz_shift_mask_w", _p(m), Hres, Wres, shift, win, _stream())
     return m
 
 
@@ -814,75 +870,93 @@ def linear_tokens(x, *wb):
 # ----------------------------------------------------------------------------- K1
 class _LNPartition(Function):
     @staticmethod
-    def forward(ctx, x, gamma, beta, Hres, Wres, shift, partition):
+    def forward(ctx, x, gamma, beta, Hres, Wres, shift, partition, win):
         _require_gpu(x, gamma, beta)
         x = x.contiguous()
         B, L, C = x.shape
         assert L == Hres * Wres
         y = torch.empty((B * L, C), device=x.device, dtype=x.dtype)
         stats = torch.empty((B * L, 2), device=x.device, dtype=torch.float32)
-        _lib.call("dhz_ln_partition_fwd_dt", _p(x), _p(gamma), _p(beta), _p(y), _p(stats), B, Hres, Wres, C, shift,
-                  int(partition), _dt(x), _stream())
+        if win == 8:
+            _lib.call("dhz_ln_partition_fwd_dt", _p(x), _p(gamma), _p(beta), _p(y), _p(stats), B, Hres, Wres, C, shift,
+                      int(partition), _dt(x), _stream())
+        else:
+            _lib.call("dhz_ln_partition_fwd_w", _p(x), _p(gamma), _p(beta), _p(y), _p(stats), B, Hres, Wres, C, shift,
+                      int(partition), win, _dt(x), _stream())
         ctx.save_for_backward(x, gamma, stats)
-        ctx.geom = (B, Hres, Wres, C, shift, int(partition))
+        ctx.geom = (B, Hres, Wres, C, shift, int(partition), win)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, gamma, stats = ctx.saved_tensors
-        B, Hres, Wres, C, shift, partition = ctx.geom
+        B, Hres, Wres, C, shift, partition, win = ctx.geom
         dy = dy.contiguous()
         dx = torch.empty_like(x)
         dgb = torch.zeros((2, C), device=x.device, dtype=torch.float32)
-        _lib.call("dhz_ln_partition_bwd_dt", _p(dy), _p(x), _p(gamma), _p(stats), None, _p(dx), dgb[0].data_ptr(),
-                  dgb[1].data_ptr(), B, Hres, Wres, C, shift, partition, _dt(x), _stream())
-        return dx, dgb[0], dgb[1], None, None, None, None
+        if win == 8:
+            _lib.call("dhz_ln_partition_bwd_dt", _p(dy), _p(x), _p(gamma), _p(stats), None, _p(dx), dgb[0].data_ptr(),
+                      dgb[1].data_ptr(), B, Hres, Wres, C, shift, partition, _dt(x), _stream())
+        else:
+            _lib.call("dhz_ln_partition_bwd_w", _p(dy), _p(x), _p(gamma), _p(stats), None, _p(dx), dgb[0].data_ptr(),
+                      dgb[1].data_ptr(), B, Hres, Wres, C, shift, partition, win, _dt(x), _stream())
+        return dx, dgb[0], dgb[1], None, None, None, None, None
 
 
-def ln_partition(x, gamma, beta, Hres, Wres, shift):
-    """LayerNorm -> roll(-shift) -> window_partition  (M1:839-852).  [B,L,C] -> [B*nW*64, C]."""
-    return _LNPartition.apply(x, gamma, beta, Hres, Wres, shift, True)
+def ln_partition(x, gamma, beta, Hres, Wres, shift, win=8):
+    """LayerNorm -> roll(-shift) -> window_partition  (M1:839-852).  [B,L,C] -> [B*nW*win*win, C]."""
+    _win_of(win * win)
+    return _LNPartition.apply(x, gamma, beta, Hres, Wres, shift, True, win)
 
 
 def layer_norm_tokens(x, gamma, beta):
     """Plain LayerNorm over the last dim, tokens stay in place (norm2, M1:873). [B,L,C] -> [B*L, C]."""
-    return _LNPartition.apply(x, gamma, beta, x.shape[1], 1, 0, False)
+    return _LNPartition.apply(x, gamma, beta, x.shape[1], 1, 0, False, 8)
 
 
 # ----------------------------------------------------------------------------- K4 tail
 class _ReverseResidual(Function):
     @staticmethod
-    def forward(ctx, yw, shortcut, scale, Hres, Wres, shift, partition):
+    def forward(ctx, yw, shortcut, scale, Hres, Wres, shift, partition, win):
         _require_gpu(yw, shortcut, scale)
         shortcut = shortcut.contiguous()
         yw = yw.contiguous()
         B, L, C = shortcut.shape
         out = torch.empty_like(shortcut)
-        _lib.call("dhz_reverse_residual_fwd_dt", _p(yw), _p(shortcut), _p(scale), _p(out), B, Hres, Wres, C, shift,
-                  int(partition), _dt(shortcut), _stream())
+        if win == 8:
+            _lib.call("dhz_reverse_residual_fwd_dt", _p(yw), _p(shortcut), _p(scale), _p(out), B, Hres, Wres, C, shift,
+                      int(partition), _dt(shortcut), _stream())
+        else:
+            _lib.call("dhz_reverse_residual_fwd_w", _p(yw), _p(shortcut), _p(scale), _p(out), B, Hres, Wres, C, shift,
+                      int(partition), win, _dt(shortcut), _stream())
         ctx.save_for_backward(scale)
-        ctx.geom = (B, Hres, Wres, C, shift, int(partition), tuple(yw.shape))
+        ctx.geom = (B, Hres, Wres, C, shift, int(partition), tuple(yw.shape), win)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         (scale,) = ctx.saved_tensors
-        B, Hres, Wres, C, shift, partition, yshape = ctx.geom
+        B, Hres, Wres, C, shift, partition, yshape, win = ctx.geom
         dout = dout.contiguous()
         dyw = torch.empty(yshape, device=dout.device, dtype=dout.dtype)
-        _lib.call("dhz_reverse_residual_bwd_dt", _p(dout), _p(scale), _p(dyw), B, Hres, Wres, C, shift, partition,
-                  _dt(dout), _stream())
-        return dyw, dout, None, None, None, None, None
+        if win == 8:
+            _lib.call("dhz_reverse_residual_bwd_dt", _p(dout), _p(scale), _p(dyw), B, Hres, Wres, C, shift, partition,
+                      _dt(dout), _stream())
+        else:
+            _lib.call("dhz_reverse_residual_bwd_w", _p(dout), _p(scale), _p(dyw), B, Hres, Wres, C, shift, partition, win,
+                      _dt(dout), _stream())
+        return dyw, dout, None, None, None, None, None, None
 
 
-def reverse_residual(yw, shortcut, scale, Hres, Wres, shift):
+def reverse_residual(yw, shortcut, scale, Hres, Wres, shift, win=8):
     """window_reverse -> roll(+shift) -> shortcut + drop_path(.)  (M1:859-872)."""
-    return _ReverseResidual.apply(yw, shortcut, scale, Hres, Wres, shift, True)
+    _win_of(win * win)
+    return _ReverseResidual.apply(yw, shortcut, scale, Hres, Wres, shift, True, win)
 
 
 def residual_scale(y, shortcut, scale):
     """shortcut + scale[b] * y with y already in token order (M1:873)."""
-    return _ReverseResidual.apply(y, shortcut, scale, shortcut.shape[1], 1, 0, False)
+    return _ReverseResidual.apply(y, shortcut, scale, shortcut.shape[1], 1, 0, False, 8)
 
 
 # ----------------------------------------------------------------------------- K5 middle
