@@ -367,16 +367,18 @@ int dhz_ps_attn_bwd_dt(const void* q, const void* k, const void* v, int ld, cons
  *     (query/key/value/out projections ATT:420-422,454-458; LeFF linear1/linear2 M1:487-492):
  *     dw[N,K] += dy^T[N,T] . x[T,K]        db[N] += sum_t dy[t,:]        (ACCUMULATED: caller zeroes,
  *     which lets the gradients land directly in the optimizer's flat gradient buffer).
- *     dy: [T,N] with row stride ldy, x: [T,K] with row stride ldx; T % 32 == 0, N % 32 == 0, K % 32 == 0.
- *     db may be NULL.  Default mode: the token slabs meet in fp32 atomics, the summation order over T is not deterministic and the slab count
+ *     dy: [T,N] with row stride ldy, x: [T,K] with row stride ldx; T % 16 == 0 (tokens in 16s: a 4x4 map has 16 per image), N % 16 == 0,
+ *     K % 16 == 0.  Rows at or beyond T are never read: dy and x may end at row T of their allocation.  db may be NULL.  Default mode: the token slabs meet in fp32 atomics, the summation order over T is not deterministic and the slab count
  *     follows the CU count.  Deterministic mode (dhz_set_deterministic): slabs cut by the shape alone, stored and summed in slab order. */
 int dhz_linear_wgrad(const float* dy, int ldy, const float* x, int ldx, int T, int N, int K,
                      float* dw, float* db, void* stream);
 /*      Same contraction for nmat (1..4) parameters that share the input x - the Q / K / V projections of
  *      AttentionLayer.forward (ATT:385-461): columns [i*nper, (i+1)*nper) of dy belong to dw[i] / db[i] (HOST arrays of
- *      nmat device pointers; db may be NULL, or all of its entries NULL).  One launch reads x once instead of nmat times. */
+ *      nmat device pointers; db may be NULL, or all of its entries NULL).  One launch reads x once instead of nmat times.
+ *      T % 16 == 0 as above; rows at or beyond T are never read. */
 /*      dhz_linear_wgrad with row t of dy multiplied by row_scale[t / rows_per_scale] on the way in (per-image DropPath scale of the
- *      branch output; rows_per_scale a multiple of 32 that divides T; row_scale NULL = plain dhz_linear_wgrad). */
+ *      branch output; rows_per_scale a multiple of 32 that divides T - with a row scale T therefore stays in 32s; row_scale NULL =
+ *      plain dhz_linear_wgrad, tokens in 16s; rows at or beyond T are never read). */
 int dhz_linear_wgrad_rs(const float* dy, int ldy, const float* x, int ldx, int T, int N, int K, float* dw, float* db,
                         const float* row_scale, int rows_per_scale, void* stream);
 int dhz_linear_wgrad_multi(const float* dy, int ldy, const float* x, int ldx, int T, int nmat, int nper, int K,

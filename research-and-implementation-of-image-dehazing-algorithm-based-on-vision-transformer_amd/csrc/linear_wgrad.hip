@@ -17,6 +17,8 @@ namespace {
 #define WG_ABL 0          // timing diagnostics (tools/variants.sh): 1 no epilogue atomics, 2 no MFMAs, 4 no global loads, 8 no bias sums
 #endif
 constexpr int TK = 32;   // tokens per LDS stage
+constexpr int TQ = 16;   // T comes in TQs: the last stage of a launch may hold only TQ live tokens (a 4x4 map has 16 tokens per image)
+constexpr int stages_of(int T) { return (T + TK - 1) / TK; }
 // fragment vector width of an operand whose wave tile is W 16 x 16 tiles wide, and the conflict-free LDS row stride for it
 constexpr int frag_vec(int W) { return (W == 4 || W == 2) ? W : 1; }
 constexpr int row_stride(int B, int W) {
@@ -36,8 +38,10 @@ struct WgradOut {
 };
 
 // WM, WN: 16x16 tiles per wave along N (rows of dW) and K (cols of dW); waves are NWM x 2 (NWM = 2: 256 threads,
-// NWM = 4: 512 threads and a 256-row tile - twice the FLOP per staged byte for the compute-bound shapes)
-template <int WM, int WN, int NWM, int TG, bool DET = false>
+// NWM = 4: 512 threads and a 256-row tile - twice the FLOP per staged byte for the compute-bound shapes).
+// HALF: T % TK == TQ, the launch ends in a half stage.  A template flag and not a run-time test: the instances for T % TK == 0
+// are, instruction for instruction, the kernels they were before half stages existed.
+template <int WM, int WN, int NWM, int TG, bool DET = false, bool HALF = false>
 __global__ __launch_bounds__(128 * NWM * TG) void linear_wgrad_kernel(const float* __restrict__ dy, int ldy,
                                                                 const float* __restrict__ x, int ldx, int T, int N,
                                                                 int K, WgradOut out, int nsplit) {
@@ -74,8 +78,9 @@ __global__ __launch_bounds__(128 * NWM * TG) void linear_wgrad_kernel(const floa
     const size_t det_off = DET ? (size_t)split * out.det_stride : 0;          // deterministic mode: this slab's slot of the workspace
     float* __restrict__ const dw = out.dw[mat] + det_off;
     float* __restrict__ const db = out.db[mat] ? out.db[mat] + det_off : nullptr;
-    // token slab of this workgroup (multiples of TK); its stages are dealt round-robin to the TG token groups
-    const int nst = T / TK;
+    // token slab of this workgroup (multiples of TK); its stages are dealt round-robin to the TG token groups.  HALF: the TQ live
+    // tokens behind the last full stage count as one more stage (stage T / TK, the last one of the last slab)
+    const int nst = HALF ? stages_of(T) : T / TK;
     const int st0 = (int)((long long)nst * split / nsplit), st1 = (int)((long long)nst * (split + 1) / nsplit);
 
     f32x4 acc[WM][WN];
@@ -94,6 +99,9 @@ __global__ __launch_bounds__(128 * NWM * TG) void linear_wgrad_kernel(const floa
     const bool do_db = (db != nullptr) && (tn == 0);
 
     int st_loaded = 0;                                 // stage whose rows sit in ra / rb
+    // The half stage: rows TQ.. of it lie at or beyond T.  They become zeros in registers - the MFMAs and the bias sums below need
+    // no second path - and NO load is issued for them: dy and x may end at row T of their allocation.  (TQ * A4 and TQ * B4 are
+    // multiples of 64: a wave loads a staged element or skips it as a whole.)
     auto gload = [&](int st) {
         st_loaded = st;
         if (WG_ABL & 4) return;
@@ -101,14 +109,20 @@ __global__ __launch_bounds__(128 * NWM * TG) void linear_wgrad_kernel(const floa
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
             const int e = tl + GT * i;
-            if (TK * A4 % GT == 0 || e < TK * A4)
+            if (TK * A4 % GT == 0 || e < TK * A4) {
+                if constexpr (HALF)
+                    if (st == T / TK && e >= TQ * A4) { ra[i] = f32x4{0.f, 0.f, 0.f, 0.f}; continue; }
                 ra[i] = *reinterpret_cast<const f32x4*>(dy + (tok0 + e / A4) * ldy + n0 + (e % A4) * 4);
+            }
         }
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
             const int e = tl + GT * i;
-            if (TK * B4 % GT == 0 || e < TK * B4)
+            if (TK * B4 % GT == 0 || e < TK * B4) {
+                if constexpr (HALF)
+                    if (st == T / TK && e >= TQ * B4) { rb[i] = f32x4{0.f, 0.f, 0.f, 0.f}; continue; }
                 rb[i] = *reinterpret_cast<const f32x4*>(x + (tok0 + e / B4) * ldx + k0 + (e % B4) * 4);
+            }
         }
     };
     auto swrite = [&](int buf) {
@@ -230,7 +244,7 @@ __global__ __launch_bounds__(128 * NWM * TG) void linear_wgrad_kernel(const floa
     }
 }
 
-template <int WM, int WN, int NWM = 2, int TG = 1>
+template <int WM, int WN, int NWM, int TG, bool HALF>
 int launch(const float* dy, int ldy, const float* x, int ldx, int T, int N, int K, const WgradOut& out, hipStream_t s) {
     constexpr int BM = 16 * WM * NWM, BN = 32 * WN;
     constexpr size_t stage = (size_t)TK * (row_stride(BM, WM) + row_stride(BN, WN)) * sizeof(float);
@@ -250,33 +264,34 @@ int launch(const float* dy, int ldy, const float* x, int ldx, int T, int N, int 
     int target = env_target > 0 ? env_target : (NWM * TG == 4 ? ncu : 2 * ncu);   // 2 (1 for 512 threads) workgroups per CU
     if (2 * smem > 160 * 1024 && target > ncu) target = ncu;
     int nsplit = target / tiles;
-    const int max_split = T / (TK * 4 * TG) > 0 ? T / (TK * 4 * TG) : 1;     // at least 4 stages per token group
+    const int nst = stages_of(T);                                            // a half stage counts as a stage
+    const int max_split = nst / (4 * TG) > 0 ? nst / (4 * TG) : 1;           // at least 4 stages per token group
     if (nsplit > max_split) nsplit = max_split;
     if (nsplit < 1) nsplit = 1;
     // short token slabs pay the per-workgroup epilogue (BM*BN atomics) over too few stages: below 16 stages per workgroup
     // trade splits for stages down to one workgroup per CU (measured: 70 -> 62 us at T=32768, N=512, K=128; 73 -> 64 us at
     // T=131072, N=K=128; the long-slab shapes are untouched)
-    if (env_target <= 0 && (T / TK) / nsplit < 16) {
+    if (env_target <= 0 && nst / nsplit < 16) {
         int alt = ncu / tiles;
-        if (alt < (T / TK) / 16) alt = (T / TK) / 16;
+        if (alt < nst / 16) alt = nst / 16;
         if (alt >= 1 && alt < nsplit) nsplit = alt;
     }
     if (smem > 48 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_wgrad_kernel<WM, WN, NWM, TG>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_wgrad_kernel<WM, WN, NWM, TG, false, HALF>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     if (dhz_det()) {
         const char* who = "dhz_linear_wgrad";
         WgradOut o2; DetSegs segs; float* ws; long slot;
         if (int rc = dhz_det_wgrad_begin(who, out, N / out.nper, K, nsplit, o2, segs, ws, slot)) return rc;
         if (smem > 48 * 1024)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_wgrad_kernel<WM, WN, NWM, TG, true>),
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_wgrad_kernel<WM, WN, NWM, TG, true, HALF>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        hipLaunchKernelGGL((linear_wgrad_kernel<WM, WN, NWM, TG, true>), dim3(tiles * nsplit), dim3(128 * NWM * TG), smem, s, dy, ldy, x,
+        hipLaunchKernelGGL((linear_wgrad_kernel<WM, WN, NWM, TG, true, HALF>), dim3(tiles * nsplit), dim3(128 * NWM * TG), smem, s, dy, ldy, x,
                            ldx, T, N, K, o2, nsplit);
         DHZ_CHECK_LAUNCH(who);
         return dhz_det_reduce(who, ws, nsplit, slot, segs, s);
     }
-    hipLaunchKernelGGL((linear_wgrad_kernel<WM, WN, NWM, TG>), dim3(tiles * nsplit), dim3(128 * NWM * TG), smem, s, dy, ldy, x,
+    hipLaunchKernelGGL((linear_wgrad_kernel<WM, WN, NWM, TG, false, HALF>), dim3(tiles * nsplit), dim3(128 * NWM * TG), smem, s, dy, ldy, x,
                        ldx, T, N, K, out, nsplit);
     return 0;
 }
@@ -322,7 +337,7 @@ __global__ __launch_bounds__(256) void narrow_wgrad_kernel(const float* __restri
 static int wgrad_dispatch(const char* who, const float* dy, int ldy, const float* x, int ldx, int T, int nmat, int nper, int K,
                           const WgradOut& out, hipStream_t s) {
     const int N = nmat * nper;
-    DHZ_REQUIRE(T > 0 && T % TK == 0, "%s: T=%d must be a multiple of %d", who, T, TK);
+    DHZ_REQUIRE(T > 0 && T % TQ == 0, "%s: T=%d must be a multiple of %d", who, T, TQ);
     if (nper > 0 && K > 0 && (nper % 32 || K % 32) && nper % 16 == 0 && K % 16 == 0) {         // narrow shapes (embed_dim 16)
         const int ntile = (N / 16) * (K / 16), groups = (ntile + 3) / 4;
         int nslab = 2048 / groups;                                                             // ~2048 workgroups, slabs of >= 64 tokens
@@ -354,11 +369,14 @@ static int wgrad_dispatch(const char* who, const float* dy, int ldy, const float
     const int bm = 32 * wm, bn = 32 * wn;
     const int tiles = (N / bm) * (K / bn);
     const int splits2 = dhz_part_cus() / tiles > 0 ? dhz_part_cus() / tiles : 1;
-    const bool two = tg_env ? tg_env == 2 : (T / TK) / splits2 >= 8;
-#define CASE(a, b)                                                               \
-    if (wm == a && wn == b) {                                                    \
-        if (two) rc = launch<a, b, 2, 2>(dy, ldy, x, ldx, T, N, K, out, s);      \
-        else rc = launch<a, b>(dy, ldy, x, ldx, T, N, K, out, s);                \
+    const bool two = tg_env ? tg_env == 2 : stages_of(T) / splits2 >= 8;
+    const bool half = T % TK != 0;
+#define CASE(a, b)                                                                                   \
+    if (wm == a && wn == b) {                                                                        \
+        if (two) rc = half ? launch<a, b, 2, 2, true>(dy, ldy, x, ldx, T, N, K, out, s)              \
+                           : launch<a, b, 2, 2, false>(dy, ldy, x, ldx, T, N, K, out, s);            \
+        else rc = half ? launch<a, b, 2, 1, true>(dy, ldy, x, ldx, T, N, K, out, s)                  \
+                       : launch<a, b, 2, 1, false>(dy, ldy, x, ldx, T, N, K, out, s);                \
     }
     int rc = DHZ_OK;
     CASE(1, 1) CASE(1, 2) CASE(1, 4) CASE(2, 1) CASE(2, 2) CASE(2, 4) CASE(3, 1) CASE(3, 2) CASE(3, 4)

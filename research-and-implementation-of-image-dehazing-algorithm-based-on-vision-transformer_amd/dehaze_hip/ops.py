@@ -749,10 +749,11 @@ def linear_wgrad(dy, off, x, params, row_scale=None):
     dy [T, .] and their common input x [T, K].  Returns the autograd slots (dW_1, db_1, dW_2, ...): None for a frozen Linear and for
     gradients that were accumulated in place into .grad (leaf parameters; GRAD_READY is told), fresh tensors otherwise.
     row_scale = (scale[B], rows_per_scale): row t of dy counts as scale[t // rows_per_scale] * dy[t] (fp32, one Linear only).
-    The kernels' shape contract: bf16 storage - T, N, K in 64s; fp32 - T in 32s, N and K in 16s (the 16-wide tile forms exist for the
-    embed_dim = 16 model, csrc/linear_wgrad.hip).  There is deliberately no library fallback."""
+    The kernels' shape contract: bf16 storage - T, N, K in 64s; fp32 - T, N and K in 16s (a 4x4 bottleneck has 16 tokens per image: any
+    batch trains; the 16-wide tile forms exist for the embed_dim = 16 model, csrc/linear_wgrad.hip).  With a row_scale, rows_per_scale
+    is a multiple of 32.  There is deliberately no library fallback."""
     T, K = x.shape
-    q, tq = (64, 64) if dy.dtype == BF16 else (16, 32)
+    q, tq = (64, 64) if dy.dtype == BF16 else (16, 16)
     slots, targets, inplace = [], [], []
     for w, b in params:
         pair = None
