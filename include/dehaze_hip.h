@@ -423,6 +423,47 @@ int dhz_maxpool2x2_blocked_bwd(const float* gy, const float* act, float* gx, int
 int dhz_layout_blocked8(const float* src, float* dst, int B, int C, int HW, int to_blocked, const float* bias, int relu,
                         void* stream);   /* towards the blocked layout optionally dst = max(src + bias[c], 0) */
 
+/* K11a dhz_winograd_conv3x3 with LeakyReLU(0.01) in its store: the Conv2d(3x3, pad 1) + LeakyReLU pairs of the UNet baseline's ConvBlock
+ *      and their autograd (M1:28-40: aten::convolution + aten::leaky_relu_, the `+ conv11(x)` of M1:40, aten::leaky_relu_backward +
+ *      aten::convolution_backward's input gradient) without an elementwise pass over the map.  Same tensors, layout and shape contract
+ *      as dhz_winograd_conv3x3 (upack from dhz_winograd_prepack).
+ *        backward == 0:  y = leaky(conv(x, W) + bias) + out_addend    (bias, out_addend may be NULL; out_mask must be NULL)
+ *        backward != 0:  y = (conv(x, W') + out_addend) * (out_mask > 0 ? 1 : 0.01)   with W' the backward-data filters and out_mask the
+ *                        saved LeakyReLU output at the OUTPUT positions, whose sign is the pre-activation's (bias must be NULL).  With an
+ *                        out_addend the forward's y is not that activation: a caller that needs the sign later keeps the addend out of this
+ *                        store (dehaze_hip/unet.py adds conv11(x) in dhz_blocked8_to_tokens).
+ *      There is no F(4x4,3x3) instance of this entry. */
+int dhz_winograd_conv3x3_act(const float* x, const float* upack, const float* bias, int backward, const float* out_mask,
+                             const float* out_addend, float* y, int B, int H, int W, int C, int K, void* stream);
+
+/*      Layout changes between tokens [B][HW][C] (row stride ld floats, ld % 4 == 0) and the blocked layout [B][C/8][HW][8], C % 8 == 0,
+ *      16-byte aligned pointers, with the elementwise factors of a ConvBlock (M1:28-40) folded into the copy:
+ *      dhz_tokens_to_blocked8: blk = tok * (leaky_mask > 0 ? 1 : 0.01) - the aten::leaky_relu_backward of a gradient on its way to the
+ *        backward-data and weight-gradient kernels; leaky_mask (blocked, the saved LeakyReLU output) may be NULL: a plain copy.
+ *      dhz_blocked8_to_tokens: tok = blk + addend (tokens with row stride ld_add; may be NULL) - the `+ conv11(x)` of M1:40. */
+int dhz_tokens_to_blocked8(const float* tok, int ld, const float* leaky_mask, float* blk, int B, int HW, int C, void* stream);
+int dhz_blocked8_to_tokens(const float* blk, const float* addend, int ld_add, float* tok, int ld, int B, int HW, int C, void* stream);
+
+/* K11w Weight and bias gradient of a dense 3x3 / stride 1 / pad 1 convolution (csrc/conv3x3_wgrad.hip) in the same channel-blocked layout
+ *      as K11, so that forward, backward-data and weight gradient of a layer share their maps without a repacking pass.  Replaces the
+ *      weight / bias outputs of aten::convolution_backward that autograd runs for the nn.Conv2d(C, K, 3, padding=1) layers of the UNet
+ *      baseline's ConvBlock (M1:28-40; the VGG filters of K11 are frozen and never needed it).
+ *        x  [B][Cin/8][H][W][8], dy [B][Kout/8][H][W][8];  dw [Kout][Cin][3][3] and db [Kout] (may be NULL) are WRITTEN, not accumulated:
+ *        dw[k][c][r][s] = sum_{b,h,w} dy[b][k][h][w] x[b][c][h+r-1][w+s-1],  db[k] = sum dy[b][k][h][w].  The zero padding around the map is
+ *        never read: x may begin and end with its allocation.
+ *        Cin and Kout multiples of 32, up to 512; H and W multiples of 16, or H == W == 8; any B >= 1; anything else DHZ_EINVAL before
+ *        any launch.
+ *      The contraction over B*H*W is cut into dhz_conv3x3_wgrad_parts(...) slabs of whole 64-position chunks (4 rows x 16 columns, or one
+ *      8 x 8 image; B*(H/4)*(W/16) or B chunks), accumulated in fp32 on the fp32 matrix pipe by a persistent grid, stored to the workspace
+ *      and summed in slab order by a second kernel.  No atomics; the cut depends on the shapes alone: the same bits from run to run, under
+ *      any dhz_set_reserved_cus, with the deterministic mode on or off.
+ *      ws: dhz_conv3x3_wgrad_workspace_bytes(...) bytes of device memory (contents undefined before and after; 0 for an unsupported
+ *      shape).  With dhz_set_deterministic on, the mode's workspace (dhz_set_det_workspace) is used instead and ws may be NULL. */
+size_t dhz_conv3x3_wgrad_workspace_bytes(int B, int H, int W, int Cin, int Kout);
+int dhz_conv3x3_wgrad_parts(int B, int H, int W, int Cin, int Kout);
+int dhz_conv3x3_wgrad(const float* x, const float* dy, float* dw, float* db, float* ws, size_t ws_bytes, int B, int H, int W, int Cin,
+                      int Kout, void* stream);
+
 /* K9b  output projection (My_model_1.py:696-723): Conv2d(C -> 3, 3x3, pad 1) from tokens x[B, H*W, C] to an NCHW image
  *      y[B, 3, H, W] (+ bias[3], may be NULL); backward-data dx[B, H*W, C] from dy[B, 3, H, W]; weight / bias gradient
  *      dw[3, C, 3, 3], db[3] (ACCUMULATED; db may be NULL).  w is the layer's own [3, C, 3, 3] tensor.  C in {64, 128}. */

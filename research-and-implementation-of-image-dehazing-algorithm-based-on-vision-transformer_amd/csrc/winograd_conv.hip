@@ -66,7 +66,12 @@ __device__ __forceinline__ void wave_sync() {
 // Q8: 8 x 8 maps (the last VGG layer of the loss, conv5_1).  FOUR images form one virtual 16 x 16 block (2 x 2 arrangement): the
 // patch offsets carry the image of every pixel, the 4 x 4 input window of a tile is masked where it reaches into the
 // neighbouring image (that is where the tile's own image has its zero padding), and the stores scatter back per image.
-template <bool FWD, bool Q8>
+//
+// LEAKY (dhz_winograd_conv3x3_act, the UNet baseline's ConvBlock M1:28-40): LeakyReLU(0.01) instead of ReLU.  Forward
+// y = leaky(conv(x) + bias) [+ addend] (the block's conv11 branch joins in the store); backward y = (conv(x) + addend) * (mask > 0 ? 1 : 0.01).
+// The instances without it are the ones that existed before: same code, same bits.
+constexpr float LEAKY_SLOPE = 0.01f;
+template <bool FWD, bool Q8, bool LEAKY = false>
 __global__ __launch_bounds__(512) void winograd_conv3x3_kernel(const float* __restrict__ x,
                                                            const float* __restrict__ upack,
                                                            const float* __restrict__ bias, int relu,
@@ -329,7 +334,10 @@ __global__ __launch_bounds__(512) void winograd_conv3x3_kernel(const float* __re
                 const float bv = FWD ? bias_s[k] : 0.f;
                 float y00 = t0[0] + t0[1] + t0[2] + bv, y01 = t0[1] - t0[2] - t0[3] + bv;
                 float y10 = t1[0] + t1[1] + t1[2] + bv, y11 = t1[1] - t1[2] - t1[3] + bv;
-                if (FWD) { y00 = fmaxf(y00, lo); y01 = fmaxf(y01, lo); y10 = fmaxf(y10, lo); y11 = fmaxf(y11, lo); }
+                if (FWD && LEAKY) {
+                    y00 = y00 > 0.f ? y00 : LEAKY_SLOPE * y00; y01 = y01 > 0.f ? y01 : LEAKY_SLOPE * y01;
+                    y10 = y10 > 0.f ? y10 : LEAKY_SLOPE * y10; y11 = y11 > 0.f ? y11 : LEAKY_SLOPE * y11;
+                } else if (FWD) { y00 = fmaxf(y00, lo); y01 = fmaxf(y01, lo); y10 = fmaxf(y10, lo); y11 = fmaxf(y11, lo); }
                 float* o = ys + k * YS + (2 * ty) * 16 + 2 * tx;
                 *reinterpret_cast<float2*>(o) = make_float2(y00, y01);
                 *reinterpret_cast<float2*>(o + 16) = make_float2(y10, y11);
@@ -351,12 +359,16 @@ __global__ __launch_bounds__(512) void winograd_conv3x3_kernel(const float* __re
                 o = ((((size_t)img * KG + kb * 4 + kg) * 8 + (vy & 7)) * 8 + (px & 7)) * 8 + hf * 4;
             } else
                 o = (((size_t)bimg * KG + kb * 4 + kg) * H + wy0 + py) * W * 8 + (size_t)(ox0 + px) * 8 + hf * 4;
-            if (!FWD) {
+            if (!FWD || LEAKY) {
                 if (out_addend) {
                     const float4 ad = *reinterpret_cast<const float4*>(out_addend + o);
                     v4.x += ad.x; v4.y += ad.y; v4.z += ad.z; v4.w += ad.w;
                 }
-                if (out_mask) {
+                if (LEAKY && !FWD && out_mask) {
+                    const float4 m = *reinterpret_cast<const float4*>(out_mask + o);
+                    v4.x = m.x > 0.f ? v4.x : LEAKY_SLOPE * v4.x; v4.y = m.y > 0.f ? v4.y : LEAKY_SLOPE * v4.y;
+                    v4.z = m.z > 0.f ? v4.z : LEAKY_SLOPE * v4.z; v4.w = m.w > 0.f ? v4.w : LEAKY_SLOPE * v4.w;
+                } else if (!FWD && out_mask) {
                     const float4 m = *reinterpret_cast<const float4*>(out_mask + o);
                     v4.x = m.x > 0.f ? v4.x : 0.f; v4.y = m.y > 0.f ? v4.y : 0.f;
                     v4.z = m.z > 0.f ? v4.z : 0.f; v4.w = m.w > 0.f ? v4.w : 0.f;
@@ -560,6 +572,34 @@ extern "C" int dhz_winograd_conv3x3(const float* x, const float* upack, const fl
     else { if (fwd) GO(true, false); else GO(false, false); }
 #undef GO
     DHZ_CHECK_LAUNCH("dhz_winograd_conv3x3");
+    return DHZ_OK;
+}
+
+// LeakyReLU(0.01) in the store.  backward != 0: y = (conv(x, W') + out_addend) * (out_mask > 0 ? 1 : 0.01) with out_mask the saved
+// activation at the OUTPUT positions (bias must be NULL); backward == 0: y = leaky(conv(x, W) + bias) + out_addend (out_mask must be NULL).
+extern "C" int dhz_winograd_conv3x3_act(const float* x, const float* upack, const float* bias, int backward, const float* out_mask,
+                                        const float* out_addend, float* y, int B, int H, int W, int C, int K, void* stream) {
+    DHZ_REQUIRE(x && upack && y, "dhz_winograd_conv3x3_act: null pointer");
+    const bool q8 = H == 8 && W == 8;
+    DHZ_REQUIRE(B > 0 && ((H % 16 == 0 && W % 16 == 0 && H > 0 && W > 0) || q8) && C > 0 && K > 0 && C % CC == 0 && K % KB == 0,
+                "dhz_winograd_conv3x3_act: unsupported shape B=%d H=%d W=%d C=%d K=%d", B, H, W, C, K);
+    DHZ_REQUIRE(backward ? (bias == nullptr && out_mask != nullptr) : out_mask == nullptr,
+                "dhz_winograd_conv3x3_act: forward takes bias / out_addend, backward out_mask / out_addend");
+    const int nblk = q8 ? (B + 3) / 4 : B * (H / 16) * (W / 16);
+    const int grid = ((nblk + 1) / 2) * (K / KB);
+    hipStream_t s = (hipStream_t)stream;
+    const int xcd_group = grid % 8 == 0;
+#define GO(F, Q)                                                                                                         \
+    do {                                                                                                                 \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&winograd_conv3x3_kernel<F, Q, true>),                   \
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)WINO_SMEM);                           \
+        hipLaunchKernelGGL((winograd_conv3x3_kernel<F, Q, true>), dim3(grid), dim3(512), WINO_SMEM, s, x, upack, bias, 0, \
+                           out_mask, out_addend, y, H, W, C, K, nblk, xcd_group, B);                                     \
+    } while (0)
+    if (q8) { if (!backward) GO(true, true); else GO(false, true); }
+    else { if (!backward) GO(true, false); else GO(false, false); }
+#undef GO
+    DHZ_CHECK_LAUNCH("dhz_winograd_conv3x3_act");
     return DHZ_OK;
 }
 

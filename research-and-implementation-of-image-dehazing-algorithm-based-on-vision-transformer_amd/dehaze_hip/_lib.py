@@ -147,8 +147,15 @@ SIGNATURES = {
     "dhz_shift_mask_w": [c_f, c_i, c_i, c_i, c_i, c_p],
     "dhz_bias_gather_w": [c_f, c_f, c_i, c_i, c_p],
     "dhz_bias_table_grad_w": [c_f, c_i, c_f, c_i, c_i, c_i, c_p],
+    # dense 3x3 convolution of the UNet baseline on the channel-blocked layout: LeakyReLU in the Winograd store, weight gradient
+    "dhz_winograd_conv3x3_act": [c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_p],
+    "dhz_tokens_to_blocked8": [c_f, c_i, c_f, c_f, c_i, c_i, c_i, c_p],
+    "dhz_blocked8_to_tokens": [c_f, c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_p],
+    "dhz_conv3x3_wgrad_workspace_bytes": [c_i, c_i, c_i, c_i, c_i],
+    "dhz_conv3x3_wgrad_parts": [c_i, c_i, c_i, c_i, c_i],
+    "dhz_conv3x3_wgrad": [c_f, c_f, c_f, c_f, c_f, ctypes.c_size_t, c_i, c_i, c_i, c_i, c_i, c_p],
 }
-_RESTYPE = {"dhz_last_error": ctypes.c_char_p, "dhz_build_id": ctypes.c_char_p}
+_RESTYPE = {"dhz_last_error": ctypes.c_char_p, "dhz_build_id": ctypes.c_char_p, "dhz_conv3x3_wgrad_workspace_bytes": ctypes.c_size_t}
 
 _lib = None
 
