@@ -267,6 +267,7 @@ extern "C" int dhz_dense_attn_bwd(const float* q, const float* k, const float* v
                                   int ldg, float* dbias_part, int B_, int H, int nW, int d, float scale, void* stream) {
     DHZ_REQUIRE(q && k && v && dout && dq && dk && dv, "dhz_dense_attn_bwd: null pointer");
     DHZ_REQUIRE(B_ > 0 && H > 0 && (d == 16 || d == 32 || d == 64), "dhz_dense_attn_bwd: bad B_=%d H=%d d=%d", B_, H, d);
+    DHZ_REQUIRE(ld % 4 == 0 && ldo % 4 == 0 && ldg % 4 == 0, "dhz_dense_attn_bwd: leading dims must be multiples of 4");
     DHZ_REQUIRE(!bias || dbias_part, "dhz_dense_attn_bwd: bias given but dbias_part is NULL");
     DHZ_REQUIRE(!mask || (nW > 0 && B_ % nW == 0), "dhz_dense_attn_bwd: B_=%d not a multiple of nW=%d", B_, nW);
     hipStream_t s = (hipStream_t)stream;

@@ -6,7 +6,9 @@ tiles; the 8 x 8 geometry (a chunk is a whole image) at an odd batch; the widest
 with 64 chunks, which the cut splits into 16 slabs of 4 chunks: more than one chunk per work item (the accumulation loop runs on) and
 more than one work item per tile (the second pass has something to sum) - asserted from the parts query below.  Under
 reserved_grid(8 / 9) the persistent grid has at most 32 / 36 workgroups: MANY_ITEMS (40 chunks, 10 slabs x 4 tiles = 40 items) makes
-workgroups of both grids walk on to a second item, with a ragged last trip."""
+workgroups of both grids walk on to a second item, with a ragged last trip.
+NONSQUARE, (B, Cin, Kout, H, W) with H != W: the chunk walk (bxn = W / 16 chunks per row group, cpi = (H / 4) * bxn per image) and the row
+pitch of the planes tell the two apart only there; Cin != Kout as well."""
 import pytest
 import torch
 
@@ -16,6 +18,7 @@ pytestmark = pytest.mark.gpu
 
 SHAPES = [(2, 32, 32, 16), (1, 32, 64, 16), (3, 64, 32, 8), (2, 512, 32, 8), (4, 32, 32, 32)]
 MANY_ITEMS = (10, 64, 64, 16)
+NONSQUARE = [(2, 32, 64, 16, 32), (2, 32, 64, 32, 16)]
 CANARY = 4096            # floats of NaN behind the queried workspace
 
 
@@ -25,16 +28,21 @@ def blocked(t):
     return t.view(B, C // 8, 8, H, W).permute(0, 1, 3, 4, 2).contiguous()
 
 
+def dims(shape):
+    """(B, Cin, Kout, H, W) of a shape given with or without W"""
+    return shape if len(shape) == 5 else shape + (shape[3],)
+
+
 _CASES = {}
 
 
 def case(shape):
     """inputs and the float64 reference of one shape, computed once and shared (never modified)"""
     if shape not in _CASES:
-        B, Cin, Kout, H = shape
-        g = torch.Generator().manual_seed(1000 + B + Cin + Kout + H)
-        x = torch.randn(B, Cin, H, H, generator=g)
-        dy = torch.randn(B, Kout, H, H, generator=g)
+        B, Cin, Kout, H, W = dims(shape)
+        g = torch.Generator().manual_seed(1000 + B + Cin + Kout + H + 7 * (W - H))
+        x = torch.randn(B, Cin, H, W, generator=g)
+        dy = torch.randn(B, Kout, H, W, generator=g)
         dw = torch.nn.grad.conv2d_weight(x.double(), (Kout, Cin, 3, 3), dy.double(), stride=1, padding=1)
         db = dy.double().sum((0, 2, 3))
         _CASES[shape] = (blocked(x).cuda(), blocked(dy).cuda(), dw, db)
@@ -44,27 +52,27 @@ def case(shape):
 def run(shape, xb, dyb, with_db=True, ws=None):
     """one call with NaN canaries in the outputs and behind the workspace; returns (dw, db) on the device"""
     from dehaze_hip import _lib
-    B, Cin, Kout, H = shape
+    B, Cin, Kout, H, W = dims(shape)
     lib = _lib.load()
-    need = lib.dhz_conv3x3_wgrad_workspace_bytes(B, H, H, Cin, Kout)
+    need = lib.dhz_conv3x3_wgrad_workspace_bytes(B, H, W, Cin, Kout)
     assert need > 0 and need % 4 == 0
     if ws is None:
         ws = torch.full((need // 4 + CANARY,), float("nan"), device="cuda")
     dw = torch.full((Kout, Cin, 3, 3), float("nan"), device="cuda")
     db = torch.full((Kout,), float("nan"), device="cuda")
     _lib.call("dhz_conv3x3_wgrad", xb.data_ptr(), dyb.data_ptr(), dw.data_ptr(), db.data_ptr() if with_db else None, ws.data_ptr(), need,
-              B, H, H, Cin, Kout, torch.cuda.current_stream().cuda_stream)
+              B, H, W, Cin, Kout, torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     assert torch.isnan(ws[need // 4:]).all(), "the kernel wrote behind the queried workspace"
     return dw, db
 
 
-@pytest.mark.parametrize("shape", SHAPES + [MANY_ITEMS])
+@pytest.mark.parametrize("shape", SHAPES + [MANY_ITEMS] + NONSQUARE)
 def test_conv3x3_wgrad_matches_float64(shape):
-    B, Cin, Kout, H = shape
+    B, Cin, Kout, H, W = dims(shape)
     xb, dyb, dwref, dbref = case(shape)
     dw, db = run(shape, xb, dyb)
-    T = B * H * H
+    T = B * H * W
     # the bounds of the existing convolution weight-gradient check, tests/test_gpu_conv.py:47-48 (dhz_conv4s2_wgrad):
     #   assert (dwp.cpu().double() - 0.5 - dwref).abs().max() < 3e-6 * T ** 0.5 * max(1.0, dwref.abs().max().item() / T ** 0.5) + 1e-4
     #   assert (db.cpu().double() + 1.0 - br.grad).abs().max() < 3e-5 * T ** 0.5 + 1e-4
@@ -97,7 +105,7 @@ def test_conv3x3_wgrad_cut_has_slabs_and_chunks():
     assert items > 4 * 9 and items % 32 != 0 and items % 36 != 0          # more items than 4 workgroups on each of 8 / 9 CUs
 
 
-@pytest.mark.parametrize("shape", [(2, 512, 32, 8), (4, 32, 32, 32), MANY_ITEMS])
+@pytest.mark.parametrize("shape", [(2, 512, 32, 8), (4, 32, 32, 32), MANY_ITEMS] + NONSQUARE)
 def test_conv3x3_wgrad_same_bits(shape):
     """run to run, on grids sized for the whole device / 8 / 9 CUs, and with the deterministic mode on: bit-equal"""
     from dehaze_hip import ops

@@ -2,7 +2,7 @@
 mode, the library fallback and the command line (second half of the file) - and, first, the LeakyReLU(0.01) store of the
 3x3 convolution, forward (with the block's conv11 branch added in the same store) and backward-data (derivative factor 1 / 0.01 from
 the sign of the saved activation), against float64 on the CPU at the tolerances of tests/test_gpu_winograd.py (forward atol 2e-5,
-backward-data atol 5e-5, rtol 1e-4)."""
+backward-data atol 5e-5, rtol 1e-4), and the two layout copies between tokens and the blocked layout, bit for bit against torch."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -20,15 +20,38 @@ def plain(tb):
     return tb.permute(0, 1, 4, 2, 3).reshape(B, CG * 8, H, W)
 
 
-@pytest.mark.parametrize("B,C,K,H", [(2, 32, 32, 16), (1, 64, 64, 8)])
+# seeds whose float64 pre-activations stay 2e-4 away from zero (found on the CPU; the guard below holds them to 1e-5).  Beside the two
+# C == K cases: C = 2K and K = 2C (the decoder and encoder blocks of the UNet: a channel count swapped in the indexing of bias, mask
+# or addend shows only there), five 8 x 8 images (a ragged last block of four, forward and backward), and maps with H != W.
+LEAKY_SEEDS = {(2, 32, 32, 16, 16): 241, (1, 64, 64, 8, 8): 457, (1, 64, 32, 16, 16): 38, (1, 32, 64, 16, 16): 37, (5, 64, 32, 8, 8): 21,
+               (1, 32, 32, 16, 32): 10, (1, 32, 32, 32, 16): 33}
+
+
+@pytest.mark.parametrize("B,C,K,H", [(2, 32, 32, 16), (1, 64, 64, 8), (1, 64, 32, 16), (1, 32, 64, 16), (5, 64, 32, 8)])
 def test_leaky_store_forward_and_backward(B, C, K, H):
+    leaky_store_case(B, C, K, H, H)
+
+
+@pytest.mark.parametrize("H,W", [(16, 32), (32, 16)])
+def test_leaky_store_forward_and_backward_nonsquare(H, W):
+    leaky_store_case(1, 32, 32, H, W)
+
+
+def close(what, got, want, atol, rtol):
+    """torch.allclose with the worst error printed first"""
+    print(f"{what}: worst error {(got - want).abs().max().item():.3e} (atol {atol:.0e}, rtol {rtol:.0e})")
+    assert torch.allclose(got, want, atol=atol, rtol=rtol), (what, (got - want).abs().max())
+
+
+def leaky_store_case(B, C, K, H, W):
     from dehaze_hip import _lib
+    tag = f"winograd_conv3x3_act B={B} C={C} K={K} {H}x{W}"
     s = torch.cuda.current_stream().cuda_stream
-    g = torch.Generator().manual_seed(7 * C + H + 1)      # seeds whose float64 pre-activations stay 2e-4 away from zero
-    x = torch.randn(B, C, H, H, generator=g)
+    g = torch.Generator().manual_seed(LEAKY_SEEDS[(B, C, K, H, W)])
+    x = torch.randn(B, C, H, W, generator=g)
     w = torch.randn(K, C, 3, 3, generator=g) * (2.0 / (9 * C)) ** 0.5
     b = 0.1 * torch.randn(K, generator=g)
-    add = torch.randn(B, K, H, H, generator=g)
+    add = torch.randn(B, K, H, W, generator=g)
     pre = F.conv2d(x.double(), w.double(), b.double(), padding=1)
     assert pre.abs().min().item() > 1e-5, "a pre-activation of the float64 reference within 1e-5 of zero: reseed"
     act = F.leaky_relu(pre, 0.01)
@@ -36,38 +59,38 @@ def test_leaky_store_forward_and_backward(B, C, K, H):
     up = torch.empty(16 * K * C, device="cuda")
     _lib.call("dhz_winograd_prepack", wd.data_ptr(), up.data_ptr(), K, C, 0, s)
     xb, addb, bd = blocked(x).cuda(), blocked(add).cuda(), b.cuda()
-    yb = torch.full((B, K // 8, H, H, 8), float("nan"), device="cuda")
+    yb = torch.full((B, K // 8, H, W, 8), float("nan"), device="cuda")
     # forward: y = leaky(conv + bias)
-    _lib.call("dhz_winograd_conv3x3_act", xb.data_ptr(), up.data_ptr(), bd.data_ptr(), 0, None, None, yb.data_ptr(), B, H, H, C, K, s)
+    _lib.call("dhz_winograd_conv3x3_act", xb.data_ptr(), up.data_ptr(), bd.data_ptr(), 0, None, None, yb.data_ptr(), B, H, W, C, K, s)
     y = plain(yb).cpu()
-    assert torch.allclose(y, act.float(), atol=2e-5, rtol=1e-4), (y - act.float()).abs().max()
+    close(tag + " forward", y, act.float(), 2e-5, 1e-4)
     act_dev = yb.clone()                                    # the saved activation of the backward below
     # ... + addend in the same store (the block's conv11 branch)
-    _lib.call("dhz_winograd_conv3x3_act", xb.data_ptr(), up.data_ptr(), bd.data_ptr(), 0, None, addb.data_ptr(), yb.data_ptr(), B, H, H, C, K, s)
+    _lib.call("dhz_winograd_conv3x3_act", xb.data_ptr(), up.data_ptr(), bd.data_ptr(), 0, None, addb.data_ptr(), yb.data_ptr(), B, H, W, C, K, s)
     y = plain(yb).cpu()
     want = (act + add.double()).float()
-    assert torch.allclose(y, want, atol=2e-5, rtol=1e-4), (y - want).abs().max()
+    close(tag + " forward + addend", y, want, 2e-5, 1e-4)
     # backward-data of a convolution ABOVE this activation: dpre = (conv_transpose(dz, w2) + addend) * leaky'(pre), the factor taken
     # from the sign of the saved activation (K channels here are that convolution's input channels)
     w2 = torch.randn(C, K, 3, 3, generator=g) * (2.0 / (9 * K)) ** 0.5
-    dz = torch.randn(B, C, H, H, generator=g)
+    dz = torch.randn(B, C, H, W, generator=g)
     w2d = w2.cuda()
     upt = torch.empty(16 * K * C, device="cuda")
     _lib.call("dhz_winograd_prepack", w2d.data_ptr(), upt.data_ptr(), K, C, 1, s)
     dzb = blocked(dz).cuda()
-    gb = torch.full((B, K // 8, H, H, 8), float("nan"), device="cuda")
+    gb = torch.full((B, K // 8, H, W, 8), float("nan"), device="cuda")
     slope = torch.where(pre > 0, 1.0, 0.01)
     refd = F.conv_transpose2d(dz.double(), w2.double(), padding=1)
     for addend in (None, addb):
         _lib.call("dhz_winograd_conv3x3_act", dzb.data_ptr(), upt.data_ptr(), None, 1, act_dev.data_ptr(),
-                  None if addend is None else addend.data_ptr(), gb.data_ptr(), B, H, H, C, K, s)
+                  None if addend is None else addend.data_ptr(), gb.data_ptr(), B, H, W, C, K, s)
         want = ((refd + (0 if addend is None else add.double())) * slope).float()
         got = plain(gb).cpu()
-        assert torch.allclose(got, want, atol=5e-5, rtol=1e-4), (got - want).abs().max()
+        close(tag + " backward, mask" + ("" if addend is None else " + addend"), got, want, 5e-5, 1e-4)
     # the mixed-up argument sets are refused
     lib = _lib.load()
-    assert lib.dhz_winograd_conv3x3_act(xb.data_ptr(), up.data_ptr(), bd.data_ptr(), 1, act_dev.data_ptr(), None, gb.data_ptr(), B, H, H, C, K, s) == -22
-    assert lib.dhz_winograd_conv3x3_act(xb.data_ptr(), up.data_ptr(), None, 0, act_dev.data_ptr(), None, gb.data_ptr(), B, H, H, C, K, s) == -22
+    assert lib.dhz_winograd_conv3x3_act(xb.data_ptr(), up.data_ptr(), bd.data_ptr(), 1, act_dev.data_ptr(), None, gb.data_ptr(), B, H, W, C, K, s) == -22
+    assert lib.dhz_winograd_conv3x3_act(xb.data_ptr(), up.data_ptr(), None, 0, act_dev.data_ptr(), None, gb.data_ptr(), B, H, W, C, K, s) == -22
 
 
 def test_leaky_and_relu_stores_agree_on_positive_maps():
@@ -86,6 +109,106 @@ def test_leaky_and_relu_stores_agree_on_positive_maps():
     _lib.call("dhz_winograd_conv3x3_act", xb.data_ptr(), up.data_ptr(), None, 0, None, None, ya.data_ptr(), B, H, H, C, K, s)
     _lib.call("dhz_winograd_conv3x3", xb.data_ptr(), up.data_ptr(), None, 1, None, None, yr.data_ptr(), B, H, H, C, K, s)
     assert (yr > 0).all() and torch.equal(ya, yr)
+
+
+# ---- the layout copies between tokens [B][HW][C] (row stride ld) and the blocked layout [B][C/8][HW][8], with the ConvBlock's elementwise
+# factors folded in (dhz_tokens_to_blocked8 / dhz_blocked8_to_tokens).  Pure data movement plus at most one fp32 operation per element:
+# compared bit for bit with torch on the CPU.  (1, 9, 8): one channel group, 18 threads; (3, 64, 40): C no multiple of 32, a ragged last
+# workgroup; the model only ever passes ld == ld_add == C and thread counts in whole workgroups.
+LAYOUT_SHAPES = [(1, 9, 8), (3, 64, 40), (2, 256, 64)]
+LAYOUT_CASES = [(s, 0, 0) for s in LAYOUT_SHAPES] + [(s, 12, 4) for s in LAYOUT_SHAPES[1:]]       # (shape, ld - C, ld_add - C)
+CANARY = 64
+
+
+def to_blocked_ref(tok, B, HW, C):
+    return tok.reshape(B, HW, C // 8, 8).permute(0, 2, 1, 3).contiguous()
+
+
+def strided_tokens(tok, ld):
+    """[B*HW, C] values as a view into a NaN-filled [B*HW, ld] buffer on the device; returns (buffer, view)"""
+    buf = torch.full((tok.shape[0], ld), float("nan"), device="cuda")
+    buf[:, :tok.shape[1]] = tok.cuda()
+    return buf, buf[:, :tok.shape[1]]
+
+
+def call_to_blocked(tokbuf, ld, mask, B, HW, C):
+    from dehaze_hip import _lib
+    blk = torch.full((B * (C // 8) * HW * 8 + CANARY,), float("nan"), device="cuda")
+    _lib.call("dhz_tokens_to_blocked8", tokbuf.data_ptr(), ld, None if mask is None else mask.data_ptr(), blk.data_ptr(), B, HW, C,
+              torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert torch.isnan(blk[-CANARY:]).all(), "written behind the blocked map"
+    return blk[:-CANARY].view(B, C // 8, HW, 8)
+
+
+def call_to_tokens(blk, addbuf, ld_add, ld, B, HW, C):
+    from dehaze_hip import _lib
+    out = torch.full((B * HW, ld), float("nan"), device="cuda")
+    _lib.call("dhz_blocked8_to_tokens", blk.data_ptr(), None if addbuf is None else addbuf.data_ptr(), ld_add, out.data_ptr(), ld, B, HW, C,
+              torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert torch.isnan(out[:, C:]).all(), "the padding columns of the token rows were written"
+    return out[:, :C]
+
+
+@pytest.mark.parametrize("shape,pad,pad_add", LAYOUT_CASES)
+def test_layout_copies_are_exact(shape, pad, pad_add):
+    B, HW, C = shape
+    ld, ld_add = C + pad, C + pad_add
+    g = torch.Generator().manual_seed(B * 1000 + HW + C + pad)
+    tok = torch.randn(B * HW, C, generator=g)
+    add = torch.randn(B * HW, C, generator=g)
+    mask = torch.randn(B, C // 8, HW, 8, generator=g)
+    flat = mask.view(-1)
+    planted = torch.tensor([0.0, -0.0, -1e-40, 1e-40])            # zero, minus zero, a negative and a positive denormal
+    assert planted[2] < 0 < planted[3]
+    for i in range(4):                                             # one of each in the first and in the last float4
+        flat[i] = planted[i]
+        flat[flat.numel() - 4 + i] = planted[3 - i]
+    tokbuf, _ = strided_tokens(tok, ld)
+    # tokens -> blocked: a plain copy ...
+    want = to_blocked_ref(tok, B, HW, C)
+    blk = call_to_blocked(tokbuf, ld, None, B, HW, C)
+    assert not torch.isnan(blk).any() and torch.equal(blk.cpu(), want)
+    # ... and with the LeakyReLU derivative of the saved activation: one fp32 multiply by the same constant
+    blk_m = call_to_blocked(tokbuf, ld, mask.cuda(), B, HW, C)
+    want_m = want * torch.where(mask > 0, 1.0, 0.01)
+    assert torch.equal(blk_m.cpu().view(torch.int32), want_m.view(torch.int32))
+    assert torch.isnan(tokbuf[:, C:]).all()
+    # blocked -> tokens: the round trip is the identity; with the addend one fp32 addition
+    back = call_to_tokens(blk, None, 0, ld, B, HW, C)
+    assert torch.equal(back.cpu(), tok)
+    addbuf, _ = strided_tokens(add, ld_add)
+    back_a = call_to_tokens(blk, addbuf, ld_add, ld, B, HW, C)
+    assert torch.equal(back_a.cpu(), tok + add)
+    assert torch.isnan(addbuf[:, C:]).all()
+
+
+def test_layout_copies_refuse_bad_arguments():
+    from dehaze_hip import _lib
+    lib = _lib.load()
+    s = torch.cuda.current_stream().cuda_stream
+    B, HW, C = 2, 16, 16
+    tok = torch.randn(B * HW, C + 8, device="cuda")
+    blk = torch.full((B * HW * (C + 8),), float("nan"), device="cuda")
+    out = torch.full((B * HW, C + 8), float("nan"), device="cuda")
+    t, k, o = tok.data_ptr(), blk.data_ptr(), out.data_ptr()
+    assert lib.dhz_tokens_to_blocked8(t, 12, None, k, B, HW, 12, s) == -22           # C % 8 != 0
+    assert lib.dhz_tokens_to_blocked8(t, C - 4, None, k, B, HW, C, s) == -22         # ld < C
+    assert lib.dhz_tokens_to_blocked8(t, C + 2, None, k, B, HW, C, s) == -22         # ld % 4 != 0
+    assert lib.dhz_tokens_to_blocked8(t + 4, C + 4, None, k, B, HW, C, s) == -22     # pointers 4 bytes off a 16-byte boundary
+    assert lib.dhz_tokens_to_blocked8(t, C, k + 4, k, B, HW, C, s) == -22
+    assert lib.dhz_tokens_to_blocked8(t, C, None, k + 4, B, HW, C, s) == -22
+    assert lib.dhz_blocked8_to_tokens(t, None, 0, o, 12, B, HW, 12, s) == -22
+    assert lib.dhz_blocked8_to_tokens(t, None, 0, o, C - 4, B, HW, C, s) == -22
+    assert lib.dhz_blocked8_to_tokens(t, None, 0, o, C + 2, B, HW, C, s) == -22
+    assert lib.dhz_blocked8_to_tokens(t, t, C - 4, o, C, B, HW, C, s) == -22         # the addend's own row stride
+    assert lib.dhz_blocked8_to_tokens(t, t, C + 2, o, C, B, HW, C, s) == -22
+    assert lib.dhz_blocked8_to_tokens(t + 4, None, 0, o, C, B, HW, C, s) == -22
+    assert lib.dhz_blocked8_to_tokens(t, t + 4, C, o, C, B, HW, C, s) == -22
+    assert lib.dhz_blocked8_to_tokens(t, None, 0, o + 4, C, B, HW, C, s) == -22
+    torch.cuda.synchronize()
+    assert torch.isnan(blk).all() and torch.isnan(out).all()
 
 
 # ---- the module on the kernels (dehaze_hip/unet.py) at dim 32, 1 x 3 x 128 x 128: the smallest input all of whose layers are tiled

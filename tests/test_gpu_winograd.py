@@ -28,39 +28,57 @@ def _plain(xb, C):
 @pytest.mark.parametrize("B,C,K,H", [(2, 64, 64, 32), (1, 64, 128, 16), (2, 128, 128, 16), (1, 256, 512, 16), (3, 8, 32, 48),
                                      (8, 64, 64, 8), (5, 32, 64, 8), (3, 128, 32, 8), (1, 32, 32, 8)])
 def test_winograd_forward_and_dgrad(B, C, K, H):
+    winograd_case(B, C, K, H, H)
+
+
+# H != W (the header's contract is H % 16 == 0 and W % 16 == 0): the block walk bx_n = W / 16, by_n = H / 16 and the row pitch W of the
+# planes, with C != K
+@pytest.mark.parametrize("H,W", [(16, 32), (32, 16)])
+def test_winograd_forward_and_dgrad_nonsquare(H, W):
+    winograd_case(2, 32, 64, H, W)
+
+
+def close(what, got, want, atol, rtol):
+    """torch.allclose with the worst error printed first"""
+    print(f"{what}: worst error {(got - want).abs().max().item():.3e} (atol {atol:.0e}, rtol {rtol:.0e})")
+    assert torch.allclose(got, want, atol=atol, rtol=rtol), (what, (got - want).abs().max())
+
+
+def winograd_case(B, C, K, H, W):
     from dehaze_hip import _lib
+    tag = f"winograd_conv3x3 B={B} C={C} K={K} {H}x{W}"
     dev = torch.device("cuda:0")
     s = torch.cuda.current_stream().cuda_stream
-    g = torch.Generator().manual_seed(C + K + H)
-    x = torch.randn(B, C, H, H, generator=g).to(dev)
+    g = torch.Generator().manual_seed(C + K + H + 1000 * (W - H))
+    x = torch.randn(B, C, H, W, generator=g).to(dev)
     w = (torch.randn(K, C, 3, 3, generator=g) * (2.0 / (9 * C)) ** 0.5).to(dev)
     b = (0.1 * torch.randn(K, generator=g)).to(dev)
     up = torch.empty(16 * K * C, device=dev)
     _lib.call("dhz_winograd_prepack", w.data_ptr(), up.data_ptr(), K, C, 0, s)
     xb = _blocked(x)
-    yb = torch.empty(B, K // 8, H, H, 8, device=dev)
-    _lib.call("dhz_winograd_conv3x3", xb.data_ptr(), up.data_ptr(), b.data_ptr(), 1, None, None, yb.data_ptr(), B, H, H, C, K, s)
+    yb = torch.empty(B, K // 8, H, W, 8, device=dev)
+    _lib.call("dhz_winograd_conv3x3", xb.data_ptr(), up.data_ptr(), b.data_ptr(), 1, None, None, yb.data_ptr(), B, H, W, C, K, s)
     y = _plain(yb, K)
     ref = F.relu(F.conv2d(x.double(), w.double(), b.double(), padding=1)).float()
-    assert torch.allclose(y, ref, atol=2e-5, rtol=1e-4), (y - ref).abs().max()
+    close(tag + " forward", y, ref, 2e-5, 1e-4)
     assert torch.equal(_plain(xb, C), x)
     # backward-data with the fused store: dx = (x > 0) ? conv_transpose(dy, w) + addend : 0  (x plays the saved post-ReLU
     # map below the layer, addend a tap gradient) == winograd with the transposed_rot filters
-    dy = torch.randn(B, K, H, H, generator=g).to(dev)
-    add = torch.randn(B, C, H, H, generator=g).to(dev)
+    dy = torch.randn(B, K, H, W, generator=g).to(dev)
+    add = torch.randn(B, C, H, W, generator=g).to(dev)
     if C % 32 == 0:
         upt = torch.empty(16 * K * C, device=dev)
         _lib.call("dhz_winograd_prepack", w.data_ptr(), upt.data_ptr(), C, K, 1, s)      # Kout = C (of fwd), Cin = K
-        dxb = torch.empty(B, C // 8, H, H, 8, device=dev)
+        dxb = torch.empty(B, C // 8, H, W, 8, device=dev)
         refdx = F.conv_transpose2d(dy.double(), w.double(), padding=1).float()
         dyb, addb = _blocked(dy), _blocked(add)
         _lib.call("dhz_winograd_conv3x3", dyb.data_ptr(), upt.data_ptr(), None, 0, xb.data_ptr(), addb.data_ptr(),
-                  dxb.data_ptr(), B, H, H, K, C, s)
+                  dxb.data_ptr(), B, H, W, K, C, s)
         want = (refdx + add) * (x > 0)
-        assert torch.allclose(_plain(dxb, C), want, atol=5e-5, rtol=1e-4), (_plain(dxb, C) - want).abs().max()
+        close(tag + " backward-data, mask + addend", _plain(dxb, C), want, 5e-5, 1e-4)
         _lib.call("dhz_winograd_conv3x3", dyb.data_ptr(), upt.data_ptr(), None, 0, None, addb.data_ptr(),
-                  dxb.data_ptr(), B, H, H, K, C, s)
-        assert torch.allclose(_plain(dxb, C), refdx + add, atol=5e-5, rtol=1e-4)
+                  dxb.data_ptr(), B, H, W, K, C, s)
+        close(tag + " backward-data + addend", _plain(dxb, C), refdx + add, 5e-5, 1e-4)
 
 
 @pytest.mark.parametrize("B,C,H", [(2, 64, 32), (1, 16, 8)])
@@ -84,50 +102,60 @@ def test_maxpool_blocked(B, C, H):
                                      (1, 256, 512, 16), (3, 64, 32, 16), (1, 16, 32, 48), (5, 32, 64, 16),
                                      (2, 512, 512, 16), (1, 384, 64, 16)])      # > 256 input channels: two accumulation chains (two launches)
 def test_winograd43_forward_and_dgrad(B, C, K, H):
+    winograd43_case(B, C, K, H, H)
+
+
+@pytest.mark.parametrize("H,W", [(16, 32), (32, 16)])
+def test_winograd43_forward_and_dgrad_nonsquare(H, W):
+    winograd43_case(2, 32, 64, H, W)
+
+
+def winograd43_case(B, C, K, H, W):
     from dehaze_hip import _lib
+    tag = f"winograd43_conv3x3 B={B} C={C} K={K} {H}x{W}"
     dev = torch.device("cuda:0")
     s = torch.cuda.current_stream().cuda_stream
-    g = torch.Generator().manual_seed(C + K + H)
-    x = torch.randn(B, C, H, H, generator=g).to(dev)
+    g = torch.Generator().manual_seed(C + K + H + 1000 * (W - H))
+    x = torch.randn(B, C, H, W, generator=g).to(dev)
     w = (torch.randn(K, C, 3, 3, generator=g) * (2.0 / (9 * C)) ** 0.5).to(dev)
     b = (0.1 * torch.randn(K, generator=g)).to(dev)
     up = torch.empty(36 * K * C, device=dev)
     _lib.call("dhz_winograd43_prepack", w.data_ptr(), up.data_ptr(), K, C, 0, s)
     xb = _blocked(x)
-    yb = torch.empty(B, K // 8, H, H, 8, device=dev)
-    _lib.call("dhz_winograd43_conv3x3", xb.data_ptr(), up.data_ptr(), b.data_ptr(), 1, None, None, yb.data_ptr(), B, H, H, C, K, s)
+    yb = torch.empty(B, K // 8, H, W, 8, device=dev)
+    _lib.call("dhz_winograd43_conv3x3", xb.data_ptr(), up.data_ptr(), b.data_ptr(), 1, None, None, yb.data_ptr(), B, H, W, C, K, s)
     y = _plain(yb, K)
     ref = F.relu(F.conv2d(x.double(), w.double(), b.double(), padding=1)).float()
-    assert torch.allclose(y, ref, atol=2e-5, rtol=1e-4), (y - ref).abs().max()
+    close(tag + " forward", y, ref, 2e-5, 1e-4)
     # without bias / ReLU
-    _lib.call("dhz_winograd43_conv3x3", xb.data_ptr(), up.data_ptr(), None, 0, None, None, yb.data_ptr(), B, H, H, C, K, s)
+    _lib.call("dhz_winograd43_conv3x3", xb.data_ptr(), up.data_ptr(), None, 0, None, None, yb.data_ptr(), B, H, W, C, K, s)
     ref0 = F.conv2d(x.double(), w.double(), padding=1).float()
-    assert torch.allclose(_plain(yb, K), ref0, atol=2e-5, rtol=1e-4)
+    close(tag + " forward, no bias / ReLU", _plain(yb, K), ref0, 2e-5, 1e-4)
     if C % 32 == 0:
-        dy = torch.randn(B, K, H, H, generator=g).to(dev)
-        add = torch.randn(B, C, H, H, generator=g).to(dev)
+        dy = torch.randn(B, K, H, W, generator=g).to(dev)
+        add = torch.randn(B, C, H, W, generator=g).to(dev)
         upt = torch.empty(36 * K * C, device=dev)
         _lib.call("dhz_winograd43_prepack", w.data_ptr(), upt.data_ptr(), C, K, 1, s)      # Kout = C (of fwd), Cin = K
-        dxb = torch.empty(B, C // 8, H, H, 8, device=dev)
+        dxb = torch.empty(B, C // 8, H, W, 8, device=dev)
         refdx = F.conv_transpose2d(dy.double(), w.double(), padding=1).float()
         dyb, addb = _blocked(dy), _blocked(add)
         _lib.call("dhz_winograd43_conv3x3", dyb.data_ptr(), upt.data_ptr(), None, 0, xb.data_ptr(), addb.data_ptr(),
-                  dxb.data_ptr(), B, H, H, K, C, s)
+                  dxb.data_ptr(), B, H, W, K, C, s)
         want = (refdx + add) * (x > 0)
-        assert torch.allclose(_plain(dxb, C), want, atol=5e-5, rtol=1e-4), (_plain(dxb, C) - want).abs().max()
+        close(tag + " backward-data, mask + addend", _plain(dxb, C), want, 5e-5, 1e-4)
         _lib.call("dhz_winograd43_conv3x3", dyb.data_ptr(), upt.data_ptr(), None, 0, None, addb.data_ptr(),
-                  dxb.data_ptr(), B, H, H, K, C, s)
-        assert torch.allclose(_plain(dxb, C), refdx + add, atol=5e-5, rtol=1e-4)
+                  dxb.data_ptr(), B, H, W, K, C, s)
+        close(tag + " backward-data + addend", _plain(dxb, C), refdx + add, 5e-5, 1e-4)
     # convolution + bias + ReLU + 2 x 2 max pooling in one launch (the un-pooled map is never written; C > 256: chains through the scratch map)
-    yp = torch.empty(B, K // 8, H // 2, H // 2, 8, device=dev)
-    scratch = torch.empty(B, K // 8, H, H, 8, device=dev) if C > 256 else None
+    yp = torch.empty(B, K // 8, H // 2, W // 2, 8, device=dev)
+    scratch = torch.empty(B, K // 8, H, W, 8, device=dev) if C > 256 else None
     _lib.call("dhz_winograd43_conv3x3_pool", xb.data_ptr(), up.data_ptr(), b.data_ptr(), yp.data_ptr(),
-              scratch.data_ptr() if scratch is not None else None, B, H, H, C, K, s)
-    assert torch.allclose(_plain(yp, K), F.max_pool2d(ref, 2, 2), atol=2e-5, rtol=1e-4), (_plain(yp, K) - F.max_pool2d(ref, 2, 2)).abs().max()
+              scratch.data_ptr() if scratch is not None else None, B, H, W, C, K, s)
+    close(tag + " forward + pooling", _plain(yp, K), F.max_pool2d(ref, 2, 2), 2e-5, 1e-4)
     lib = _lib.load()
     assert lib.dhz_winograd43_conv3x3(xb.data_ptr(), up.data_ptr(), None, 0, None, None, yb.data_ptr(), B, 8, 8, C, K, s) == -22
     if C > 256:
-        assert lib.dhz_winograd43_conv3x3_pool(xb.data_ptr(), up.data_ptr(), b.data_ptr(), yp.data_ptr(), None, B, H, H, C, K, s) == -22
+        assert lib.dhz_winograd43_conv3x3_pool(xb.data_ptr(), up.data_ptr(), b.data_ptr(), yp.data_ptr(), None, B, H, W, C, K, s) == -22
 
 
 @pytest.mark.parametrize("ablation", [False, True])
@@ -364,3 +392,40 @@ def test_vgg_engine_pooling_in_the_convolution_store_is_bit_identical():
     assert len(a) == len(b) == 5
     for u, v in zip(a, b):
         assert torch.equal(u, v)
+
+
+@pytest.mark.parametrize("with_n", [True, False])
+def test_l1_pair_fp32(with_n):
+    """dhz_l1_pair_fwd / _bwd on fp32 maps: the twin of test_l1_pair_bf16 (tests/test_gpu_vgg_bf16.py) - same count, planted exact ties
+    (sign 0), with and without the negative.  The sums against float64 at that test's 1e-5 relative bound.  The backward against
+    g0 / cnt * sign(a - p) + g1 / cnt * sign(a - n) formed in fp32: the kernel multiplies g by a host-computed 1.0f / cnt instead of
+    dividing (csrc/elementwise.hip, l1_pair_bwd_kernel: cp = g[0] * inv_n), one more rounding than the quotient, so the comparison is
+    allclose at rtol 1e-6 with no absolute term - not torch.equal.  The signs themselves are exact: where a == p the term is 0."""
+    from dehaze_hip import _lib
+    dev = torch.device("cuda:0")
+    s = torch.cuda.current_stream().cuda_stream
+    g = torch.Generator().manual_seed(3)
+    cnt = 8 * 12345
+    a, p, n = ((torch.randn(cnt, generator=g) * 2).to(dev) for _ in range(3))
+    p[:100] = a[:100]                                   # exact zeros of the difference: sign 0
+    n[50:150] = a[50:150]                               # ... of either difference, and of both at once (50..99)
+    sums = torch.zeros(2, device=dev)
+    _lib.call("dhz_l1_pair_fwd", a.data_ptr(), p.data_ptr(), n.data_ptr() if with_n else None, sums.data_ptr(), cnt, s)
+    rp = (a.double() - p.double()).abs().sum().item()
+    rn = (a.double() - n.double()).abs().sum().item()
+    print(f"l1_pair fp32 with_n={with_n}: relative error of the sums {abs(sums[0].item() - rp) / rp:.3e}"
+          + (f", {abs(sums[1].item() - rn) / rn:.3e}" if with_n else ""))
+    assert abs(sums[0].item() - rp) < 1e-5 * rp
+    assert abs(sums[1].item() - rn) < 1e-5 * rn if with_n else sums[1].item() == 0.0
+    gsc = torch.tensor([0.7, -1.3], device=dev)
+    da = torch.full((cnt + 64,), float("nan"), device=dev)
+    _lib.call("dhz_l1_pair_bwd", a.data_ptr(), p.data_ptr(), n.data_ptr() if with_n else None, gsc.data_ptr(), da.data_ptr(), cnt, s)
+    assert torch.isnan(da[cnt:]).all() and not torch.isnan(da[:cnt]).any()
+    da = da[:cnt].cpu()
+    ac, pc, nc, gc = a.cpu(), p.cpu(), n.cpu(), gsc.cpu()
+    ref = gc[0] / cnt * torch.sign(ac - pc)
+    if with_n:
+        ref = ref + gc[1] / cnt * torch.sign(ac - nc)
+    print(f"l1_pair fp32 with_n={with_n}: worst relative error of da {((da - ref).abs() / ref.abs().clamp_min(1e-30)).max().item():.3e}")
+    assert torch.allclose(da, ref, rtol=1e-6, atol=0.0)
+    assert (da[50:100] == 0).all() if with_n else (da[:100] == 0).all()

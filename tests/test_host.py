@@ -438,3 +438,55 @@ def test_token_linear_launches_match_the_table_of_the_parent_commit():
     assert "T524288 K64 N64 32x128x128 f32 split6 res1 notp0 shadow1 | dgrad | dgrad_split(64,64,524288,64,64,6)" in want
     diff = [(w, g) for w, g in zip(want, got) if w != g]
     assert len(want) == len(got) and not diff, f"{len(diff)} of {len(want)} lines differ (table, now), first: {diff[:5]}"
+
+
+# Exported entries that no tests/test_gpu*.py names: entry -> (the wrapper that calls it, as module.attribute of the package; the test that
+# reaches it through that wrapper, with inputs and a reference of its own - not a whole-model test).  Three are host-side queries.
+_REACHED_THROUGH_A_WRAPPER = {
+    "dhz_abi_version": ("_lib.load", "test_host.py::test_library_exports_every_declared_symbol"),
+    "dhz_build_id": ("_lib.load", "test_host.py::test_pmc_traffic_is_tied_to_the_loaded_library"),
+    "dhz_set_det_workspace": ("ops._det_workspace", "test_deterministic_host.py::test_flag_round_trip_and_workspace_argument_checks"),
+    "dhz_charbonnier_bwd": ("ops.charbonnier", "test_gpu_kernels.py::test_charbonnier"),
+    "dhz_fused_attn_bwd_prepack": ("fused._attn_fused_fwd", "test_gpu_persistent.py::test_fused_attention_c32_multi_trip"),
+    "dhz_fused_window_attn_bwd": ("fused._attn_bwd", "test_gpu_persistent.py::test_fused_attention_c32_multi_trip"),
+    "dhz_input_proj_fwd_dt": ("ops.input_proj", "test_gpu_conv.py::test_input_proj_vs_torch"),
+    "dhz_input_proj_bwd_dt": ("ops.input_proj", "test_gpu_conv.py::test_input_proj_vs_torch"),
+    "dhz_leff_dwconv_fwd_dt": ("ops.leff_dwconv", "test_gpu_kernels.py::test_leff_dwconv"),
+    "dhz_leff_dwconv_bwd_dt": ("ops.leff_dwconv", "test_gpu_kernels.py::test_leff_dwconv"),
+    "dhz_leff_prepack6": ("fused.leff_branch", "test_gpu_leff.py::test_leff_fused_vs_fp64_and_chain"),
+    "dhz_linear_dgrad_split_scaled": ("ops.gemm_dgrad", "test_gpu_epilogue.py::test_scaled_dgrad_vs_fp64"),
+    "dhz_ln_partition_bwd_dt": ("ops.ln_partition", "test_gpu_kernels.py::test_ln_partition"),
+    "dhz_maxpool2x2_blocked_fwd": ("vgg.pool_fwd", "test_gpu_winograd.py::test_maxpool_blocked"),
+    "dhz_maxpool2x2_blocked_bwd": ("vgg.pool_bwd_relu", "test_gpu_winograd.py::test_maxpool_blocked"),
+    "dhz_reverse_residual_fwd_dt": ("ops.reverse_residual", "test_gpu_kernels.py::test_reverse_residual"),
+    "dhz_reverse_residual_bwd_dt": ("ops.reverse_residual", "test_gpu_kernels.py::test_reverse_residual"),
+    "dhz_thin_conv3x3_fwd_dt": ("ops.thin_conv3x3", "test_gpu_kernels.py::test_thin_conv3x3_vs_torch"),
+    "dhz_thin_conv3x3_dgrad_dt": ("ops.thin_conv3x3", "test_gpu_kernels.py::test_thin_conv3x3_vs_torch"),
+    "dhz_thin_conv3x3_wgrad_dt": ("ops.thin_conv3x3", "test_gpu_kernels.py::test_thin_conv3x3_vs_torch"),
+}
+
+
+def test_every_exported_entry_is_named_by_a_gpu_test_or_mapped_to_one():
+    """The gap this guards: an entry of include/dehaze_hip.h that only whole-model tests launch (one shape, 5e-3 norm bounds).  Every
+    exported dhz_* name appears in some tests/test_gpu*.py - called through the raw ABI there, or spied on - or in the table above,
+    whose rows are checked as far as text goes: the package module defines the wrapper and names the entry, the test file defines the
+    test and names the wrapper, and no row is stale (an entry that a GPU test has come to name leaves the table)."""
+    import glob
+    hdr = open(os.path.join(ROOT, "include", "dehaze_hip.h")).read()
+    declared = set(re.findall(r"\b(dhz_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)))
+    assert len(declared) > 100, len(declared)
+    gpu = "\n".join(open(f).read() for f in sorted(glob.glob(os.path.join(ROOT, "tests", "test_gpu*.py"))))
+    named = {n for n in declared if re.search(r"\b%s\b" % n, gpu)}
+    table = _REACHED_THROUGH_A_WRAPPER
+    assert not declared - named - set(table), f"no GPU test names these entries and no row maps them: {sorted(declared - named - set(table))}"
+    assert not set(table) - declared, sorted(set(table) - declared)
+    assert not set(table) & named, f"named by a GPU test by now - drop the rows: {sorted(set(table) & named)}"
+    for entry, (wrapper, test) in table.items():
+        mod, attr = wrapper.split(".")
+        src = open(os.path.join(PKG, "dehaze_hip", mod + ".py")).read()
+        assert re.search(r"^(def|class) %s\b" % attr, src, re.M), f"{entry}: dehaze_hip/{mod}.py defines no {attr}"
+        assert entry in src or mod == "_lib", f"{entry}: dehaze_hip/{mod}.py never names it"
+        fname, tname = test.split("::")
+        tsrc = open(os.path.join(ROOT, "tests", fname)).read()
+        assert re.search(r"^def %s\(" % tname, tsrc, re.M), f"{entry}: {test} does not exist"
+        assert attr in tsrc or entry in tsrc, f"{entry}: {fname} names neither {wrapper} nor the entry"
