@@ -356,6 +356,15 @@ int dhz_leff_dwconv_bwd_dt(const void* dz, const void* u, const void* t, const f
  *      dz_scale NULL = 1) */
 int dhz_leff_dwconv_bwd_scaled_dt(const void* dz, const void* u, const void* t, const float* w, void* du, float* dw, float* db,
                                   const float* dz_scale, int B, int Hres, int Wres, int Ch, int dtype, void* stream);
+/*      the same with dz FORMED IN THE KERNEL from linear2's output gradient (fp32 storage; csrc/leff_dwconv_dz.hip): replaces
+ *          dz = dy @ W2                                   (at::mm; [T, C] x [C, Ch], written and read once)
+ *          dhz_leff_dwconv_bwd_scaled_dt(dz, ...)
+ *      dy: [B Hres Wres, C] in token order with row stride ldy (ldy % 4 == 0, ldy >= C); w2t_hi / mid / lo: the three bf16 truncation
+ *      planes of W2^T ([Ch][C] row-major, what dhz_split3_planes writes for W2.t().contiguous() and dhz_split3_planes_t maintains); the
+ *      product is the six-term one on the bf16 matrix pipe, fp32 accumulation.  C in {32, 64, 128}, Ch % 32 == 0.  dw / db accumulate. */
+int dhz_leff_dwconv_bwd_dy(const float* dy, int ldy, const void* w2t_hi, const void* w2t_mid, const void* w2t_lo, const float* u,
+                           const float* tpre, const float* wd, float* du, float* dw, float* db, const float* dz_scale, int B, int Hres,
+                           int Wres, int C, int Ch, void* stream);
 int dhz_ps_attn_fwd_dt(const void* q, const void* k, const void* v, int ld, const uint8_t* idx, const float* bias,
                        const float* mask, void* out, int ldo, uint8_t* rank, int B_, int H, int nW, int d, int dtype,
                        void* stream);

@@ -53,6 +53,13 @@ LEFF_FUSED_P6 = __import__("os").environ.get("DHZ_LEFF_P6", "1") != "0"
 # 128 x 128: 367.6 / 264.0 -> 393.4 / 308.8, SLOWER: at C = 32 the matrix share of this kernel is a fifth of its time and the piece images
 # cost more vector / LDS work than the shorter MFMAs return - the fp32-pipe instance stays there
 LEFF_FUSED_P6_C = (64,)
+# LeFF backward: the depthwise backward forms dz = dy . W2 itself (csrc/leff_dwconv_dz.hip, six-term on the bf16 matrix pipe from the planes
+# of W2^T) instead of reading it from a backward-data GEMM: one write and one read of [T, 4C] less per block.  DHZ_LEFF_BWD_DZ=0: the chain.
+# A width is listed when it wins on every map size it occurs at by more than the spread between rounds (tools/bench_leff_bwd_dz.py, bs 32,
+# us, chain -> dz in the kernel: C = 32 at 128 x 128 310 -> 207; C = 64 at 64 x 64 173 -> 133, at 128 x 128 666 -> 501; C = 128 at
+# 32 x 32 93 -> 86, at 64 x 64 375 -> 342; profiles/r07_leff_bwd_dz.txt).  C >= 256 has no instance.
+LEFF_BWD_DZ = __import__("os").environ.get("DHZ_LEFF_BWD_DZ", "1") != "0"
+LEFF_BWD_DZ_C = (32, 64, 128)
 
 
 def _wgrad(dy, off, x, w, b, row_scale=None):
@@ -499,18 +506,31 @@ def _leff_bwd(rec, dout, dx_window=None, dx2=None):
         _lib.call("dhz_reverse_residual_bwd_dt", _p(dout), _p(dscale), _p(dy), B, L, 1, C, 0, 0, ops._dt(dout), _stream())
     else:
         dy = dout.view(T, C)
-    dz = ops.gemm_dgrad(dy, w2_)
+    # dz = dy . W2 inside the depthwise backward where that is measured faster (fp32 storage, six-term arithmetic, registered W^T planes)
+    planes = None
+    if LEFF_BWD_DZ and C in LEFF_BWD_DZ_C and u.dtype == torch.float32 and dy.dtype == torch.float32 and ops.SPLIT_BF16 == 6:
+        planes = ops.split_planes_t(w2_ if w2_.is_contiguous() else w2_.contiguous())
+        if planes is not None and any(_p(pl) % 16 for pl in planes):
+            planes = None
+    dz = ops.gemm_dgrad(dy, w2_) if planes is None else None
     g_w2, g_b2 = _wgrad(dy, 0, z, w2, b2, (dscale, L) if fold else None)
     du = torch.empty_like(u)
+
+    def dwconv_bwd(pdw, pdb):
+        if planes is None:
+            _lib.call("dhz_leff_dwconv_bwd_scaled_dt", _p(dz), _p(u), _p(tg), _p(wdc), _p(du), pdw, pdb, _p(zscale), B, Hres, Wres, Ch,
+                      ops._dt(u), _stream())
+        else:
+            _lib.call("dhz_leff_dwconv_bwd_dy", _p(dy), dy.stride(0), _p(planes[0]), _p(planes[1]), _p(planes[2]), _p(u), _p(tg), _p(wdc),
+                      _p(du), pdw, pdb, _p(zscale), B, Hres, Wres, C, Ch, _stream())
+
     if gwd is not None and gbd is not None:          # depthwise weight / bias gradients straight into .grad
-        _lib.call("dhz_leff_dwconv_bwd_scaled_dt", _p(dz), _p(u), _p(tg), _p(wdc), _p(du), _p(gwd), _p(gbd), _p(zscale), B, Hres,
-                  Wres, Ch, ops._dt(u), _stream())
+        dwconv_bwd(_p(gwd), _p(gbd))
         _ready(wd, bd)
         g_wd = g_bd = None
     else:
         dwb = torch.zeros((Ch * 10,), **f32)
-        _lib.call("dhz_leff_dwconv_bwd_scaled_dt", _p(dz), _p(u), _p(tg), _p(wdc), _p(du), dwb.data_ptr(),
-                  dwb.data_ptr() + 4 * Ch * 9, _p(zscale), B, Hres, Wres, Ch, ops._dt(u), _stream())
+        dwconv_bwd(dwb.data_ptr(), dwb.data_ptr() + 4 * Ch * 9)
         g_wd, g_bd = dwb[:Ch * 9].view(Ch, 1, 3, 3), dwb[Ch * 9:]
     dxn = ops.gemm_dgrad(du, w1_)
     g_w1, g_b1 = _wgrad(du, 0, xn, w1, b1)
