@@ -131,6 +131,19 @@ int dhz_fused_window_attn_fwd6(const float* x, const float* gamma, const float* 
                                const float* wo_p, const float* bo, const uint8_t* idx, const float* bias, const float* mask,
                                const float* drop_scale, float* out, float* xn_save, float* qkv_save, float* ctx_save, float* stats_save,
                                uint8_t* rank_save, int B, int Hres, int Wres, int C, int shift, void* stream);
+/* The inference form (no save buffers) of either kernel with the PADDING MASK of any-size evaluation as one 64-bit word per window:
+ *     pad[B nW] from dhz_pad_window_bits, bit j of word b = token j of window b (image-major, then window row, window column of the ROLLED
+ *     map, M1:791-800) is padding.  Replaces, per block,
+ *          m  = F.interpolate(mask, (H, W)); am = window_partition(m)              ([B nW, 64])
+ *          am = (am[:, :, None] * am[:, None, :]).masked_fill(!= 0, -100)          ([B nW, 64, 64] fp32: 16 KiB per window)
+ *          attn_mask = am + shift_mask                                             (batch 1 only: [B nW, ..] + [nW, ..])
+ *     and the unfused kernel chain that a [B nW, 64, 64] mask forced.  The kernel adds (shift-mask term + padding term) where it adds the
+ *     shift mask; a word of 0 skips the term.  six_term != 0: wqkv_p holds dhz_fused_attn_prepack6's planes (dhz_fused_window_attn_fwd6),
+ *     else dhz_fused_attn_prepack's fragments.  mask stays the [nW, 64, 64] shift mask (NULL iff shift == 0); pad is valid at any shift. */
+int dhz_fused_window_attn_fwd_pad(int six_term, const float* x, const float* gamma, const float* beta, const void* wqkv_p, const float* bqkv,
+                                  const float* wo_p, const float* bo, const uint8_t* idx, const float* bias, const float* mask,
+                                  const uint64_t* pad, const float* drop_scale, float* out, int B, int Hres, int Wres, int C, int shift,
+                                  void* stream);
 int dhz_fused_attn_prepack6(const float* wq, const float* wk, const float* wv, const float* wo, void* wqkv6_p, int C, void* stream);
 /* ... for n <= 16 blocks in ONE launch (host arrays of device pointers). */
 int dhz_fused_attn_prepack6_multi(const float* const* wq, const float* const* wk, const float* const* wv, const float* const* wo,
@@ -371,6 +384,18 @@ int dhz_ps_attn_fwd_dt(const void* q, const void* k, const void* v, int ld, cons
 int dhz_ps_attn_bwd_dt(const void* q, const void* k, const void* v, int ld, const float* bias, const float* mask,
                        const uint8_t* rank, const void* dout, int ldo, void* dq, void* dk, void* dv, int ldg,
                        float* dbias_part, int B_, int H, int nW, int d, int dtype, void* stream);
+/*      ... with the padding mask of any-size evaluation (M1:791-800) as one uint64 per window instead of a [B_, 64, 64] tensor: replaces
+ *          am = window_partition(F.interpolate(mask, (H, W))); am = am[:, :, None] * am[:, None, :]
+ *          attn_mask = am.masked_fill(am != 0, -100) (+ shift_mask)                 -> ProbAttention.forward(..., attn_mask)
+ *      pad[B_]: bit j of word b = token j of GLOBAL window b is padding (dhz_pad_window_bits); mask stays the [nW, 64, 64] shift mask
+ *      (window b % nW) or NULL.  B_ must be a whole number of images (B_ % nW == 0, nW > 0 also without a shift mask).  The kernels add
+ *      (shift term + padding term), both exact, where they add the mask: bit-identical to the entries above given the summed tensor.  The
+ *      backward needs the words only to recompute P. */
+int dhz_ps_attn_fwd_dt_pad(const void* q, const void* k, const void* v, int ld, const uint8_t* idx, const float* bias, const float* mask,
+                           const uint64_t* pad, void* out, int ldo, uint8_t* rank, int B_, int H, int nW, int d, int dtype, void* stream);
+int dhz_ps_attn_bwd_dt_pad(const void* q, const void* k, const void* v, int ld, const float* bias, const float* mask, const uint64_t* pad,
+                           const uint8_t* rank, const void* dout, int ldo, void* dq, void* dk, void* dv, int ldg, float* dbias_part, int B_,
+                           int H, int nW, int d, int dtype, void* stream);
 
 /* K2/K4/K5 (backward)  weight + bias gradient of every token-major nn.Linear on the path
  *     (query/key/value/out projections ATT:420-422,454-458; LeFF linear1/linear2 M1:487-492):
@@ -586,6 +611,19 @@ int dhz_ps_attn_bwd_parts_w(int B_, int H, int d, int win);
 int dhz_ps_attn_bwd_w(const void* q, const void* k, const void* v, int ld, const float* bias, const float* mask, const uint8_t* rank,
                       const void* dout, int ldo, void* dq, void* dk, void* dv, int ldg, float* dbias_part, int B_, int H, int nW, int d,
                       int win, int dtype, void* stream);
+/* K3 with padding words (see dhz_ps_attn_fwd_dt_pad, which win = 8 runs): pad[B_] uint64, 4 x 4 windows use the low 16 bits. */
+int dhz_ps_attn_fwd_w_pad(const void* q, const void* k, const void* v, int ld, const uint8_t* idx, const float* bias, const float* mask,
+                          const uint64_t* pad, void* out, int ldo, uint8_t* rank, int B_, int H, int nW, int d, int win, int dtype,
+                          void* stream);
+int dhz_ps_attn_bwd_w_pad(const void* q, const void* k, const void* v, int ld, const float* bias, const float* mask, const uint64_t* pad,
+                          const uint8_t* rank, const void* dout, int ldo, void* dq, void* dk, void* dv, int ldg, float* dbias_part, int B_,
+                          int H, int nW, int d, int win, int dtype, void* stream);
+/* The padding words of one block resolution: replaces
+ *          m = F.interpolate(mask, (H, W)); am = window_partition(m.permute(0, 2, 3, 1), win).view(-1, win win)    (M1:791-793)
+ *     and keeps of it what the attention reads: bits[b] bit i = (am[b, i] != 0), b over B (H / win) (W / win) windows in window_partition's
+ *     order (no cyclic shift, as the reference).  mask [B, 1, Himg, Wimg] fp32; Himg % H == 0 and Wimg % W == 0 (nearest resampling then
+ *     reads mask[y Himg / H, x Wimg / W] exactly), anything else returns DHZ_EINVAL; win = 4 or 8. */
+int dhz_pad_window_bits(const float* mask, uint64_t* bits, int B, int Himg, int Wimg, int H, int W, int win, void* stream);
 int dhz_dense_attn_fwd_w(const float* q, const float* k, const float* v, int ld, const float* bias, const float* mask, float* out,
                          int ldo, int B_, int H, int nW, int d, float scale, int win, void* stream);
 int dhz_dense_attn_bwd_w(const float* q, const float* k, const float* v, int ld, const float* bias, const float* mask, const float* dout,

@@ -228,3 +228,11 @@ __device__ __forceinline__ int window_slot(int hh, int ww, int Hres, int Wres, i
     int ws = ww - shift; if (ws < 0) ws += Wres;
     return ((hs >> LW) * (Wres >> LW) + (ws >> LW)) * (1 << (2 * LW)) + (hs & M) * (1 << LW) + (ws & M);
 }
+
+// Trailing kernel argument of the attention kernels that exist with and without the padding words of any-size evaluation (one uint64 per
+// window, bit j: token j is padding; dhz_pad_window_bits).  Without them it is a class of size ZERO (an empty class still takes a byte, which
+// can move the hidden arguments behind it): such an instance has the kernarg segment and the instructions of the kernel before padding
+// words existed.
+template <bool PAD> struct PadArg { char none[0]; };
+template <> struct PadArg<true> { const uint64_t* words; };
+static_assert(sizeof(PadArg<false>) == 0, "PadArg<false> must add nothing to a kernel's kernarg segment (zero-length array member)");

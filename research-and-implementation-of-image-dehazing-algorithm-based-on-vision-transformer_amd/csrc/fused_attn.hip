@@ -111,14 +111,18 @@ struct FusedSmem {
 // matrix pipe with its weight planes brought ONCE per workgroup by LDS-DMA into the Q / K / V / S tiles (dead at that point: 36 KiB per 64
 // channels), shared by the four waves - not 4 x through L1 per wave (the round-4 attempt), three workgroups per CU kept (not the
 // resident-planes form of round 5).
-template <int C, int SAVE, int NW = 1, bool P6 = false>
+// PAD (inference instances only): pad.words[win] is the padding word of window `win` (bit j: token j is padding, csrc/ps_attn16.hip
+// dhz_pad_window_bits); query AND key padding adds -100 to the shift-mask term of step 2d.  Without PAD the last argument has size zero
+// (PadArg, common.h): the kernarg segment and the instructions of the kernel before padding words existed.
+template <int C, int SAVE, int NW = 1, bool P6 = false, bool PAD = false>
 __global__ __launch_bounds__(256 * NW, NW == 2 ? 1 : (C == 64 ? 3 : (C == 128 ? 1 : 2))) void fused_window_attn_fwd_kernel(
     const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
     const float4* __restrict__ wqkv_p, const float* __restrict__ bqkv, const float4* __restrict__ wo_p,
     const float* __restrict__ bo, const uint8_t* __restrict__ idx, const float* __restrict__ bias,
     const float* __restrict__ mask, const float* __restrict__ dscale, float* __restrict__ out,
     float* __restrict__ xn_save, float* __restrict__ qkv_save, float* __restrict__ ctx_save,
-    float* __restrict__ stats_save, uint8_t* __restrict__ rank_save, int Hres, int Wres, int shift, int nwin) {
+    float* __restrict__ stats_save, uint8_t* __restrict__ rank_save, int Hres, int Wres, int shift, int nwin, PadArg<PAD> pad) {
+    static_assert(!PAD || SAVE == 0, "padding words: inference instances only");
     constexpr int abl = DHZ_FUSED_ABL;
     constexpr int H = C / 32;
     constexpr int CPT = C / 4;            // floats per thread in the token-row phases (4 threads per token)
@@ -385,6 +389,10 @@ __global__ __launch_bounds__(256 * NW, NW == 2 ? 1 : (C == 64 ? 3 : (C == 128 ? 
             //      count of the lane mask, handed to lane q with v_writelane: 2 VALU + 3 SALU per query instead of ~4.5 VALU
             //      for the per-lane count with the index tie rule.  The window has two EQUAL measures iff the counts do not add
             //      up to 64*63/2 ordered pairs - only then (practically never) the exact tie rule is evaluated per lane.
+            // (PAD) the window's padding word: uniform over the workgroup (half); loaded here, once per head, so that the scalar pair lives from
+            // the ranking to the softmax only - held across the window loop it costs registers in the projections
+            uint64_t pw = 0;
+            if constexpr (PAD) pw = pad.words[win];
             int myrank = lane;
             if (!(abl & 8)) {
                 const float mq = sm.m[lane];
@@ -437,6 +445,14 @@ __global__ __launch_bounds__(256 * NW, NW == 2 ? 1 : (C == 64 ? 3 : (C == 128 ? 
                     if (mask && ((wdx / nWw) == (Hres >> 3) - 1 || (wdx % nWw) == nWw - 1)) {   // elsewhere the mask is all zero
                         const float* mr = mask + ((size_t)wdx * NT + qrow) * NT + c0;
                         m0 = *reinterpret_cast<const float4*>(mr); m1 = *reinterpret_cast<const float4*>(mr + 4);
+                    }
+                    if constexpr (PAD) {
+                        if (pw != 0) {                    // shift term + padding term first (0, -100, -200: exact); 64-bit shifts on the word
+                            const float pq = ((pw >> qrow) & 1ull) ? -100.0f : 0.f;
+                            const uint32_t kb = (uint32_t)((pw >> c0) & 0xffull);
+                            m0.x += (kb & 1u) ? pq : 0.f; m0.y += (kb & 2u) ? pq : 0.f; m0.z += (kb & 4u) ? pq : 0.f; m0.w += (kb & 8u) ? pq : 0.f;
+                            m1.x += (kb & 16u) ? pq : 0.f; m1.y += (kb & 32u) ? pq : 0.f; m1.z += (kb & 64u) ? pq : 0.f; m1.w += (kb & 128u) ? pq : 0.f;
+                        }
                     }
                     float xr[8], a2[8];
                     const float4 s0 = *reinterpret_cast<const float4*>(&sm.s[qrow * SS + c0]);
@@ -748,15 +764,15 @@ __global__ void prepack_weights_multi_kernel(const PrepackMulti d) {
     }
 }
 
-template <int C, int SAVE, int NW = 1, bool P6 = false>
+template <int C, int SAVE, int NW = 1, bool P6 = false, bool PAD = false>
 void launch_fused(hipStream_t s, int nwin, const float* x, const float* gamma, const float* beta, const float* wqkv_p,
                   const float* bqkv, const float* wo_p, const float* bo, const uint8_t* idx, const float* bias,
                   const float* mask, const float* dscale, float* out, float* xn_save, float* qkv_save, float* ctx_save,
-                  float* stats_save, uint8_t* rank_save, int Hres, int Wres, int shift) {
+                  float* stats_save, uint8_t* rank_save, int Hres, int Wres, int shift, const uint64_t* pad = nullptr) {
     const size_t smem = NW * sizeof(FusedSmem<C>);
     static_assert(sizeof(FusedSmem<C>) % 16 == 0, "the second half's tiles start 16-byte aligned");
     if (smem > 48 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_window_attn_fwd_kernel<C, SAVE, NW, P6>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_window_attn_fwd_kernel<C, SAVE, NW, P6, PAD>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     // persistent workgroups (only with register-resident weights): exactly as many as are RESIDENT at once - the occupancy
     // the runtime reports for this code object (registers and LDS together: 2 per CU at 222 VGPRs, although 3 would fit the
@@ -769,7 +785,7 @@ void launch_fused(hipStream_t s, int nwin, const float* x, const float* gamma, c
     // resident workgroups per CU of this instantiation: queried once (thread-safe function-local static initialisation)
     static const int occ = [&] {
         int q = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, reinterpret_cast<const void*>(&fused_window_attn_fwd_kernel<C, SAVE, NW, P6>),
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, reinterpret_cast<const void*>(&fused_window_attn_fwd_kernel<C, SAVE, NW, P6, PAD>),
                                                          256 * NW, smem) != hipSuccess || q < 1)
             q = 2;
         return q;
@@ -778,10 +794,12 @@ void launch_fused(hipStream_t s, int nwin, const float* x, const float* gamma, c
     const int ncu = dhz_num_cus();
     int grid = (C == 32 && FUSED_PERSIST_C32) ? ncu * per_cu : nwin / NW;
     if (grid > nwin / NW) grid = nwin / NW;
-    hipLaunchKernelGGL((fused_window_attn_fwd_kernel<C, SAVE, NW, P6>), dim3(grid), dim3(256 * NW), smem, s, x, gamma, beta,
+    PadArg<PAD> pa;
+    if constexpr (PAD) pa.words = pad;
+    hipLaunchKernelGGL((fused_window_attn_fwd_kernel<C, SAVE, NW, P6, PAD>), dim3(grid), dim3(256 * NW), smem, s, x, gamma, beta,
                        reinterpret_cast<const float4*>(wqkv_p), bqkv, reinterpret_cast<const float4*>(wo_p), bo, idx,
                        bias, mask, dscale, out, xn_save, qkv_save, ctx_save, stats_save, rank_save, Hres, Wres, shift,
-                       nwin);
+                       nwin, pa);
 }
 
 }  // namespace
@@ -818,7 +836,7 @@ static int fused_fwd_impl(bool p6, const float* x, const float* gamma, const flo
                           const float* bqkv, const float* wo_p, const float* bo, const uint8_t* idx,
                           const float* bias, const float* mask, const float* drop_scale, float* out,
                           float* xn_save, float* qkv_save, float* ctx_save, float* stats_save,
-                          uint8_t* rank_save, int B, int Hres, int Wres, int C, int shift, void* stream) {
+                          uint8_t* rank_save, int B, int Hres, int Wres, int C, int shift, void* stream, const uint64_t* pad = nullptr) {
     DHZ_REQUIRE(x && gamma && beta && wqkv_p && bqkv && wo_p && bo && idx && out, "dhz_fused_window_attn_fwd: null pointer");
     DHZ_REQUIRE(C == 32 || C == 64 || C == 128, "dhz_fused_window_attn_fwd: C=%d unsupported (32, 64, 128)", C);
     DHZ_REQUIRE(B > 0 && Hres % 8 == 0 && Wres % 8 == 0 && Hres >= 8 && Wres >= 8 && shift >= 0 && shift < 8,
@@ -839,6 +857,8 @@ static int fused_fwd_impl(bool p6, const float* x, const float* gamma, const flo
                                            out, xn_save, qkv_save, ctx_save, stats_save, rank_save, Hres, Wres, shift);   \
         else if (save == 2) launch_fused<CC, 2>(s, nwin, x, gamma, beta, wqkv_p, bqkv, wo_p, bo, idx, bias, mask, drop_scale, \
                                                 out, nullptr, nullptr, nullptr, nullptr, rank_save, Hres, Wres, shift);      \
+        else if (pad) launch_fused<CC, 0, 1, false, true>(s, nwin, x, gamma, beta, wqkv_p, bqkv, wo_p, bo, idx, bias, mask, drop_scale, out, \
+                                                          nullptr, nullptr, nullptr, nullptr, nullptr, Hres, Wres, shift, pad); \
         else launch_fused<CC, 0>(s, nwin, x, gamma, beta, wqkv_p, bqkv, wo_p, bo, idx, bias, mask, drop_scale, out, \
                                  nullptr, nullptr, nullptr, nullptr, nullptr, Hres, Wres, shift);                \
     } while (0)
@@ -850,7 +870,7 @@ static int fused_fwd_impl(bool p6, const float* x, const float* gamma, const flo
 #else
     constexpr int pair_env = 0;
 #endif
-    if (C == 64 && pair_env == 2 && nwin % 2 == 0) {
+    if (C == 64 && pair_env == 2 && nwin % 2 == 0 && !pad) {
         if (save == 1) launch_fused<64, 1, 2>(s, nwin, x, gamma, beta, wqkv_p, bqkv, wo_p, bo, idx, bias, mask, drop_scale, out, xn_save,
                                               qkv_save, ctx_save, stats_save, rank_save, Hres, Wres, shift);
         else if (save == 2) launch_fused<64, 2, 2>(s, nwin, x, gamma, beta, wqkv_p, bqkv, wo_p, bo, idx, bias, mask, drop_scale, out,
@@ -868,6 +888,8 @@ static int fused_fwd_impl(bool p6, const float* x, const float* gamma, const flo
                                                     qkv_save, ctx_save, stats_save, rank_save, Hres, Wres, shift);         \
         else if (save == 2) launch_fused<CC, 2, 1, true>(s, nwin, x, gamma, beta, wqkv_p, bqkv, wo_p, bo, idx, bias, mask, drop_scale, out, \
                                                          nullptr, nullptr, nullptr, nullptr, rank_save, Hres, Wres, shift); \
+        else if (pad) launch_fused<CC, 0, 1, true, true>(s, nwin, x, gamma, beta, wqkv_p, bqkv, wo_p, bo, idx, bias, mask, drop_scale, out, nullptr, \
+                                                         nullptr, nullptr, nullptr, nullptr, Hres, Wres, shift, pad);      \
         else launch_fused<CC, 0, 1, true>(s, nwin, x, gamma, beta, wqkv_p, bqkv, wo_p, bo, idx, bias, mask, drop_scale, out, nullptr, nullptr, \
                                           nullptr, nullptr, nullptr, Hres, Wres, shift);                                   \
     } while (0)
@@ -912,6 +934,15 @@ extern "C" int dhz_fused_window_attn_fwd6(const float* x, const float* gamma, co
                                           uint8_t* rank_save, int B, int Hres, int Wres, int C, int shift, void* stream) {
     return fused_fwd_impl(true, x, gamma, beta, (const float*)wqkv6_p, bqkv, wo_p, bo, idx, bias, mask, drop_scale, out, xn_save, qkv_save,
                           ctx_save, stats_save, rank_save, B, Hres, Wres, C, shift, stream);
+}
+
+extern "C" int dhz_fused_window_attn_fwd_pad(int six_term, const float* x, const float* gamma, const float* beta, const void* wqkv_p,
+                                             const float* bqkv, const float* wo_p, const float* bo, const uint8_t* idx, const float* bias,
+                                             const float* mask, const uint64_t* pad, const float* drop_scale, float* out, int B, int Hres,
+                                             int Wres, int C, int shift, void* stream) {
+    DHZ_REQUIRE(pad, "dhz_fused_window_attn_fwd_pad: pad is NULL (dhz_fused_window_attn_fwd / _fwd6 take no padding words)");
+    return fused_fwd_impl(six_term != 0, x, gamma, beta, (const float*)wqkv_p, bqkv, wo_p, bo, idx, bias, mask, drop_scale, out, nullptr, nullptr,
+                          nullptr, nullptr, nullptr, B, Hres, Wres, C, shift, stream, pad);
 }
 
 extern "C" int dhz_fused_attn_prepack6(const float* wq, const float* wk, const float* wv, const float* wo, void* wqkv6_p, int C, void* stream) {

@@ -77,8 +77,12 @@ __device__ __forceinline__ float row8_sum(float v) {
 
 // Double softmax of one selected row, 8 columns per thread (8 threads per row):
 //   p1 = softmax(x);  a = p1 + bias + mask;  p2 = softmax(a)          (ATT:195, 229, 251-258, 262)
+// PAD: the padding word pw of the window (bit j: token j is padding) adds -100 where query qrow AND key c0 + i are padding.  The term is
+// summed with the shift-mask row FIRST (0, -100, -200: exact) and that sum added where the mask is added: the same bits as a materialised
+// [B_, 64, 64] tensor holding shift mask + padding mask.  Every shift on the word is 64-bit.
+template <bool PAD = false>
 __device__ __forceinline__ void double_softmax8(const float* x, const float* brow, const float* mrow, float* p1,
-                                                float* p2) {
+                                                float* p2, uint64_t pw = 0, int qrow = 0, int c0 = 0) {
     float mx = x[0];
 #pragma unroll
     for (int i = 1; i < 8; ++i) mx = fmaxf(mx, x[i]);
@@ -94,7 +98,17 @@ __device__ __forceinline__ void double_softmax8(const float* x, const float* bro
         const float4 b0 = *reinterpret_cast<const float4*>(brow), b1 = *reinterpret_cast<const float4*>(brow + 4);
         a[0] += b0.x; a[1] += b0.y; a[2] += b0.z; a[3] += b0.w; a[4] += b1.x; a[5] += b1.y; a[6] += b1.z; a[7] += b1.w;
     }
-    if (mrow) {
+    if (PAD && pw != 0) {                                // wave-uniform: one window per workgroup
+        float m[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (mrow) {
+            const float4 b0 = *reinterpret_cast<const float4*>(mrow), b1 = *reinterpret_cast<const float4*>(mrow + 4);
+            m[0] = b0.x; m[1] = b0.y; m[2] = b0.z; m[3] = b0.w; m[4] = b1.x; m[5] = b1.y; m[6] = b1.z; m[7] = b1.w;
+        }
+        const float pq = ((pw >> qrow) & 1ull) ? -100.0f : 0.f;
+        const uint32_t kb = (uint32_t)((pw >> c0) & 0xffull);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) a[i] += m[i] + (((kb >> i) & 1u) ? pq : 0.f);
+    } else if (mrow) {
         const float4 b0 = *reinterpret_cast<const float4*>(mrow), b1 = *reinterpret_cast<const float4*>(mrow + 4);
         a[0] += b0.x; a[1] += b0.y; a[2] += b0.z; a[3] += b0.w; a[4] += b1.x; a[5] += b1.y; a[6] += b1.z; a[7] += b1.w;
     }
@@ -110,13 +124,15 @@ __device__ __forceinline__ void double_softmax8(const float* x, const float* bro
     for (int i = 0; i < 8; ++i) p2[i] = e[i] * sum2;
 }
 
-template <int D, typename T>
+// PAD: the last argument carries the padding words (PadArg, common.h): pad.words[b] of the GLOBAL window b; the shift mask keeps b % nW.
+
+template <int D, typename T, bool PAD = false>
 __global__ __launch_bounds__(256) void ps_attn_fwd_kernel(const T* __restrict__ q, const T* __restrict__ k,
                                                           const T* __restrict__ v, int ld,
                                                           const uint8_t* __restrict__ idx,
                                                           const float* __restrict__ bias,
                                                           const float* __restrict__ mask, T* __restrict__ out,
-                                                          int ldo, uint8_t* __restrict__ rank_out, int H, int nW, int nwh) {
+                                                          int ldo, uint8_t* __restrict__ rank_out, int H, int nW, int nwh, PadArg<PAD> pad) {
     constexpr int DS = D + 4;
     constexpr int F = D / 4;            // float4 per row
     constexpr int RPP = 256 / F;        // rows per load pass
@@ -144,6 +160,8 @@ __global__ __launch_bounds__(256) void ps_attn_fwd_kernel(const T* __restrict__ 
     for (int wh = blockIdx.x; wh < nwh; wh += gridDim.x) {
     const int b = wh / H, h = wh % H;
     const size_t tok0 = (size_t)b * NT;
+    uint64_t pw = 0;
+    if constexpr (PAD) pw = pad.words[b];
     __syncthreads();                                   // the previous window-head's scatter has read O / rank
 
     // ---- stage Q,K,V into LDS, then start the next window-head's loads
@@ -249,7 +267,7 @@ __global__ __launch_bounds__(256) void ps_attn_fwd_kernel(const T* __restrict__ 
             x[4] = s1.x * scale; x[5] = s1.y * scale; x[6] = s1.z * scale; x[7] = s1.w * scale;
             const float* brow = bias ? bias + ((size_t)h * NT + qrow) * NT + c0 : nullptr;
             const float* mrow = mask ? mask + ((size_t)(b % nW) * NT + qrow) * NT + c0 : nullptr;
-            double_softmax8(x, brow, mrow, p1, p2);
+            double_softmax8<PAD>(x, brow, mrow, p1, p2, pw, qrow, c0);
         } else {
             const float f = (r == NU) ? (1.0f / NT) : 0.f;
 #pragma unroll
@@ -308,12 +326,13 @@ struct BwdSmem {
     uint8_t rank[NT];
 };
 
-template <int D, bool HAS_BIAS, typename T>
+// (PAD as in the forward; the padding term only enters the recomputation of P: no gradient flows to it)
+template <int D, bool HAS_BIAS, typename T, bool PAD = false>
 __global__ __launch_bounds__(256) void ps_attn_bwd_kernel(
     const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, int ld,
     const float* __restrict__ bias, const float* __restrict__ mask, const uint8_t* __restrict__ rank_in,
     const T* __restrict__ dout, int ldo, T* __restrict__ dq, T* __restrict__ dk, T* __restrict__ dv,
-    int ldg, float* __restrict__ dbias_part, int B_, int H, int nW) {
+    int ldg, float* __restrict__ dbias_part, int B_, int H, int nW, PadArg<PAD> pad) {
     constexpr int DS = D + 4;
     constexpr int F = D / 4;
     constexpr int RPP = 256 / F;
@@ -362,6 +381,8 @@ __global__ __launch_bounds__(256) void ps_attn_bwd_kernel(
 
     for (int b = blockIdx.x / H; b < B_; b += bstep) {
         const size_t tok0 = (size_t)b * NT;
+        uint64_t pw = 0;
+        if constexpr (PAD) pw = pad.words[b];
         __syncthreads();   // previous iteration's staging reads are done
         if (t < NT) {
             const uint8_t r = prank;
@@ -428,7 +449,7 @@ __global__ __launch_bounds__(256) void ps_attn_bwd_kernel(
                 for (int i = 0; i < 8; ++i) x[i] = sm.p1[r * SS + c0 + i] * scale;
                 const float* brow = bias ? bias + ((size_t)h * NT + qrow) * NT + c0 : nullptr;
                 const float* mrow = mask ? mask + ((size_t)(b % nW) * NT + qrow) * NT + c0 : nullptr;
-                double_softmax8(x, brow, mrow, p1, p2);
+                double_softmax8<PAD>(x, brow, mrow, p1, p2, pw, qrow, c0);
             } else {
                 const float f = (r == NU) ? (1.0f / NT) : 0.f;
 #pragma unroll
@@ -721,10 +742,24 @@ static void allow_smem(const void* fn, size_t bytes) {
     if (bytes > 48 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
+template <int D, typename T>
+static void launch_fwd(int grid, hipStream_t s, const T* q, const T* k, const T* v, int ld, const uint8_t* idx, const float* bias,
+                       const float* mask, const uint64_t* pad, T* out, int ldo, uint8_t* rank, int H, int nW, int nwh) {
+    if (pad) {
+        allow_smem(reinterpret_cast<const void*>(&ps_attn_fwd_kernel<D, T, true>), sizeof(FwdSmem<D>));
+        hipLaunchKernelGGL((ps_attn_fwd_kernel<D, T, true>), dim3(grid), dim3(256), sizeof(FwdSmem<D>), s, q, k, v, ld, idx,
+                           bias, mask, out, ldo, rank, H, nW, nwh, PadArg<true>{pad});
+    } else {
+        allow_smem(reinterpret_cast<const void*>(&ps_attn_fwd_kernel<D, T>), sizeof(FwdSmem<D>));
+        hipLaunchKernelGGL((ps_attn_fwd_kernel<D, T>), dim3(grid), dim3(256), sizeof(FwdSmem<D>), s, q, k, v, ld, idx,
+                           bias, mask, out, ldo, rank, H, nW, nwh, PadArg<false>{});
+    }
+}
+
 template <typename T>
 static int ps_attn_fwd_t(const T* q, const T* k, const T* v, int ld, const uint8_t* idx,
                                const float* bias, const float* mask, T* out, int ldo, uint8_t* rank, int B_,
-                               int H, int nW, int d, void* stream) {
+                               int H, int nW, int d, void* stream, const uint64_t* pad = nullptr) {
     DHZ_REQUIRE(q && k && v && idx && out && rank, "dhz_ps_attn_fwd: null pointer");
     DHZ_REQUIRE(B_ > 0 && H > 0, "dhz_ps_attn_fwd: B_=%d H=%d", B_, H);
     DHZ_REQUIRE(d == 16 || d == 32 || d == 64, "dhz_ps_attn_fwd: head_dim %d unsupported (16, 32 or 64)", d);
@@ -734,18 +769,11 @@ static int ps_attn_fwd_t(const T* q, const T* k, const T* v, int ld, const uint8
     // persistent workgroups, three per CU (LDS: 36.3 KiB at d = 32, 52.7 KiB at d = 64)
     const int resident = (d == 32 ? PSF_WG32 : PSF_WG64) * dhz_num_cus();
     const int grid = B_ * H < resident ? B_ * H : resident;
-    if (d == 16) {                                 // embed_dim 16 ("Uformer16", utils/model_utils.py:96-98): four MFMA k-steps per score tile
-        hipLaunchKernelGGL((ps_attn_fwd_kernel<16, T>), dim3(grid), dim3(256), sizeof(FwdSmem<16>), s, q, k, v, ld, idx,
-                           bias, mask, out, ldo, rank, H, nW > 0 ? nW : 1, B_ * H);
-    } else if (d == 32) {
-        allow_smem(reinterpret_cast<const void*>(&ps_attn_fwd_kernel<32, T>), sizeof(FwdSmem<32>));
-        hipLaunchKernelGGL((ps_attn_fwd_kernel<32, T>), dim3(grid), dim3(256), sizeof(FwdSmem<32>), s, q, k, v, ld, idx,
-                           bias, mask, out, ldo, rank, H, nW > 0 ? nW : 1, B_ * H);
-    } else {
-        allow_smem(reinterpret_cast<const void*>(&ps_attn_fwd_kernel<64, T>), sizeof(FwdSmem<64>));
-        hipLaunchKernelGGL((ps_attn_fwd_kernel<64, T>), dim3(grid), dim3(256), sizeof(FwdSmem<64>), s, q, k, v, ld, idx,
-                           bias, mask, out, ldo, rank, H, nW > 0 ? nW : 1, B_ * H);
-    }
+    if (nW <= 0) nW = 1;
+    // d = 16: embed_dim 16 ("Uformer16", utils/model_utils.py:96-98): four MFMA k-steps per score tile
+    if (d == 16) launch_fwd<16, T>(grid, s, q, k, v, ld, idx, bias, mask, pad, out, ldo, rank, H, nW, B_ * H);
+    else if (d == 32) launch_fwd<32, T>(grid, s, q, k, v, ld, idx, bias, mask, pad, out, ldo, rank, H, nW, B_ * H);
+    else launch_fwd<64, T>(grid, s, q, k, v, ld, idx, bias, mask, pad, out, ldo, rank, H, nW, B_ * H);
     DHZ_CHECK_LAUNCH("dhz_ps_attn_fwd");
     return DHZ_OK;
 }
@@ -761,6 +789,19 @@ extern "C" int dhz_ps_attn_fwd_dt(const void* q, const void* k, const void* v, i
     if (dtype == DHZ_F32) return ps_attn_fwd_t<float>((const float*)q, (const float*)k, (const float*)v, ld, idx, bias, mask, (float*)out, ldo, rank, B_, H, nW, d, stream);
     if (dtype == DHZ_BF16) return ps_attn_fwd_t<bf16s>((const bf16s*)q, (const bf16s*)k, (const bf16s*)v, ld, idx, bias, mask, (bf16s*)out, ldo, rank, B_, H, nW, d, stream);
     dhz_set_error("dhz_ps_attn_fwd_dt: unknown dtype %d", dtype);
+    return DHZ_EINVAL;
+}
+// the padding words of a forward are one per window of the batch: B_ is a whole number of images of nW windows
+#define DHZ_REQUIRE_PAD(who)                                                                                       \
+    DHZ_REQUIRE(pad, "%s: pad is NULL (the entry without _pad takes no padding words)", who);                      \
+    DHZ_REQUIRE(nW > 0 && B_ % nW == 0, "%s: B_=%d is not a whole number of images of nW=%d windows", who, B_, nW)
+extern "C" int dhz_ps_attn_fwd_dt_pad(const void* q, const void* k, const void* v, int ld, const uint8_t* idx,
+                                      const float* bias, const float* mask, const uint64_t* pad, void* out, int ldo, uint8_t* rank,
+                                      int B_, int H, int nW, int d, int dtype, void* stream) {
+    DHZ_REQUIRE_PAD("dhz_ps_attn_fwd_dt_pad");
+    if (dtype == DHZ_F32) return ps_attn_fwd_t<float>((const float*)q, (const float*)k, (const float*)v, ld, idx, bias, mask, (float*)out, ldo, rank, B_, H, nW, d, stream, pad);
+    if (dtype == DHZ_BF16) return ps_attn_fwd_t<bf16s>((const bf16s*)q, (const bf16s*)k, (const bf16s*)v, ld, idx, bias, mask, (bf16s*)out, ldo, rank, B_, H, nW, d, stream, pad);
+    dhz_set_error("dhz_ps_attn_fwd_dt_pad: unknown dtype %d", dtype);
     return DHZ_EINVAL;
 }
 
@@ -782,18 +823,24 @@ extern "C" int dhz_ps_attn_bwd_parts(int B_, int H) { return dhz_ps_attn_bwd_par
 template <int D, bool HB, typename T>
 static void launch_bwd(int parts, hipStream_t s, const T* q, const T* k, const T* v, int ld,
                        const float* bias, const float* mask, const uint8_t* rank, const T* dout, int ldo,
-                       T* dq, T* dk, T* dv, int ldg, float* dbias_part, int B_, int H, int nW) {
+                       T* dq, T* dk, T* dv, int ldg, float* dbias_part, int B_, int H, int nW, const uint64_t* pad) {
     const size_t smem = sizeof(BwdSmem<D>);
+    if (pad) {
+        allow_smem(reinterpret_cast<const void*>(&ps_attn_bwd_kernel<D, HB, T, true>), smem);
+        hipLaunchKernelGGL((ps_attn_bwd_kernel<D, HB, T, true>), dim3(parts), dim3(256), smem, s, q, k, v, ld, bias, mask, rank,
+                           dout, ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW, PadArg<true>{pad});
+        return;
+    }
     allow_smem(reinterpret_cast<const void*>(&ps_attn_bwd_kernel<D, HB, T>), smem);
     hipLaunchKernelGGL((ps_attn_bwd_kernel<D, HB, T>), dim3(parts), dim3(256), smem, s, q, k, v, ld, bias, mask, rank,
-                       dout, ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW);
+                       dout, ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW, PadArg<false>{});
 }
 
 template <typename T>
 static int ps_attn_bwd_t(const T* q, const T* k, const T* v, int ld, const float* bias,
                          const float* mask, const uint8_t* rank, const T* dout, int ldo, T* dq,
                          T* dk, T* dv, int ldg, float* dbias_part, int B_, int H, int nW, int d,
-                         void* stream) {
+                         void* stream, const uint64_t* pad = nullptr) {
     DHZ_REQUIRE(q && k && v && rank && dout && dq && dk && dv, "dhz_ps_attn_bwd: null pointer");
     DHZ_REQUIRE(d == 16 || d == 32 || d == 64, "dhz_ps_attn_bwd: head_dim %d unsupported (16, 32 or 64)", d);
     DHZ_REQUIRE(!bias || dbias_part, "dhz_ps_attn_bwd: bias given but dbias_part is NULL");
@@ -803,14 +850,14 @@ static int ps_attn_bwd_t(const T* q, const T* k, const T* v, int ld, const float
     const int parts = dhz_ps_attn_bwd_parts_d(B_, H, d);
     if (nW <= 0) nW = 1;
     if (d == 16) {
-        if (bias) launch_bwd<16, true>(parts, s, q, k, v, ld, bias, mask, rank, dout, ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW);
-        else launch_bwd<16, false>(parts, s, q, k, v, ld, bias, mask, rank, dout, ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW);
+        if (bias) launch_bwd<16, true>(parts, s, q, k, v, ld, bias, mask, rank, dout, ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW, pad);
+        else launch_bwd<16, false>(parts, s, q, k, v, ld, bias, mask, rank, dout, ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW, pad);
     } else if (d == 32) {
-        if (bias) launch_bwd<32, true>(parts, s, q, k, v, ld, bias, mask, rank, dout, ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW);
-        else launch_bwd<32, false>(parts, s, q, k, v, ld, bias, mask, rank, dout, ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW);
+        if (bias) launch_bwd<32, true>(parts, s, q, k, v, ld, bias, mask, rank, dout, ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW, pad);
+        else launch_bwd<32, false>(parts, s, q, k, v, ld, bias, mask, rank, dout, ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW, pad);
     } else {
-        if (bias) launch_bwd<64, true>(parts, s, q, k, v, ld, bias, mask, rank, dout, ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW);
-        else launch_bwd<64, false>(parts, s, q, k, v, ld, bias, mask, rank, dout, ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW);
+        if (bias) launch_bwd<64, true>(parts, s, q, k, v, ld, bias, mask, rank, dout, ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW, pad);
+        else launch_bwd<64, false>(parts, s, q, k, v, ld, bias, mask, rank, dout, ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW, pad);
     }
     DHZ_CHECK_LAUNCH("dhz_ps_attn_bwd");
     return DHZ_OK;
@@ -831,6 +878,17 @@ extern "C" int dhz_ps_attn_bwd_dt(const void* q, const void* k, const void* v, i
     dhz_set_error("dhz_ps_attn_bwd_dt: unknown dtype %d", dtype);
     return DHZ_EINVAL;
 }
+extern "C" int dhz_ps_attn_bwd_dt_pad(const void* q, const void* k, const void* v, int ld, const float* bias,
+                                      const float* mask, const uint64_t* pad, const uint8_t* rank, const void* dout, int ldo, void* dq,
+                                      void* dk, void* dv, int ldg, float* dbias_part, int B_, int H, int nW, int d,
+                                      int dtype, void* stream) {
+    DHZ_REQUIRE_PAD("dhz_ps_attn_bwd_dt_pad");
+    if (dtype == DHZ_F32) return ps_attn_bwd_t<float>((const float*)q, (const float*)k, (const float*)v, ld, bias, mask, rank, (const float*)dout, ldo, (float*)dq, (float*)dk, (float*)dv, ldg, dbias_part, B_, H, nW, d, stream, pad);
+    if (dtype == DHZ_BF16) return ps_attn_bwd_t<bf16s>((const bf16s*)q, (const bf16s*)k, (const bf16s*)v, ld, bias, mask, rank, (const bf16s*)dout, ldo, (bf16s*)dq, (bf16s*)dk, (bf16s*)dv, ldg, dbias_part, B_, H, nW, d, stream, pad);
+    dhz_set_error("dhz_ps_attn_bwd_dt_pad: unknown dtype %d", dtype);
+    return DHZ_EINVAL;
+}
+#undef DHZ_REQUIRE_PAD
 
 extern "C" int dhz_bias_gather(const float* table, float* bias, int H, void* stream) {
     DHZ_REQUIRE(table && bias && H > 0, "dhz_bias_gather: bad arguments");

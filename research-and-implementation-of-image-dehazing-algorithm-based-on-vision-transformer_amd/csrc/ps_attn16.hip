@@ -57,8 +57,11 @@ __device__ __forceinline__ void softmax4(const float* x, float* p) {
 // the probabilities of row r, columns c0 .. c0 + 3, from the scaled scores x.  Every lane runs the shuffles (no divergence around them).
 //   ProbSparse: p1 = softmax(x); p2 = softmax(p1 + bias + mask)  (ATT:195, 229, 251-258, 262); unselected row: p1 = 0, p2 = 1/16
 //   dense:      p2 = softmax(x + bias + mask)  (M0:470-488); p1 is not used
-template <bool DENSE>
-__device__ __forceinline__ void probs16(const float* x, const float* brow, const float* mrow, bool sel, float* p1, float* p2) {
+// PAD: the padding word pw of the window (low 16 bits; bit j: token j is padding) adds -100 where query r AND key c0 + i are padding - summed
+// with the shift-mask row first (exact), that sum added where the mask is added: the bits of a materialised shift + padding mask tensor
+template <bool DENSE, bool PAD = false>
+__device__ __forceinline__ void probs16(const float* x, const float* brow, const float* mrow, bool sel, float* p1, float* p2,
+                                        uint64_t pw = 0, int r = 0, int c0 = 0) {
     float a[4];
     if (DENSE) {
 #pragma unroll
@@ -69,7 +72,14 @@ __device__ __forceinline__ void probs16(const float* x, const float* brow, const
         for (int i = 0; i < 4; ++i) a[i] = p1[i];
     }
     if (brow) { const float4 b = *reinterpret_cast<const float4*>(brow); a[0] += b.x; a[1] += b.y; a[2] += b.z; a[3] += b.w; }
-    if (mrow) { const float4 b = *reinterpret_cast<const float4*>(mrow); a[0] += b.x; a[1] += b.y; a[2] += b.z; a[3] += b.w; }
+    if (PAD && pw != 0) {                                  // wave-uniform: one window per wave
+        float m[4] = {0.f, 0.f, 0.f, 0.f};
+        if (mrow) { const float4 b = *reinterpret_cast<const float4*>(mrow); m[0] = b.x; m[1] = b.y; m[2] = b.z; m[3] = b.w; }
+        const float pq = ((pw >> r) & 1ull) ? -100.0f : 0.f;
+        const uint32_t kb = (uint32_t)((pw >> c0) & 0xfull);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a[i] += m[i] + (((kb >> i) & 1u) ? pq : 0.f);
+    } else if (mrow) { const float4 b = *reinterpret_cast<const float4*>(mrow); a[0] += b.x; a[1] += b.y; a[2] += b.z; a[3] += b.w; }
     softmax4(a, p2);
     if (!DENSE && !sel) {
 #pragma unroll
@@ -89,11 +99,13 @@ struct Fwd16 {
     uint8_t rank[NT];
 };
 
-template <int D, typename T, bool DENSE>
+// PAD: the last argument carries the padding words (PadArg, common.h): pad.words[b] of the GLOBAL window b; the shift mask keeps b % nW.
+template <int D, typename T, bool DENSE, bool PAD = false>
 __global__ __launch_bounds__(256) void attn16_fwd_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v,
                                                          int ld, const uint8_t* __restrict__ idx, const float* __restrict__ bias,
                                                          const float* __restrict__ mask, T* __restrict__ out, int ldo,
-                                                         uint8_t* __restrict__ rank_out, int H, int nW, int nwh, float scale) {
+                                                         uint8_t* __restrict__ rank_out, int H, int nW, int nwh, float scale,
+                                                         PadArg<PAD> pad) {
     constexpr int DS = D + 4, F = D / 4, NR = D / 16;      // float4 per row; staged float4 per lane and tensor
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -130,6 +142,8 @@ __global__ __launch_bounds__(256) void attn16_fwd_kernel(const T* __restrict__ q
     for (; wh < nwh; wh += stride) {
         const int b = wh / H, h = wh % H;
         const size_t tok0 = (size_t)b * NT;
+        uint64_t pw = 0;
+        if constexpr (PAD) pw = pad.words[b] & 0xffffull;
         wave_sync();                                       // the previous window-head's stores have read O / rank
 #pragma unroll
         for (int p = 0; p < NR; ++p) {
@@ -191,7 +205,7 @@ __global__ __launch_bounds__(256) void attn16_fwd_kernel(const T* __restrict__ q
             const float* brow = bias ? bias + ((size_t)h * NT + r) * NT + c0 : nullptr;
             const float* mrow = mask ? mask + ((size_t)(b % nW) * NT + r) * NT + c0 : nullptr;
             float p1[4], p2[4];
-            probs16<DENSE>(x, brow, mrow, DENSE || sm.rank[r] != 255, p1, p2);
+            probs16<DENSE, PAD>(x, brow, mrow, DENSE || sm.rank[r] != 255, p1, p2, pw, r, c0);
             *reinterpret_cast<float4*>(&sm.s[r * SS + c0]) = make_float4(p2[0], p2[1], p2[2], p2[3]);
         }
         wave_sync();
@@ -231,13 +245,14 @@ struct Bwd16 {
 
 // wave gw (< parts) owns head gw % H and the windows gw / H, + parts / H, ...; it stores the bias-gradient sum of its window-heads at
 // dbias_part[gw] (4 registers per lane: row lane >> 2, columns 4 (lane & 3) ..)
-template <int D, typename T, bool DENSE, bool HAS_BIAS>
+// (PAD as in the forward; the padding term only enters the recomputation of P: no gradient flows to it)
+template <int D, typename T, bool DENSE, bool HAS_BIAS, bool PAD = false>
 __global__ __launch_bounds__(256) void attn16_bwd_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v,
                                                          int ld, const float* __restrict__ bias, const float* __restrict__ mask,
                                                          const uint8_t* __restrict__ rank_in, const T* __restrict__ dout, int ldo,
                                                          T* __restrict__ dq, T* __restrict__ dk, T* __restrict__ dv, int ldg,
                                                          float* __restrict__ dbias_part, int B_, int H, int nW, int parts,
-                                                         float scale) {
+                                                         float scale, PadArg<PAD> pad) {
     constexpr int DS = D + 4, F = D / 4, NR = D / 16;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -268,6 +283,8 @@ __global__ __launch_bounds__(256) void attn16_bwd_kernel(const T* __restrict__ q
 #pragma unroll 1
     for (; b < B_; b += bstep) {
         const size_t tok0 = (size_t)b * NT;
+        uint64_t pw = 0;
+        if constexpr (PAD) pw = pad.words[b] & 0xffffull;
         wave_sync();                                       // the previous window-head's stores have read the staging tiles
 #pragma unroll
         for (int p = 0; p < NR; ++p) {
@@ -300,7 +317,7 @@ __global__ __launch_bounds__(256) void attn16_bwd_kernel(const T* __restrict__ q
             const float x[4] = {s4.x * scale, s4.y * scale, s4.z * scale, s4.w * scale};
             const float* brow = bias ? bias + ((size_t)h * NT + r) * NT + c0 : nullptr;
             const float* mrow = mask ? mask + ((size_t)(b % nW) * NT + r) * NT + c0 : nullptr;
-            probs16<DENSE>(x, brow, mrow, sel, p1, p2);
+            probs16<DENSE, PAD>(x, brow, mrow, sel, p1, p2, pw, r, c0);
             *reinterpret_cast<float4*>(&sm.p[r * SS + c0]) = make_float4(p2[0], p2[1], p2[2], p2[3]);
         }
         wave_sync();
@@ -383,6 +400,31 @@ __global__ __launch_bounds__(256) void attn16_bwd_kernel(const T* __restrict__ q
             make_float4(accb[0], accb[1], accb[2], accb[3]);
 }
 
+// ------------------------------------------------------------------------------------------------ padding words
+// bits[b] of window b = image (nW) + window row (nWw) + window column of the UNSHIFTED H x W map: bit i = mask[img, 0, y Himg / H, x Wimg / W] != 0
+// for token i = (y % win) win + x % win - nearest-neighbour resampling at a whole ratio.  One lane per token; a wave ballots 64 tokens
+// (one 8 x 8 window, or four 4 x 4 windows whose words are the 16-bit fields).
+__global__ __launch_bounds__(256) void pad_window_bits_kernel(const float* __restrict__ mask, uint64_t* __restrict__ bits, int Himg, int Wimg,
+                                                              int H, int W, int lw, long long ntok) {
+    const int win = 1 << lw, N = win * win;
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;      // token of the window-ordered list
+    const bool valid = e < ntok;
+    float m = 0.f;
+    long long b = 0;
+    if (valid) {
+        b = e >> (2 * lw);
+        const int tok = (int)(e & (N - 1));
+        const int nWw = W >> lw, nWi = (H >> lw) * nWw;
+        const long long img = b / nWi;
+        const int wdx = (int)(b % nWi);
+        const int y = ((wdx / nWw) << lw) + (tok >> lw), x = ((wdx % nWw) << lw) + (tok & (win - 1));
+        m = mask[(size_t)img * Himg * Wimg + (size_t)(y * (Himg / H)) * Wimg + x * (Wimg / W)];
+    }
+    const uint64_t bal = __builtin_amdgcn_ballot_w64(valid && m != 0.f);
+    const int lane = threadIdx.x & 63;
+    if (valid && (lane & (N - 1)) == 0) bits[b] = lw == 3 ? bal : ((bal >> (lane & 48)) & 0xffffull);
+}
+
 // ------------------------------------------------------------------------------------------------ small helpers, window = 1 << lw
 __global__ void bias_gather_w_kernel(const float* __restrict__ table, float* __restrict__ bias, int H, int lw) {
     const int win = 1 << lw, N = win * win;
@@ -456,18 +498,26 @@ int win_log2(int win) { return win == 4 ? 2 : (win == 8 ? 3 : -1); }
 
 template <int D, typename T, bool DENSE>
 void launch_fwd16(hipStream_t s, const T* q, const T* k, const T* v, int ld, const uint8_t* idx, const float* bias, const float* mask,
-                  T* out, int ldo, uint8_t* rank, int B_, int H, int nW, float scale) {
+                  T* out, int ldo, uint8_t* rank, int B_, int H, int nW, float scale, const uint64_t* pad) {
     const int nwh = B_ * H, wgs = (nwh + 3) / 4;
     const int resident = PS16_FWD_WG(D) * dhz_num_cus();
     const size_t smem = 4 * sizeof(Fwd16<D>);
+    if constexpr (!DENSE) {
+        if (pad) {
+            allow_smem(&attn16_fwd_kernel<D, T, false, true>, smem);
+            hipLaunchKernelGGL((attn16_fwd_kernel<D, T, false, true>), dim3(wgs < resident ? wgs : resident), dim3(256), smem, s, q, k, v, ld, idx,
+                               bias, mask, out, ldo, rank, H, nW, nwh, scale, PadArg<true>{pad});
+            return;
+        }
+    }
     allow_smem(&attn16_fwd_kernel<D, T, DENSE>, smem);
     hipLaunchKernelGGL((attn16_fwd_kernel<D, T, DENSE>), dim3(wgs < resident ? wgs : resident), dim3(256), smem, s, q, k, v, ld, idx, bias,
-                       mask, out, ldo, rank, H, nW, nwh, scale);
+                       mask, out, ldo, rank, H, nW, nwh, scale, PadArg<false>{});
 }
 
 template <typename T, bool DENSE>
 int attn16_fwd(const char* who, const T* q, const T* k, const T* v, int ld, const uint8_t* idx, const float* bias, const float* mask, T* out,
-               int ldo, uint8_t* rank, int B_, int H, int nW, int d, float scale, void* stream) {
+               int ldo, uint8_t* rank, int B_, int H, int nW, int d, float scale, void* stream, const uint64_t* pad = nullptr) {
     DHZ_REQUIRE(q && k && v && out && (DENSE || (idx && rank)), "%s: null pointer", who);
     DHZ_REQUIRE(B_ > 0 && H > 0, "%s: B_=%d H=%d", who, B_, H);
     DHZ_REQUIRE(d == 16 || d == 32 || d == 64, "%s: head_dim %d unsupported (16, 32 or 64)", who, d);
@@ -475,9 +525,9 @@ int attn16_fwd(const char* who, const T* q, const T* k, const T* v, int ld, cons
     DHZ_REQUIRE(!mask || (nW > 0 && B_ % nW == 0), "%s: B_=%d not a multiple of nW=%d", who, B_, nW);
     hipStream_t s = (hipStream_t)stream;
     if (nW <= 0) nW = 1;
-    if (d == 16) launch_fwd16<16, T, DENSE>(s, q, k, v, ld, idx, bias, mask, out, ldo, rank, B_, H, nW, scale);
-    else if (d == 32) launch_fwd16<32, T, DENSE>(s, q, k, v, ld, idx, bias, mask, out, ldo, rank, B_, H, nW, scale);
-    else launch_fwd16<64, T, DENSE>(s, q, k, v, ld, idx, bias, mask, out, ldo, rank, B_, H, nW, scale);
+    if (d == 16) launch_fwd16<16, T, DENSE>(s, q, k, v, ld, idx, bias, mask, out, ldo, rank, B_, H, nW, scale, pad);
+    else if (d == 32) launch_fwd16<32, T, DENSE>(s, q, k, v, ld, idx, bias, mask, out, ldo, rank, B_, H, nW, scale, pad);
+    else launch_fwd16<64, T, DENSE>(s, q, k, v, ld, idx, bias, mask, out, ldo, rank, B_, H, nW, scale, pad);
     DHZ_CHECK_LAUNCH(who);
     return DHZ_OK;
 }
@@ -494,24 +544,39 @@ int parts16(int B_, int H, int d) {
 
 template <int D, typename T, bool DENSE>
 void launch_bwd16(hipStream_t s, const T* q, const T* k, const T* v, int ld, const float* bias, const float* mask, const uint8_t* rank,
-                  const T* dout, int ldo, T* dq, T* dk, T* dv, int ldg, float* dbias_part, int B_, int H, int nW, float scale) {
+                  const T* dout, int ldo, T* dq, T* dk, T* dv, int ldg, float* dbias_part, int B_, int H, int nW, float scale,
+                  const uint64_t* pad) {
     const int parts = parts16(B_, H, D);
     const size_t smem = 4 * sizeof(Bwd16<D>);
+    if constexpr (!DENSE) {
+        if (pad && bias) {
+            allow_smem(&attn16_bwd_kernel<D, T, false, true, true>, smem);
+            hipLaunchKernelGGL((attn16_bwd_kernel<D, T, false, true, true>), dim3((parts + 3) / 4), dim3(256), smem, s, q, k, v, ld, bias, mask, rank,
+                               dout, ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW, parts, scale, PadArg<true>{pad});
+            return;
+        }
+        if (pad) {
+            allow_smem(&attn16_bwd_kernel<D, T, false, false, true>, smem);
+            hipLaunchKernelGGL((attn16_bwd_kernel<D, T, false, false, true>), dim3((parts + 3) / 4), dim3(256), smem, s, q, k, v, ld, bias, mask, rank,
+                               dout, ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW, parts, scale, PadArg<true>{pad});
+            return;
+        }
+    }
     if (bias) {
         allow_smem(&attn16_bwd_kernel<D, T, DENSE, true>, smem);
         hipLaunchKernelGGL((attn16_bwd_kernel<D, T, DENSE, true>), dim3((parts + 3) / 4), dim3(256), smem, s, q, k, v, ld, bias, mask, rank, dout,
-                           ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW, parts, scale);
+                           ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW, parts, scale, PadArg<false>{});
     } else {
         allow_smem(&attn16_bwd_kernel<D, T, DENSE, false>, smem);
         hipLaunchKernelGGL((attn16_bwd_kernel<D, T, DENSE, false>), dim3((parts + 3) / 4), dim3(256), smem, s, q, k, v, ld, bias, mask, rank, dout,
-                           ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW, parts, scale);
+                           ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW, parts, scale, PadArg<false>{});
     }
 }
 
 template <typename T, bool DENSE>
 int attn16_bwd(const char* who, const T* q, const T* k, const T* v, int ld, const float* bias, const float* mask, const uint8_t* rank,
                const T* dout, int ldo, T* dq, T* dk, T* dv, int ldg, float* dbias_part, int B_, int H, int nW, int d, float scale,
-               void* stream) {
+               void* stream, const uint64_t* pad = nullptr) {
     DHZ_REQUIRE(q && k && v && dout && dq && dk && dv && (DENSE || rank), "%s: null pointer", who);
     DHZ_REQUIRE(B_ > 0 && H > 0, "%s: B_=%d H=%d", who, B_, H);
     DHZ_REQUIRE(d == 16 || d == 32 || d == 64, "%s: head_dim %d unsupported (16, 32 or 64)", who, d);
@@ -521,9 +586,9 @@ int attn16_bwd(const char* who, const T* q, const T* k, const T* v, int ld, cons
     DHZ_REQUIRE(!mask || (nW > 0 && B_ % nW == 0), "%s: B_=%d not a multiple of nW=%d", who, B_, nW);
     hipStream_t s = (hipStream_t)stream;
     if (nW <= 0) nW = 1;
-    if (d == 16) launch_bwd16<16, T, DENSE>(s, q, k, v, ld, bias, mask, rank, dout, ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW, scale);
-    else if (d == 32) launch_bwd16<32, T, DENSE>(s, q, k, v, ld, bias, mask, rank, dout, ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW, scale);
-    else launch_bwd16<64, T, DENSE>(s, q, k, v, ld, bias, mask, rank, dout, ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW, scale);
+    if (d == 16) launch_bwd16<16, T, DENSE>(s, q, k, v, ld, bias, mask, rank, dout, ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW, scale, pad);
+    else if (d == 32) launch_bwd16<32, T, DENSE>(s, q, k, v, ld, bias, mask, rank, dout, ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW, scale, pad);
+    else launch_bwd16<64, T, DENSE>(s, q, k, v, ld, bias, mask, rank, dout, ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW, scale, pad);
     DHZ_CHECK_LAUNCH(who);
     return DHZ_OK;
 }
@@ -567,6 +632,63 @@ extern "C" int dhz_ps_attn_bwd_w(const void* q, const void* k, const void* v, in
                                         (const bf16s*)dout, ldo, (bf16s*)dq, (bf16s*)dk, (bf16s*)dv, ldg, dbias_part, B_, H, nW, d, scale, stream);
     dhz_set_error("dhz_ps_attn_bwd_w: unknown dtype %d", dtype);
     return DHZ_EINVAL;
+}
+
+// padding-bit forms: pad[B_] uint64, bit i of word b = token i of GLOBAL window b is padding (4 x 4 windows: the low 16 bits); the shift
+// mask keeps b % nW.  win = 8 runs dhz_ps_attn_fwd_dt_pad / dhz_ps_attn_bwd_dt_pad.
+#define DHZ_REQUIRE_PAD(who)                                                                                       \
+    DHZ_REQUIRE(pad, "%s: pad is NULL (the entry without _pad takes no padding words)", who);                      \
+    DHZ_REQUIRE(nW > 0 && B_ % nW == 0, "%s: B_=%d is not a whole number of images of nW=%d windows", who, B_, nW)
+extern "C" int dhz_ps_attn_fwd_w_pad(const void* q, const void* k, const void* v, int ld, const uint8_t* idx, const float* bias,
+                                     const float* mask, const uint64_t* pad, void* out, int ldo, uint8_t* rank, int B_, int H, int nW, int d,
+                                     int win, int dtype, void* stream) {
+    DHZ_REQUIRE_WIN("dhz_ps_attn_fwd_w_pad", win);
+    if (win == 8) return dhz_ps_attn_fwd_dt_pad(q, k, v, ld, idx, bias, mask, pad, out, ldo, rank, B_, H, nW, d, dtype, stream);
+    DHZ_REQUIRE_PAD("dhz_ps_attn_fwd_w_pad");
+    const float scale = d > 0 ? 1.0f / sqrtf((float)d) : 0.f;
+    if (dtype == DHZ_F32)
+        return attn16_fwd<float, false>("dhz_ps_attn_fwd_w_pad", (const float*)q, (const float*)k, (const float*)v, ld, idx, bias, mask, (float*)out,
+                                        ldo, rank, B_, H, nW, d, scale, stream, pad);
+    if (dtype == DHZ_BF16)
+        return attn16_fwd<bf16s, false>("dhz_ps_attn_fwd_w_pad", (const bf16s*)q, (const bf16s*)k, (const bf16s*)v, ld, idx, bias, mask, (bf16s*)out,
+                                        ldo, rank, B_, H, nW, d, scale, stream, pad);
+    dhz_set_error("dhz_ps_attn_fwd_w_pad: unknown dtype %d", dtype);
+    return DHZ_EINVAL;
+}
+
+extern "C" int dhz_ps_attn_bwd_w_pad(const void* q, const void* k, const void* v, int ld, const float* bias, const float* mask,
+                                     const uint64_t* pad, const uint8_t* rank, const void* dout, int ldo, void* dq, void* dk, void* dv, int ldg,
+                                     float* dbias_part, int B_, int H, int nW, int d, int win, int dtype, void* stream) {
+    DHZ_REQUIRE_WIN("dhz_ps_attn_bwd_w_pad", win);
+    if (win == 8)
+        return dhz_ps_attn_bwd_dt_pad(q, k, v, ld, bias, mask, pad, rank, dout, ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW, d, dtype, stream);
+    DHZ_REQUIRE_PAD("dhz_ps_attn_bwd_w_pad");
+    const float scale = d > 0 ? 1.0f / sqrtf((float)d) : 0.f;
+    if (dtype == DHZ_F32)
+        return attn16_bwd<float, false>("dhz_ps_attn_bwd_w_pad", (const float*)q, (const float*)k, (const float*)v, ld, bias, mask, rank,
+                                        (const float*)dout, ldo, (float*)dq, (float*)dk, (float*)dv, ldg, dbias_part, B_, H, nW, d, scale, stream, pad);
+    if (dtype == DHZ_BF16)
+        return attn16_bwd<bf16s, false>("dhz_ps_attn_bwd_w_pad", (const bf16s*)q, (const bf16s*)k, (const bf16s*)v, ld, bias, mask, rank,
+                                        (const bf16s*)dout, ldo, (bf16s*)dq, (bf16s*)dk, (bf16s*)dv, ldg, dbias_part, B_, H, nW, d, scale, stream, pad);
+    dhz_set_error("dhz_ps_attn_bwd_w_pad: unknown dtype %d", dtype);
+    return DHZ_EINVAL;
+}
+#undef DHZ_REQUIRE_PAD
+
+extern "C" int dhz_pad_window_bits(const float* mask, uint64_t* bits, int B, int Himg, int Wimg, int H, int W, int win, void* stream) {
+    DHZ_REQUIRE_WIN("dhz_pad_window_bits", win);
+    DHZ_REQUIRE(mask && bits, "dhz_pad_window_bits: null pointer (mask, bits)");
+    DHZ_REQUIRE(B > 0 && H > 0 && W > 0 && H % win == 0 && W % win == 0, "dhz_pad_window_bits: B=%d, map H x W = %d x %d is no multiple of win=%d", B,
+                H, W, win);
+    DHZ_REQUIRE(Himg > 0 && Wimg > 0 && Himg % H == 0 && Wimg % W == 0,
+                "dhz_pad_window_bits: Himg x Wimg = %d x %d is no whole multiple of H x W = %d x %d (nearest resampling at a whole ratio only)", Himg,
+                Wimg, H, W);
+    const long long ntok = (long long)B * H * W;
+    DHZ_REQUIRE((ntok + 255) / 256 < (1ll << 31), "dhz_pad_window_bits: B H W = %lld tokens exceed the grid", ntok);
+    hipLaunchKernelGGL(pad_window_bits_kernel, dim3((unsigned)((ntok + 255) / 256)), dim3(256), 0, (hipStream_t)stream, mask, bits, Himg, Wimg, H,
+                       W, win_log2(win), ntok);
+    DHZ_CHECK_LAUNCH("dhz_pad_window_bits");
+    return DHZ_OK;
 }
 
 extern "C" int dhz_dense_attn_fwd_w(const float* q, const float* k, const float* v, int ld, const float* bias, const float* mask, float* out,

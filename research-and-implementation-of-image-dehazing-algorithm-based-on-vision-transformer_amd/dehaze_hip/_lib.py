@@ -148,6 +148,13 @@ SIGNATURES = {
     "dhz_shift_mask_w": [c_f, c_i, c_i, c_i, c_i, c_p],
     "dhz_bias_gather_w": [c_f, c_f, c_i, c_i, c_p],
     "dhz_bias_table_grad_w": [c_f, c_i, c_f, c_i, c_i, c_i, c_p],
+    # padding mask of any-size evaluation as one uint64 per window: the entry of the same name without `_pad` plus `pad` behind `mask`
+    "dhz_pad_window_bits": [c_f, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p],
+    "dhz_ps_attn_fwd_dt_pad": [c_f, c_f, c_f, c_i, c_p, c_f, c_f, c_p, c_f, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_p],
+    "dhz_ps_attn_bwd_dt_pad": [c_f, c_f, c_f, c_i, c_f, c_f, c_p, c_p, c_f, c_i, c_f, c_f, c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_p],
+    "dhz_ps_attn_fwd_w_pad": [c_f, c_f, c_f, c_i, c_p, c_f, c_f, c_p, c_f, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p],
+    "dhz_ps_attn_bwd_w_pad": [c_f, c_f, c_f, c_i, c_f, c_f, c_p, c_p, c_f, c_i, c_f, c_f, c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_p],
+    "dhz_fused_window_attn_fwd_pad": [c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_p, c_f, c_f, c_p, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_p],
     # dense 3x3 convolution of the UNet baseline on the channel-blocked layout: LeakyReLU in the Winograd store, weight gradient
     "dhz_winograd_conv3x3_act": [c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_p],
     "dhz_tokens_to_blocked8": [c_f, c_i, c_f, c_f, c_i, c_i, c_i, c_p],

@@ -41,6 +41,12 @@ ATTN_FUSED_P6 = __import__("os").environ.get("DHZ_FUSED_P6", "1") != "0"
 # C = 32 (planes in registers of the persistent workgroups) exists and is tested, but is not dispatched: its extra 50 registers cost the third
 # workgroup per CU (tools/bench_fused_p6.py: 101.5 -> 100.1 us training, 100.0 -> 96.0 inference at 128 x 128)
 ATTN_FUSED_P6_C = (64, 128)
+# Padding words (ops.PAD_BITS) in the fused forward's inference instances: the widths that keep six-term projections when the call carries
+# padding words; the others run the fp32-pipe instance.  Compile remarks (-Rpass-analysis=kernel-resource-usage, SAVE = 0, without / with
+# words): C = 128 208 / 208 bytes of scratch per lane; C = 64 12 / 28 at 167 VGPRs (its cap for three workgroups per CU) against 155 / 157
+# VGPRs and no scratch on the fp32 pipe.  Measured on the 1664 x 1664 canvas (tools/bench_any_resolution.py --pad-p6, model forward, ms,
+# mask-free 38.7): C = 64 six-term 38.8, fp32-pipe 39.8 - the sixteen more bytes of scratch cost less than the fp32 pipe
+ATTN_FUSED_PAD_P6_C = (64, 128)
 LEFF_FUSED = True           # False forces the kernel chain everywhere
 LEFF_FUSED_C = (32, 64)     # widths that take the fused forward
 # ... C = 64 only below this many tokens when the chain's GEMMs run in the six-term form (tools/bench_leff.py, bs 32, forward with the
@@ -157,8 +163,14 @@ def _n6(C):
     return 8 * 3 * 512 if C == 32 else (C // 32) * ((C // 64) * 36 + (C // 16) * 3) * 512
 
 
-def stage_block_operands(entries, device):
-    """entries: [(table or None, H, (wq, wk, wv, wo) or None, C)] in execution order (Uformer.forward builds it)."""
+def _use6(C, pad):
+    """the fused forward's weight products six-term on the bf16 matrix pipe (pad: the call carries padding words)"""
+    return ATTN_FUSED_P6 and C in ATTN_FUSED_P6_C and (not pad or C in ATTN_FUSED_PAD_P6_C)
+
+
+def stage_block_operands(entries, device, pad=False):
+    """entries: [(table or None, H, (wq, wk, wv, wo) or None, C)] in execution order (Uformer.forward builds it); pad: the forward carries
+    padding words."""
     STAGED_BIAS.clear()
     STAGED_PREPACK.clear()
     STAGED_PACK6.clear()
@@ -178,7 +190,7 @@ def stage_block_operands(entries, device):
                       ints([H for (_, H), _ in part]), len(part), _stream())
         for (t, _), o in zip(tabs, outs):
             STAGED_BIAS[id(t)] = (t, o)          # (the parameter itself rides along: its id cannot be reused while the entry lives)
-    p6 = lambda C: ATTN_FUSED_P6 and C in ATTN_FUSED_P6_C
+    p6 = lambda C: _use6(C, pad)
     packs6 = [(w, C) for _, _, w, C in entries if w is not None and p6(C)]
     if packs6:
         n6 = _n6
@@ -223,16 +235,18 @@ def _bias_tile(table, H, dev):
 
 
 # ----------------------------------------------------------------------------- attention branch: forward / backward as functions
-def _attn_fused_fwd(train, x, gamma, beta, wq, bq, wk, bk, wv, bv, wo, bo, table, idx, mask, dscale, Hres, Wres, shift, H):
-    """one kernel: LN, roll, partition, QKV, ProbSparse core, out-projection, reverse, residual (csrc/fused_attn.hip)"""
+def _attn_fused_fwd(train, x, gamma, beta, wq, bq, wk, bk, wv, bv, wo, bo, table, idx, mask, dscale, Hres, Wres, shift, H, pad=None):
+    """one kernel: LN, roll, partition, QKV, ProbSparse core, out-projection, reverse, residual (csrc/fused_attn.hip); pad: the padding
+    words of the B nW windows (inference only: dhz_fused_window_attn_fwd_pad)"""
     _require_gpu(x, gamma, beta, wq, wo, table, idx, mask, dscale)
+    assert pad is None or not train, "padding words under autograd: LeWinTransformerBlock.forward runs ops.ps_window_attention"
     x = x.contiguous()
     B, L, C = x.shape
     assert L == Hres * Wres and C == 32 * H and C in SUPPORTED_C
     dev = x.device
     T = B * L
     f32 = dict(device=dev, dtype=torch.float32)
-    use6 = ATTN_FUSED_P6 and C in ATTN_FUSED_P6_C
+    use6 = _use6(C, pad is not None)
     n6 = _n6(C)
     wqkv_p = wo_p = None
     will_fuse_bwd = train and C in _fused_bwd_widths() and x.dtype == torch.float32      # (the fused backward reads the fp32 fragment pack)
@@ -269,9 +283,15 @@ def _attn_fused_fwd(train, x, gamma, beta, wq, bq, wk, bk, wv, bv, wo, bo, table
         rank = torch.empty(((T // NTOK) * H * NTOK,), device=dev, dtype=torch.uint8)
     entry = "dhz_fused_window_attn_fwd6" if use6 else "dhz_fused_window_attn_fwd"
     ev = ops._timed("dhz_fused_window_attn_fwd")
-    _lib.call(entry, _p(x), _p(gamma), _p(beta), _p(wqkv_p), _p(bqkv), _p(wo_p), _p(bo), _p(idx),
-              _p(bias), _p(mask), _p(dscale), _p(out), _p(xn), _p(qkv), _p(cx), _p(stats), _p(rank), B, Hres, Wres, C,
-              shift, _stream())
+    if pad is not None:
+        assert pad.is_cuda and pad.dtype == torch.int64 and pad.numel() == T // NTOK and pad.is_contiguous(), \
+            f"padding words {tuple(pad.shape)} {pad.dtype} on {pad.device}"
+        _lib.call("dhz_fused_window_attn_fwd_pad", 1 if use6 else 0, _p(x), _p(gamma), _p(beta), _p(wqkv_p), _p(bqkv), _p(wo_p), _p(bo), _p(idx),
+                  _p(bias), _p(mask), _p(pad), _p(dscale), _p(out), B, Hres, Wres, C, shift, _stream())
+    else:
+        _lib.call(entry, _p(x), _p(gamma), _p(beta), _p(wqkv_p), _p(bqkv), _p(wo_p), _p(bo), _p(idx),
+                  _p(bias), _p(mask), _p(dscale), _p(out), _p(xn), _p(qkv), _p(cx), _p(stats), _p(rank), B, Hres, Wres, C,
+                  shift, _stream())
     ops._timed_end(ev, T // NTOK, C)
     rec = None
     params = (wq, bq, wk, bk, wv, bv, wo, bo, gamma, beta, table)
@@ -285,9 +305,11 @@ def _attn_fused_fwd(train, x, gamma, beta, wq, bq, wk, bk, wv, bv, wo, bo, table
     return out, rec
 
 
-def _attn_chain_fwd(train, x, gamma, beta, wq, bq, wk, bk, wv, bv, wo, bo, table, idx, mask, dscale, Hres, Wres, shift, H):
-    """dhz_ln_partition_fwd -> QKV GEMM -> dhz_ps_attn_fwd -> out-projection GEMM with the residual epilogue (K4 inside the GEMM)"""
+def _attn_chain_fwd(train, x, gamma, beta, wq, bq, wk, bk, wv, bv, wo, bo, table, idx, mask, dscale, Hres, Wres, shift, H, pad=None):
+    """dhz_ln_partition_fwd -> QKV GEMM -> dhz_ps_attn_fwd -> out-projection GEMM with the residual epilogue (K4 inside the GEMM); pad: the
+    padding words of the B nW windows (inference only: dhz_ps_attn_fwd_dt_pad)"""
     _require_gpu(x, gamma, beta, wq, wo, table, idx, mask, dscale)
+    assert pad is None or not train, "padding words under autograd: LeWinTransformerBlock.forward runs ops.ps_window_attention"
     x = x.contiguous()
     B, L, C = x.shape
     d = C // H
@@ -303,7 +325,7 @@ def _attn_chain_fwd(train, x, gamma, beta, wq, bq, wk, bk, wv, bv, wo, bo, table
     bias = _bias_tile(table, H, dev)
     cx = torch.empty((T, C), device=dev, dtype=x.dtype)
     rank = torch.empty(((T // NTOK) * H * NTOK,), device=dev, dtype=torch.uint8)
-    ops.ps_attn_fwd_launch(qkv, idx, bias, mask, cx, rank, T // NTOK, H, d)
+    ops.ps_attn_fwd_launch(qkv, idx, bias, mask, cx, rank, T // NTOK, H, d, pad=pad, nW=(Hres // 8) * (Wres // 8))
     out = ops.gemm_fwd_res(cx, wo, bo, x.view(T, C), dscale, B, Hres, Wres, shift, True).view(B, L, C)
     rec = None
     if train:
@@ -398,14 +420,26 @@ def use_fused_attn(C, dtype, heads, HW):
     return ENABLED and dtype == torch.float32 and C == 32 * heads and (C in (32, 64) or (C == 128 and fused_c128_ok(HW)))
 
 
+def takes_node(block, tensor_mask=False, pad=False):
+    """a LeWin block whose attention branch runs as one autograd node (attn_branch / block) - the ONE predicate of LeWinTransformerBlock.forward
+    and Uformer._stage_block_operands.  tensor_mask: the block was handed a materialised [B nW, N, N] attention mask (CPU tensors, the dense
+    twin, DHZ_PAD_BITS=0), which only the ops-level kernel chain (ops.ps_window_attention under autograd) takes.  pad: the mask travels as
+    padding words - they do not exclude a block from the node in a no-gradient forward (the fused kernel's inference instances and the
+    chain forward take them); under autograd such a block runs the tensor route's kernel sequence with the `_pad` entries, so that its
+    results and gradients are that route's, bit for bit."""
+    h = block.num_heads
+    return block.attn.variant == "probsparse" and block.win_size == 8 and block.dim in (16 * h, 32 * h, 64 * h) and not tensor_mask \
+        and not (pad and torch.is_grad_enabled())
+
+
 class _AttnNode(Function):
     """the attention branch as one autograd node; FUSED selects the forward (the backward follows the record)"""
 
     @staticmethod
-    def forward(ctx, fused, x, gamma, beta, wq, bq, wk, bk, wv, bv, wo, bo, table, idx, mask, dscale, Hres, Wres, shift, H, grad_mode):
+    def forward(ctx, fused, x, gamma, beta, wq, bq, wk, bk, wv, bv, wo, bo, table, idx, mask, dscale, Hres, Wres, shift, H, pad, grad_mode):
         train = grad_mode and any(ctx.needs_input_grad)      # grad mode reads False inside Function.forward: passed in
         out, rec = (_attn_fused_fwd if fused else _attn_chain_fwd)(train, x, gamma, beta, wq, bq, wk, bk, wv, bv, wo, bo, table, idx, mask,
-                                                                   dscale, Hres, Wres, shift, H)
+                                                                   dscale, Hres, Wres, shift, H, pad)
         if rec is not None:
             ctx.save_for_backward(*rec.saved)
             rec.saved = ()
@@ -418,21 +452,23 @@ class _AttnNode(Function):
         rec.saved = ctx.saved_tensors
         g = _attn_bwd(rec, dout)
         rec.saved = ()
-        return (None,) + g + (None,) * 8
+        return (None,) + g + (None,) * 9
 
 
-def fused_attn_branch(x, norm, layer, table, idx, mask, dscale, Hres, Wres, shift, heads):
+def fused_attn_branch(x, norm, layer, table, idx, mask, dscale, Hres, Wres, shift, heads, pad=None):
     """x: [B,L,C]; norm: nn.LayerNorm; layer: AttentionLayer (query/key/value/out projections)."""
     q, k, v, o = layer.query_projection, layer.key_projection, layer.value_projection, layer.out_projection
     return _AttnNode.apply(True, x, norm.weight, norm.bias, q.weight, q.bias, k.weight, k.bias, v.weight, v.bias,
-                           o.weight, o.bias, table, idx, mask, dscale, Hres, Wres, shift, heads, torch.is_grad_enabled())
+                           o.weight, o.bias, table, idx, mask, dscale, Hres, Wres, shift, heads, pad, torch.is_grad_enabled())
 
 
-def attn_branch(x, norm, layer, table, idx, mask, dscale, Hres, Wres, shift, heads):
-    """Dispatch: fused kernel where it wins (measured, tools/bench_fused.py), kernel chain elsewhere."""
+def attn_branch(x, norm, layer, table, idx, mask, dscale, Hres, Wres, shift, heads, pad=None):
+    """Dispatch: fused kernel where it wins (measured, tools/bench_fused.py), kernel chain elsewhere.  mask: the [nW, 64, 64] shift mask or
+    None; pad: the [B nW] padding words of any-size evaluation (ops.pad_window_bits) or None (no-gradient forwards only)."""
     q, k, v, o = layer.query_projection, layer.key_projection, layer.value_projection, layer.out_projection
-    return _AttnNode.apply(use_fused_attn(x.shape[-1], x.dtype, heads, Hres * Wres), x, norm.weight, norm.bias, q.weight, q.bias, k.weight, k.bias, v.weight,
-                           v.bias, o.weight, o.bias, table, idx, mask, dscale, Hres, Wres, shift, heads, torch.is_grad_enabled())
+    return _AttnNode.apply(use_fused_attn(x.shape[-1], x.dtype, heads, Hres * Wres), x, norm.weight, norm.bias, q.weight, q.bias,
+                           k.weight, k.bias, v.weight, v.bias, o.weight, o.bias, table, idx, mask, dscale, Hres, Wres, shift, heads, pad,
+                           torch.is_grad_enabled())
 
 
 # ----------------------------------------------------------------------------- LeFF branch
@@ -635,8 +671,8 @@ BLOCK_NODE = True       # False: two nodes per block (attn_branch, leff_branch) 
 class _BlockNode(Function):
     """attention branch + LeFF branch of one LeWin block (M1:839-873).  Forward = the two branch forwards; backward = the two branch
     backwards with the gradient between them in the attention branch's window order whenever that branch runs the kernel chain
-    backward (module docstring).  Argument layout: (fused, x, 18 attention arguments, 11 LeFF arguments, grad_mode)."""
-    NA, NL = 18, 11
+    backward (module docstring).  Argument layout: (fused, x, 19 attention arguments, 11 LeFF arguments, grad_mode)."""
+    NA, NL = 19, 11
 
     @staticmethod
     def forward(ctx, fused, x, *args):
@@ -670,16 +706,16 @@ class _BlockNode(Function):
             gl = _leff_bwd(rl, dout, dx_window=shift if windowed else None)
             ga = _attn_bwd(ra, gl[0], windowed=windowed)
         ra.saved = rl.saved = ()
-        #      fused   x       attention parameters (11)   idx, mask, dscale, Hres, Wres, shift, H      LeFF parameters (8)   dscale, Hres, Wres, grad_mode
-        return (None, ga[0]) + ga[1:] + (None,) * 7 + gl[1:] + (None,) * 4
+        #      fused   x       attention parameters (11)   idx, mask, dscale, Hres, Wres, shift, H, pad      LeFF parameters (8)   dscale, Hres, Wres, grad_mode
+        return (None, ga[0]) + ga[1:] + (None,) * 8 + gl[1:] + (None,) * 4
 
 
-def block(x, norm1, layer, table, idx, mask, dscale_attn, Hres, Wres, shift, heads, norm2, mlp, dscale_mlp):
-    """both branches of a LeWin block with a LeFF token mixer as one autograd node"""
+def block(x, norm1, layer, table, idx, mask, dscale_attn, Hres, Wres, shift, heads, norm2, mlp, dscale_mlp, pad=None):
+    """both branches of a LeWin block with a LeFF token mixer as one autograd node (mask / pad as in attn_branch)"""
     q, k, v, o = layer.query_projection, layer.key_projection, layer.value_projection, layer.out_projection
     return _BlockNode.apply(use_fused_attn(x.shape[-1], x.dtype, heads, Hres * Wres), x,
                             norm1.weight, norm1.bias, q.weight, q.bias, k.weight, k.bias, v.weight, v.bias, o.weight, o.bias, table, idx,
-                            mask, dscale_attn, Hres, Wres, shift, heads,
+                            mask, dscale_attn, Hres, Wres, shift, heads, pad,
                             norm2.weight, norm2.bias, mlp.linear1[0].weight, mlp.linear1[0].bias, mlp.dwconv[0].weight, mlp.dwconv[0].bias,
                             mlp.linear2[0].weight, mlp.linear2[0].bias, dscale_mlp, Hres, Wres,
                             torch.is_grad_enabled())

@@ -127,9 +127,10 @@ class AttentionLayer(nn.Module):
         self.n_heads = n_heads
         self.mix = mix
 
-    def forward(self, queries, keys, values, table, SW_mask, attn_mask=None, idx=None):
+    def forward(self, queries, keys, values, table, SW_mask, attn_mask=None, idx=None, pad=None, nW=None):
         """queries (= keys = values): [B_, N, C] window tokens, N = 64 (8 x 8 windows) or 16 (4 x 4).  `table` is the
-        [(2 win - 1)^2, H] bias table (or None when options.is_relative_position_bias is False); returns ([B_,N,C], None)."""
+        [(2 win - 1)^2, H] bias table (or None when options.is_relative_position_bias is False); returns ([B_,N,C], None).
+        pad: [B_] padding words (ops.pad_window_bits) with nW windows per image, beside the [nW, N, N] shift mask in SW_mask."""
         assert keys is queries and values is queries, "self-attention only (M1:413 passes x, x, x)"
         B_, N, C = queries.shape
         H = self.n_heads
@@ -140,7 +141,7 @@ class AttentionLayer(nn.Module):
             idx = draw_sample_index(1, N)[0]
         if idx.device != qkv.device or idx.dtype != torch.uint8:
             idx = idx.to(device=qkv.device, dtype=torch.uint8)
-        ctx = ops.ps_window_attention(qkv, table, idx.contiguous(), SW_mask, H, C // H)
+        ctx = ops.ps_window_attention(qkv, table, idx.contiguous(), SW_mask, H, C // H, pad, nW)
         out = ops.linear_tokens(ctx, self.out_projection.weight, self.out_projection.bias)
         return out.view(B_, N, C), None
 
@@ -286,13 +287,14 @@ class WindowAttention(nn.Module):
         trunc_normal_(self.relative_position_bias_table, std=.02)
         self.softmax = nn.Softmax(dim=-1)
 
-    def forward(self, x, attn_kv=None, mask=None, idx=None):
+    def forward(self, x, attn_kv=None, mask=None, idx=None, pad=None, nW=None):
         check_window(self.win_size)
         if self.variant == "probsparse":
             import options                                         # read at call time, like ATT:227
             table = self.relative_position_bias_table if options.is_relative_position_bias else None
-            out, _ = self.ProbSpare(x, x, x, table, mask, idx=idx)
+            out, _ = self.ProbSpare(x, x, x, table, mask, idx=idx, pad=pad, nW=nW)
             return out
+        assert pad is None, "padding words: ProbSparse attention only (the dense twin takes the mask tensor)"
         return self._dense(x, mask)
 
     def _dense(self, x, mask):
@@ -384,6 +386,7 @@ class LeWinTransformerBlock(nn.Module):
             else LeFF(dim, int(dim * mlp_ratio), act_layer=act_layer, drop=drop)                              # M1:778-779
         self._mask_cache = {}
         self._staged_idx = None      # set by Uformer.forward (one batched host draw per model forward)
+        self._staged_pad = None      # set by Uformer.forward with a mask: the padding words of this block's resolution
         self._staged_scales = None   # set by Uformer.forward on the GPU: the two DropPath vectors of this block
 
     def extra_repr(self):
@@ -408,7 +411,14 @@ class LeWinTransformerBlock(nn.Module):
         B, L, C = x.shape
         H = W = int(math.sqrt(L))
         attn_mask = None
-        if mask is not None:                                                 # input-mask path, M1:791-800
+        pad, self._staged_pad = self._staged_pad, None
+        if mask is None:
+            pad = None
+        elif pad is None and ops.PAD_BITS and x.is_cuda and self.attn.variant == "probsparse" and ops.pad_bits_cover(mask, H, W):
+            pad = ops.pad_window_bits(mask, H, W, self.win_size)             # (a block called on its own: Uformer.forward stages them)
+        if pad is not None and torch.is_grad_enabled():
+            ops.warn_pad_under_grad()
+        if mask is not None and pad is None:                                 # input-mask path as a tensor, M1:791-800: CPU, dense twin, DHZ_PAD_BITS=0
             im = F.interpolate(mask, size=(H, W)).permute(0, 2, 3, 1)
             am = window_partition(im, self.win_size).view(-1, self.win_size * self.win_size)
             am = am.unsqueeze(2) * am.unsqueeze(1)
@@ -418,7 +428,7 @@ class LeWinTransformerBlock(nn.Module):
             attn_mask = attn_mask + sm if attn_mask is not None else sm
         idx, self._staged_idx = self._staged_idx, None
 
-        if self.attn.variant == "probsparse" and self.win_size == 8 and C in (16 * self.num_heads, 32 * self.num_heads, 64 * self.num_heads) and mask is None:
+        if C == self.dim and fused.takes_node(self, tensor_mask=mask is not None and pad is None, pad=pad is not None):
             # attention branch as ONE autograd node: the fused kernel (LN, roll, partition, QKV, ProbSparse core,
             # out-proj, residual) where it wins, the kernel chain elsewhere; hand-sequenced backward in both cases
             import options
@@ -430,13 +440,14 @@ class LeWinTransformerBlock(nn.Module):
             if fused.BLOCK_NODE and self.token_mlp == 'leff':
                 # both branches as one node: the gradient between them never takes the token-order detour (fused.block)
                 return fused.block(x, self.norm1, self.attn.ProbSpare, table, idx.contiguous(), attn_mask, self._scale(x), H, W,
-                                   self.shift_size, self.num_heads, self.norm2, self.mlp, self._scale(x))
+                                   self.shift_size, self.num_heads, self.norm2, self.mlp, self._scale(x), pad)
             x = fused.attn_branch(x, self.norm1, self.attn.ProbSpare, table, idx.contiguous(), attn_mask,
-                                  self._scale(x), H, W, self.shift_size, self.num_heads)
+                                  self._scale(x), H, W, self.shift_size, self.num_heads, pad)
         else:
             # the kernel chain under autograd, for either window (the fused single-kernel paths above are 8 x 8 only)
             xw = ops.ln_partition(x, self.norm1.weight, self.norm1.bias, H, W, self.shift_size, self.win_size)   # LN+roll+partition
-            aw = self.attn(xw.view(-1, self.win_size * self.win_size, C), mask=attn_mask, idx=idx)
+            aw = self.attn(xw.view(-1, self.win_size * self.win_size, C), mask=attn_mask, idx=idx, pad=pad,
+                           nW=(H // self.win_size) * (W // self.win_size))
             x = ops.reverse_residual(aw.reshape(-1, C), x, self._scale(x), H, W, self.shift_size, self.win_size)  # reverse+unroll+res
         if self.token_mlp == 'ffn':
             # Mlp branch (norm2 -> fc1 -> GELU -> fc2 -> residual) as one autograd node
@@ -744,6 +755,24 @@ class Uformer(nn.Module):
             for i, j in enumerate(run):
                 blocks[j]._staged_idx = idx[i]
 
+    def _stage_pad_bits(self, x, mask):
+        """The padding mask of any-size evaluation as one 64-bit word per window (ops.pad_window_bits): one word vector per distinct
+        (resolution, window) of this forward - at most five launches - handed to the blocks, instead of a [B nW, N, N] fp32 tensor built
+        by every block.  Tensor route (the blocks build the tensor): no mask, CPU tensors, the dense twin, DHZ_PAD_BITS=0."""
+        blocks = [b for st in self.stages() for b in st.blocks]
+        for b in blocks:
+            b._staged_pad = None
+        if mask is None or not (ops.PAD_BITS and x.is_cuda and self.variant == "probsparse"):
+            return False
+        Himg, Wimg = x.shape[-2], x.shape[-1]
+        keys = [(Himg // sc, Wimg // sc, b.win_size) for st, sc in zip(self.stages(), [1, 2, 4, 8, 16, 8, 4, 2, 1]) for b in st.blocks]
+        if not all(ops.pad_bits_cover(mask, H, W) for H, W, _ in keys):
+            return False                       # (a mask of another size than the image: the blocks resample it with F.interpolate)
+        words = {key: ops.pad_window_bits(mask, *key) for key in dict.fromkeys(keys)}
+        for b, key in zip(blocks, keys):
+            b._staged_pad = words[key]
+        return True
+
     def _stage_drop_path(self, x):
         """All DropPath keep/keep_prob vectors of one training forward (two per block with drop_prob > 0) from ONE
         bernoulli launch + one division instead of two tiny launches per residual (~70 launches of ~4 us per step).  GPU
@@ -769,9 +798,10 @@ class Uformer(nn.Module):
         for i, b in enumerate(live):
             b._staged_scales = [r[2 * i], r[2 * i + 1]]
 
-    def _stage_block_operands(self, x, mask):
+    def _stage_block_operands(self, x, mask, pad=False):
         """The relative-position bias tiles of all blocks and the fragment-ordered weights of the fused attention blocks of this forward in
-        ONE launch each (fused.stage_block_operands) - 26 launches of ~4.5 us per training step otherwise."""
+        ONE launch each (fused.stage_block_operands) - 26 launches of ~4.5 us per training step otherwise.  pad: the mask travels as
+        padding words (_stage_pad_bits); a mask that the blocks turn into a tensor keeps them off the nodes that consume these operands."""
         if not x.is_cuda or self.variant != "probsparse":
             return
         import options
@@ -781,8 +811,7 @@ class Uformer(nn.Module):
         entries = []
         for st, sc in zip(self.stages(), scales + [1]):
             for b in st.blocks:
-                if b.attn.variant != "probsparse" or b.win_size != 8 or mask is not None \
-                        or b.dim not in (16 * b.num_heads, 32 * b.num_heads, 64 * b.num_heads):
+                if not fused.takes_node(b, tensor_mask=mask is not None and not pad, pad=pad):
                     continue
                 lay = b.attn.ProbSpare
                 fused_fwd = fused.use_fused_attn(b.dim, self.act_dtype, b.num_heads, (Himg // sc) * (Wimg // sc))
@@ -790,7 +819,7 @@ class Uformer(nn.Module):
                     if fused_fwd else None
                 entries.append((b.attn.relative_position_bias_table if rel else None, b.num_heads, w, b.dim))
         if entries:
-            fused.stage_block_operands(entries, x.device)
+            fused.stage_block_operands(entries, x.device, pad)
 
     def forward(self, x, mask=None):
         for st in self.stages():     # before anything runs: a window the kernels do not have is an error, not a late surprise
@@ -799,7 +828,7 @@ class Uformer(nn.Module):
         ops.sync_shadows()          # derived weight copies (bf16 / split planes) follow parameters written outside the optimizer
         self._stage_sample_indices(x.device)
         self._stage_drop_path(x)
-        self._stage_block_operands(x, mask)
+        self._stage_block_operands(x, mask, self._stage_pad_bits(x, mask))
         self.input_proj.out_dtype = self.act_dtype if x.is_cuda else torch.float32
         y = self.pos_drop(self.input_proj(x))
         if self.act_dtype == torch.bfloat16 and y.is_cuda and y.dtype != torch.bfloat16:

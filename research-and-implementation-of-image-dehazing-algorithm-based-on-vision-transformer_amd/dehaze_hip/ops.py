@@ -489,10 +489,67 @@ def gemm_dgrad(dy, W, row_scale=None):
 
 
 # ----------------------------------------------------------------------------- K3 / K7
-def ps_attn_fwd_launch(qkv, idx, bias, mask, out, rank, B_, H, d, N=NTOK):
+# The padding mask of any-size evaluation (M1:791-800) travels as ONE 64-bit word per window (bit i: token i is padding) instead of a
+# [B nW, N, N] fp32 tensor; the kernels form the -100 term from it in registers.  DHZ_PAD_BITS=0 restores the tensor everywhere (A/B).
+PAD_BITS = os.environ.get("DHZ_PAD_BITS", "1") != "0"
+
+
+def pad_bits_cover(mask, H, W):
+    """padding words exist for this mask on an H x W map: [B, 1, Himg, Wimg] with Himg, Wimg whole multiples of H, W (what the model's
+    stages give).  Any other mask - another ratio, more channels - keeps the tensor route, which resamples with F.interpolate."""
+    return mask.dim() == 4 and mask.shape[1] == 1 and mask.shape[2] % H == 0 and mask.shape[3] % W == 0
+
+
+_WARNED_PAD_GRAD = False
+
+
+def warn_pad_under_grad():
+    """once: a masked forward with gradients enabled does not reach the fused window-attention kernel"""
+    global _WARNED_PAD_GRAD
+    if not _WARNED_PAD_GRAD:
+        _WARNED_PAD_GRAD = True
+        import warnings
+        warnings.warn("dehaze_hip: a forward with a padding mask runs with gradients enabled: its blocks take the unfused kernel chain "
+                      "(with padding words); run any-size evaluation under torch.no_grad() to reach the fused window-attention kernel",
+                      stacklevel=3)
+
+
+def pad_window_bits(mask, H, W, win=8):
+    """mask [B, 1, Himg, Wimg] fp32 -> [B (H / win) (W / win)] int64 words (the bit pattern of a uint64) for a block that works on an
+    H x W map: bit i of word b = (window_partition(F.interpolate(mask, (H, W)))[b, i] != 0), the windows in window_partition's order
+    (dhz_pad_window_bits; Himg % H == 0 and Wimg % W == 0)"""
+    _win_of(win * win)
+    _require_gpu(mask)
+    assert mask.dim() == 4 and mask.shape[1] == 1, f"padding mask {tuple(mask.shape)}: [B, 1, Himg, Wimg] expected"
+    m = mask.contiguous().float()
+    B, _, Himg, Wimg = m.shape
+    bits = torch.empty((B * (H // win) * (W // win),), device=m.device, dtype=torch.int64)
+    _lib.call("dhz_pad_window_bits", _p(m), _p(bits), B, Himg, Wimg, H, W, win, _stream())
+    return bits
+
+
+def _pad_nw(pad, mask, B_, nW):
+    """windows per image of a launch with padding words: the shift mask's, else the caller's, else one image"""
+    assert pad.is_cuda and pad.dtype == torch.int64 and pad.numel() == B_ and pad.is_contiguous(), \
+        f"padding words {tuple(pad.shape)} {pad.dtype} on {pad.device} for {B_} windows"
+    return mask.shape[0] if mask is not None else (nW or B_)
+
+
+def ps_attn_fwd_launch(qkv, idx, bias, mask, out, rank, B_, H, d, N=NTOK, pad=None, nW=None):
     """dhz_ps_attn_fwd_dt (N = 64) / dhz_ps_attn_fwd_w (N = 16) on a packed [T, 3C] buffer (columns [Q | K | V]), inside bench.py's
-    timing bracket"""
+    timing bracket; pad: the padding words of the B_ windows (dhz_ps_attn_fwd_dt_pad / dhz_ps_attn_fwd_w_pad), nW: windows per image"""
     C, es, base = H * d, qkv.element_size(), qkv.data_ptr()
+    if pad is not None:
+        nW = _pad_nw(pad, mask, B_, nW)
+        ev = _timed("dhz_ps_attn_fwd")
+        if N == NTOK:
+            _lib.call("dhz_ps_attn_fwd_dt_pad", base, base + es * C, base + 2 * es * C, 3 * C, _p(idx), _p(bias), _p(mask), _p(pad), _p(out), C,
+                      _p(rank), B_, H, nW, d, _dt(qkv), _stream())
+        else:
+            _lib.call("dhz_ps_attn_fwd_w_pad", base, base + es * C, base + 2 * es * C, 3 * C, _p(idx), _p(bias), _p(mask), _p(pad), _p(out), C,
+                      _p(rank), B_, H, nW, d, _win_of(N), _dt(qkv), _stream())
+        _timed_end(ev, B_ * H * 4 * N * d * es)
+        return
     nW = mask.shape[0] if mask is not None else 1
     ev = _timed("dhz_ps_attn_fwd")
     if N == NTOK:
@@ -504,9 +561,19 @@ def ps_attn_fwd_launch(qkv, idx, bias, mask, out, rank, B_, H, d, N=NTOK):
     _timed_end(ev, B_ * H * 4 * N * d * es)
 
 
-def ps_attn_bwd_launch(qkv, dqkv, bias, mask, rank, dout, dpart, B_, H, d, N=NTOK):
-    """dhz_ps_attn_bwd_dt (N = 64) / dhz_ps_attn_bwd_w (N = 16): packed qkv / dqkv [T, 3C]"""
+def ps_attn_bwd_launch(qkv, dqkv, bias, mask, rank, dout, dpart, B_, H, d, N=NTOK, pad=None, nW=None):
+    """dhz_ps_attn_bwd_dt (N = 64) / dhz_ps_attn_bwd_w (N = 16): packed qkv / dqkv [T, 3C]; pad / nW as in ps_attn_fwd_launch
+    (dhz_ps_attn_bwd_dt_pad / dhz_ps_attn_bwd_w_pad)"""
     C, es, base, gb = H * d, qkv.element_size(), qkv.data_ptr(), dqkv.data_ptr()
+    if pad is not None:
+        nW = _pad_nw(pad, mask, B_, nW)
+        if N == NTOK:
+            _lib.call("dhz_ps_attn_bwd_dt_pad", base, base + es * C, base + 2 * es * C, 3 * C, _p(bias), _p(mask), _p(pad), _p(rank), _p(dout), C,
+                      gb, gb + es * C, gb + 2 * es * C, 3 * C, _p(dpart), B_, H, nW, d, _dt(qkv), _stream())
+        else:
+            _lib.call("dhz_ps_attn_bwd_w_pad", base, base + es * C, base + 2 * es * C, 3 * C, _p(bias), _p(mask), _p(pad), _p(rank), _p(dout), C,
+                      gb, gb + es * C, gb + 2 * es * C, 3 * C, _p(dpart), B_, H, nW, d, _win_of(N), _dt(qkv), _stream())
+        return
     nW = mask.shape[0] if mask is not None else 1
     if N == NTOK:
         _lib.call("dhz_ps_attn_bwd_dt", base, base + es * C, base + 2 * es * C, 3 * C, _p(bias), _p(mask), _p(rank), _p(dout), C,
@@ -545,10 +612,11 @@ class _PSWindowAttention(Function):
     qkv   : [T, 3C] (T = B_*N window-ordered tokens; columns [Q | K | V], each [H, d])
     table : [(2 win - 1)^2, H] relative position bias table, or None (options.is_relative_position_bias False)
     idx   : [N, u] uint8 sampled keys ([64, 25] for 8 x 8 windows, [16, 15] for 4 x 4: N is taken from it);  mask: [nW, N, N] or None
+    pad   : [B_] int64 padding words (pad_window_bits) or None; nW: windows per image (with pad and without mask)
     """
 
     @staticmethod
-    def forward(ctx, qkv, table, idx, mask, H, d):
+    def forward(ctx, qkv, table, idx, mask, H, d, pad=None, nW=None):
         _require_gpu(qkv, table, idx, mask)
         T, C3 = qkv.shape
         C = H * d
@@ -559,29 +627,29 @@ class _PSWindowAttention(Function):
         out = torch.empty((T, C), device=qkv.device, dtype=qkv.dtype)
         rank = torch.empty((B_ * H * N,), device=qkv.device, dtype=torch.uint8)
         bias = bias_tile(table, H, N) if table is not None else None
-        ps_attn_fwd_launch(qkv, idx, bias, mask, out, rank, B_, H, d, N)
-        ctx.save_for_backward(qkv, bias, mask, rank)
-        ctx.dims = (B_, H, d, N)
+        ps_attn_fwd_launch(qkv, idx, bias, mask, out, rank, B_, H, d, N, pad, nW)
+        ctx.save_for_backward(qkv, bias, mask, rank, pad)
+        ctx.dims = (B_, H, d, N, nW)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        qkv, bias, mask, rank = ctx.saved_tensors
-        B_, H, d, N = ctx.dims
+        qkv, bias, mask, rank, pad = ctx.saved_tensors
+        B_, H, d, N, nW = ctx.dims
         dout = dout.contiguous()
         dqkv = torch.empty_like(qkv)
         dpart, dtable = None, None
         parts = _lib.load().dhz_ps_attn_bwd_parts_d(B_, H, d) if N == NTOK else _lib.load().dhz_ps_attn_bwd_parts_w(B_, H, d, _win_of(N))
         if bias is not None:
             dpart = torch.empty((parts, N, N), device=qkv.device, dtype=torch.float32)
-        ps_attn_bwd_launch(qkv, dqkv, bias, mask, rank, dout, dpart, B_, H, d, N)
+        ps_attn_bwd_launch(qkv, dqkv, bias, mask, rank, dout, dpart, B_, H, d, N, pad, nW)
         if bias is not None:
             dtable = bias_table_grad(dpart, parts, H, N)
-        return dqkv, dtable, None, None, None, None
+        return dqkv, dtable, None, None, None, None, None, None
 
 
-def ps_window_attention(qkv, table, idx, mask, H, d):
-    return _PSWindowAttention.apply(qkv, table, idx, mask, H, d)
+def ps_window_attention(qkv, table, idx, mask, H, d, pad=None, nW=None):
+    return _PSWindowAttention.apply(qkv, table, idx, mask, H, d, pad, nW)
 
 
 def ps_window_attention_rank(qkv, table, idx, mask, H, d):
