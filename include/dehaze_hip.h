@@ -220,6 +220,11 @@ int dhz_conv4s2_fwd(const float* x, const float* wp, const float* bias, float* y
 int dhz_conv4s2_dgrad(const float* dy, const float* wq, float* dx, int B, int H, int W, int Cin, int Cout, void* stream);
 int dhz_conv4s2_wgrad(const float* dy, const float* x, float* dwp, float* db, int B, int H, int W, int Cin, int Cout,
                       void* stream);
+/*     dhz_conv4s2_tile: which tile instance <WM, WN> (32 WM rows x 32 WN columns per workgroup) the entry above runs for this shape
+ *     under the current dhz_set_reserved_cus / dhz_set_deterministic state, as 10 WM + WN.  mode 1 = forward, 2 = backward-data
+ *     (all four parity launches share it), 3 = weight gradient (a function of Cin, Cout alone).  0 for a shape the entry refuses.
+ *     Host-side only; the dispatch asks the same function, so the answer is what is launched. */
+int dhz_conv4s2_tile(int mode, int B, int H, int W, int Cin, int Cout);
 
 /* K8 in bf16 (BASELINE config 4): the same convolution as three token-Linear GEMMs on the bf16 matrix pipe (dhz_linear_fwd_bf16 /
  *     _dgrad_bf16 / _wgrad_bf16 with wp [Cout, 16*Cin]) over an explicit tap-major patch matrix; in the token layout a tap of an
@@ -263,6 +268,11 @@ int dhz_leff_prepack6(const float* w1, const float* w2, void* w6, int C, void* s
 int dhz_linear_fwd(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, int T, int N, int K,
                    void* stream);
 int dhz_linear_dgrad(const float* dy, int ldy, const float* w, float* dx, int ldx, int T, int N, int K, void* stream);
+/*     dhz_linear_tile: which tile instance <WM, WN> the two entries above run for `rows` tokens and `out_features` output columns
+ *     (N of the forward, K of the backward-data) under the current dhz_set_reserved_cus / dhz_set_deterministic state, as
+ *     10 WM + WN; the last row tile is ragged where rows % (32 WM) != 0.  0 for a shape the entries refuse and for a width that
+ *     takes the narrow kernel (a multiple of 16 but not of 32).  Host-side only; the dispatch asks the same function. */
+int dhz_linear_tile(int rows, int out_features);
 
 /* EXPERIMENT, off by default (dehaze_hip.ops.SPLIT_BF16 / bench.py --split-bf16; BASELINE configs[1] never takes it): the same two
  *     GEMMs with fp32 operands and results in HBM but the products on the bf16 matrix pipe, each operand split on its way into LDS

@@ -245,8 +245,9 @@ void launch(const float* A, const float* Wt, const float* bias, float* Y, const 
     hipLaunchKernelGGL((conv_gemm_kernel<WM, WN, MODE>), dim3(grid), dim3(256), smem, s, A, Wt, bias, Y, G, M, N, K, tiles_n, ntiles);
 }
 
-template <int MODE>
-void dispatch(const float* A, const float* Wt, const float* bias, float* Y, const ConvGeom& G, int M, int N, int K, hipStream_t s) {
+// The tile <WM, WN> of an M x N problem as 10 WM + WN: the first candidate (largest first) that still fills the 2 x dhz_part_cus()
+// workgroup slots, else the candidate with the most blocks.  The dispatch and dhz_conv4s2_tile both ask here.
+int choose_tile(int M, int N) {
     int wm = 2, wn = 1;
     static const int cand[8][2] = {{4, 4}, {4, 3}, {4, 2}, {2, 4}, {2, 3}, {2, 2}, {4, 1}, {2, 1}};
     long best = -1;
@@ -258,6 +259,19 @@ void dispatch(const float* A, const float* Wt, const float* bias, float* Y, cons
         if (blocks >= slots) { wm = a; wn = b; break; }
         if (blocks > best) { best = blocks; wm = a; wn = b; }
     }
+    return 10 * wm + wn;
+}
+
+// the weight gradient's tile: a function of (Cout, Cin) alone
+int choose_wgrad_tile(int Cin, int Cout) {
+    const int wm = (Cout % 128 == 0) ? 4 : (Cout % 96 == 0) ? 3 : (Cout % 64 == 0) ? 2 : 1;
+    const int wn = (Cin % 128 == 0) ? 4 : (Cin % 64 == 0) ? 2 : 1;               // a K tile stays inside one tap
+    return 10 * wm + wn;
+}
+
+template <int MODE>
+void dispatch(const float* A, const float* Wt, const float* bias, float* Y, const ConvGeom& G, int M, int N, int K, hipStream_t s) {
+    const int tile = choose_tile(M, N), wm = tile / 10, wn = tile % 10;
 #define CASE(a, b) \
     if (wm == a && wn == b) launch<a, b, MODE>(A, Wt, bias, Y, G, M, N, K, s);
     CASE(4, 1) CASE(4, 2) CASE(4, 3) CASE(4, 4) CASE(2, 1) CASE(2, 2) CASE(2, 3) CASE(2, 4)
@@ -461,8 +475,7 @@ extern "C" int dhz_conv4s2_wgrad(const float* dy, const float* x, float* dwp, fl
     DHZ_REQUIRE(T % TK == 0, "dhz_conv4s2_wgrad: B*Ho*Wo = %d must be a multiple of %d", T, TK);
     ConvGeom G = {H, W, Ho, Wo, Cin, Cout, 0, 0};
     const int N = Cout, K = 16 * Cin;
-    const int wm = (N % 128 == 0) ? 4 : (N % 96 == 0) ? 3 : (N % 64 == 0) ? 2 : 1;
-    const int wn = (Cin % 128 == 0) ? 4 : (Cin % 64 == 0) ? 2 : 1;               // a K tile stays inside one tap
+    const int tile = choose_wgrad_tile(Cin, Cout), wm = tile / 10, wn = tile % 10;
 #define CASE(a, b) \
     if (wm == a && wn == b) rc = launch_wgrad<a, b>(dy, x, dwp, db, G, T, N, K, lgWo, lgHW, (hipStream_t)stream);
     int rc = DHZ_OK;
@@ -471,4 +484,17 @@ extern "C" int dhz_conv4s2_wgrad(const float* dy, const float* x, float* dwp, fl
     if (rc) return rc;
     DHZ_CHECK_LAUNCH("dhz_conv4s2_wgrad");
     return DHZ_OK;
+}
+
+extern "C" int dhz_conv4s2_tile(int mode, int B, int H, int W, int Cin, int Cout) {
+    if (mode < 1 || mode > 3) return 0;
+    if (!(B > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && Cin % 32 == 0 && Cout % 32 == 0 && Cin > 0 && Cout > 0)) return 0;
+    const int Ho = H / 2, Wo = W / 2;
+    if ((long)B * Ho * Wo > 0x7fffffffL) return 0;
+    const int M = B * Ho * Wo;
+    if (mode == 3) {
+        if (ilog2(Wo) < 0 || ilog2(Ho * Wo) < 0 || M % TK) return 0;
+        return choose_wgrad_tile(Cin, Cout);
+    }
+    return choose_tile(M, mode == 1 ? Cout : Cin);
 }

@@ -444,6 +444,23 @@ __global__ __launch_bounds__(256) void narrow_gemm_kernel(const float* __restric
     }
 }
 
+// The tile <WM, WN> of an M x N problem as 10 WM + WN: the largest tile that still gives every CU two blocks, 128 x 128 down to
+// 64 x 32 (tile width must divide N), else the candidate with the most blocks.  The dispatch and dhz_linear_tile both ask here.
+int choose_tile(int M, int N) {
+    int wm = 2, wn = 1;
+    static const int cand[6][2] = {{4, 4}, {4, 2}, {2, 4}, {2, 2}, {4, 1}, {2, 1}};
+    long best_blocks = -1;
+    const long slots = 2 * dhz_part_cus();               // (a tile choice: a function of the shape in deterministic mode)
+    for (int i = 0; i < 6; ++i) {
+        const int a = cand[i][0], b = cand[i][1];
+        if (N % (32 * b)) continue;
+        const long blocks = (long)((M + 32 * a - 1) / (32 * a)) * (N / (32 * b));
+        if (blocks >= slots) { wm = a; wn = b; break; }    // two resident workgroups per CU
+        if (blocks > best_blocks) { best_blocks = blocks; wm = a; wn = b; }
+    }
+    return 10 * wm + wn;
+}
+
 template <bool WT>
 int dispatch(const char* who, const float* A, int lda, const float* W, int ldw, const float* bias, float* Y, int ldy, int M,
              int N, int K, hipStream_t s) {
@@ -462,20 +479,8 @@ int dispatch(const char* who, const float* A, int lda, const float* W, int ldw, 
     DHZ_REQUIRE((((uintptr_t)A | (uintptr_t)Y | (uintptr_t)W) & 15) == 0 && ((uintptr_t)bias & 3) == 0,
                 "%s: activations and weights must be 16-byte aligned", who);
     DHZ_REQUIRE((long)128 * (lda > ldw ? lda : ldw) < (1L << 30), "%s: row stride too large", who);
-    // largest tile that still gives every CU two blocks: 128 x 128 down to 64 x 32 (tile width must divide N)
-    int wm = 2, wn = 1;
-    {
-        static const int cand[6][2] = {{4, 4}, {4, 2}, {2, 4}, {2, 2}, {4, 1}, {2, 1}};
-        long best_blocks = -1;
-        const long slots = 2 * dhz_part_cus();               // (a tile choice: a function of the shape in deterministic mode)
-        for (int i = 0; i < 6; ++i) {
-            const int a = cand[i][0], b = cand[i][1];
-            if (N % (32 * b)) continue;
-            const long blocks = (long)((M + 32 * a - 1) / (32 * a)) * (N / (32 * b));
-            if (blocks >= slots) { wm = a; wn = b; break; }    // two resident workgroups per CU
-            if (blocks > best_blocks) { best_blocks = blocks; wm = a; wn = b; }
-        }
-    }
+    const int tile = choose_tile(M, N);
+    int wm = tile / 10, wn = tile % 10;
 #ifdef DHZ_DIAG
     if (const char* e = getenv("DHZ_GEMM_TILE")) {               // "wm,wn" (ignored where wn does not divide N / 32)
         int a = 0, b = 0;
@@ -515,4 +520,9 @@ extern "C" int dhz_linear_dgrad(const float* dy, int ldy, const float* w, float*
                                 void* stream) {
     // dx[T,K] = dy[T,N] w[N,K]: the contraction runs over the N rows of w, the output features are its K columns
     return dispatch<false>("dhz_linear_dgrad", dy, ldy, w, K, nullptr, dx, ldx, T, K, N, (hipStream_t)stream);
+}
+
+extern "C" int dhz_linear_tile(int rows, int out_features) {
+    if (rows <= 0 || out_features <= 0 || out_features % 32 || out_features > 16384) return 0;
+    return choose_tile(rows, out_features);
 }

@@ -161,6 +161,8 @@ SIGNATURES = {
     "dhz_blocked8_to_tokens": [c_f, c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_p],
     "dhz_conv3x3_wgrad_workspace_bytes": [c_i, c_i, c_i, c_i, c_i],
     "dhz_conv3x3_wgrad_parts": [c_i, c_i, c_i, c_i, c_i],
+    "dhz_conv4s2_tile": [c_i, c_i, c_i, c_i, c_i, c_i],
+    "dhz_linear_tile": [c_i, c_i],
     "dhz_conv3x3_wgrad": [c_f, c_f, c_f, c_f, c_f, ctypes.c_size_t, c_i, c_i, c_i, c_i, c_i, c_p],
 }
 _RESTYPE = {"dhz_last_error": ctypes.c_char_p, "dhz_build_id": ctypes.c_char_p, "dhz_conv3x3_wgrad_workspace_bytes": ctypes.c_size_t}
