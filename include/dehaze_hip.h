@@ -307,6 +307,11 @@ int dhz_linear_dgrad_split6(const float* dy, int ldy, const void* w_hi, const vo
 int dhz_linear_fwd_split6_res(const float* x, int ldx, const void* w_hi, const void* w_mid, const void* w_lo, const float* bias,
                               const float* res, const float* scale, float* out, int ldo, int T, int N, int K, int tokens_per_image,
                               int Hres, int Wres, int shift, int windowed, void* stream);
+/*     dhz_linear_split6_tile: which kernel dhz_linear_fwd_split6 / _split6_res (mode 1) or dhz_linear_dgrad_split6 (mode 2) runs for T
+ *     tokens, N = w's rows, K = w's columns (mode 2 answers for K output features and contraction N, as the entry passes them) under
+ *     the current dhz_set_reserved_cus / dhz_set_deterministic state: 10 (tile rows / 32) + tile columns / 32, i.e. 84 = 256 x 128,
+ *     44 = 128 x 128, 42 = 128 x 64, 41 = 128 x 32; 0 for a shape the entry refuses.  Host-side only; the dispatch asks the same function. */
+int dhz_linear_split6_tile(int mode, int T, int N, int K);
 int dhz_linear_fwd_split_res(const float* x, int ldx, const float* w, const float* bias, const float* res, const float* scale, float* out,
                              int ldo, int T, int N, int K, int tokens_per_image, int Hres, int Wres, int shift, int windowed, int terms,
                              void* stream);

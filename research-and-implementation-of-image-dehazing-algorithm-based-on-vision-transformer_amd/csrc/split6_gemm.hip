@@ -165,7 +165,7 @@ __global__ __launch_bounds__(NT, 1) void split6_gemm_kernel(const float* __restr
     const int wm = w / WAVES_N, wn = w % WAVES_N;
     const int nst = KC / BK;
     const int grid = gridDim.x;
-    auto tile_of = [&](int i) -> int {
+    auto tile_of = [&](int i) -> int {                // (restated in Python by s6_stream of tests/_tile_cases.py: change both together)
         const int lin = blockIdx.x + i * grid;
         if (lin >= ntiles) return -1;
         if ((grid & 7) == 0 && (ntiles & 7) == 0) return (lin & 7) * (ntiles >> 3) + (lin >> 3);
@@ -496,7 +496,7 @@ __global__ __launch_bounds__(NT, 1) void split6_wide_kernel(const float* __restr
     const int wm = w / WAVES_N, wn = w % WAVES_N;
     const int nst = KC / BK;
     const int grid = gridDim.x;
-    auto tile_of = [&](int i) -> int {
+    auto tile_of = [&](int i) -> int {                // (restated in Python by s6_stream of tests/_tile_cases.py: change both together)
         const int lin = blockIdx.x + i * grid;
         if (lin >= ntiles) return -1;
         if ((grid & 7) == 0 && (ntiles & 7) == 0) return (lin & 7) * (ntiles >> 3) + (lin >> 3);
@@ -729,6 +729,8 @@ __global__ __launch_bounds__(NT, 1) void split6_wide_kernel(const float* __restr
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+// launch_wide / launch: one workgroup per CU, grid = min(tiles, dhz_num_cus()).  s6_plan of tests/_tile_cases.py restates tiles, grid
+// and trips in Python, and the host proofs of tests/test_split6_instances_host.py rest on it: change both together.
 template <bool BTR, bool EPI>
 void launch_wide(const float* A, int lda, const uint16_t* Bh, const uint16_t* Bm, const uint16_t* Bl, int ldb, const float* bias, float* C,
                  int ldc, int M, int NF, int KC, const TokEpi& epi, hipStream_t s) {
@@ -758,6 +760,23 @@ void launch(const float* A, int lda, const uint16_t* Bh, const uint16_t* Bm, con
                        M, NF, KC, tiles_n, ntiles, epi);
 }
 
+// The tile of T tokens x NF output features as 10 (rows / 32) + columns / 32 - 84 = 256 x 128 (the wide kernel), 44 = 128 x 128,
+// 42 = 128 x 64, 41 = 128 x 32 - or 0 for a shape the checks of dispatch() refuse.  BTR: backward-data (NF = w's columns, KC = its
+// rows).  The dispatch and dhz_linear_split6_tile both ask here.  The weight bound: dispatch() refuses on ldb * (BTR ? KC : NF), and all
+// three entries pass packed planes, ldb = the planes' width (KC forward, NF backward-data), so that product is NF * KC - the query, which
+// has no ldb, refuses on that.  An entry that passed planes with ldb > width would need the bound restated here.
+int split6_tile(bool BTR, int M, int NF, int KC) {
+    if (M <= 0 || NF <= 0 || KC <= 0 || NF % (BTR ? 64 : 32) || KC % 32 || (long)NF * KC >= (1L << 31) || NF > 2048) return 0;
+    // the widest feature block that divides NF (the pre-split weight side costs no vector work: wide tiles re-split the
+    // activations fewer times); 128 tokens (three ring slots of both operands fit the LDS)
+    const int cus = dhz_part_cus();                               // (tile choices: a function of the shape in deterministic mode)
+    int bn = NF % 128 == 0 ? 128 : NF % 64 == 0 ? 64 : 32;
+    if (bn == 128 && (long)((M + 127) / 128) * (NF / 128) < cus && (long)((M + 127) / 128) * (NF / 64) >= cus / 2) bn = 64;
+    static const int force = getenv("DHZ_S6_TILE") ? atoi(getenv("DHZ_S6_TILE")) : 0;          // diagnostics: 1 = never wide, 2 = always wide
+    const bool wide = bn == 128 && force != 1 && (force == 2 || (long)((M + 255) / 256) * (NF / 128) >= cus);
+    return wide ? 84 : 40 + bn / 32;
+}
+
 template <bool BTR, bool EPI = false>
 int dispatch(const char* who, const float* A, int lda, const uint16_t* Bh, const uint16_t* Bm, const uint16_t* Bl, int ldb,
              const float* bias, float* C, int ldc, int M, int NF, int KC, hipStream_t s, const TokEpi& epi = TokEpi{}) {
@@ -769,22 +788,16 @@ int dispatch(const char* who, const float* A, int lda, const uint16_t* Bh, const
                 "%s: operands must be 16-byte aligned", who);
     DHZ_REQUIRE((long)ldb * (BTR ? KC : NF) < (1L << 31), "%s: weight matrix too large", who);
     DHZ_REQUIRE(NF <= 2048, "%s: %d output features (at most 2048: the bias vector is staged in LDS)", who, NF);
-    // tile: the widest feature block that divides NF (the pre-split weight side costs no vector work: wide tiles re-split the
-    // activations fewer times); 128 tokens (three ring slots of both operands fit the LDS)
-    const int cus = dhz_part_cus();                               // (tile choices: a function of the shape in deterministic mode)
-    int bn = NF % 128 == 0 ? 128 : NF % 64 == 0 ? 64 : 32;
-    if (bn == 128 && (long)((M + 127) / 128) * (NF / 128) < cus && (long)((M + 127) / 128) * (NF / 64) >= cus / 2) bn = 64;
     if (EPI) {
         const char* bad = tok_epi_check(epi, M);
         DHZ_REQUIRE(!bad, "%s: %s", who, bad);
         DHZ_REQUIRE(((uintptr_t)epi.res & 15) == 0, "%s: the shortcut must be 16-byte aligned", who);
     }
 #define GO(WM_, WN_, WV_) launch<WM_, WN_, WV_, BTR, EPI>(A, lda, Bh, Bm, Bl, ldb, bias, C, ldc, M, NF, KC, epi, s)
-    static const int force = getenv("DHZ_S6_TILE") ? atoi(getenv("DHZ_S6_TILE")) : 0;          // diagnostics: 1 = never wide, 2 = always wide
-    const bool wide = bn == 128 && force != 1 && (force == 2 || (long)((M + 255) / 256) * (NF / 128) >= cus);
-    if (wide) launch_wide<BTR, EPI>(A, lda, Bh, Bm, Bl, ldb, bias, C, ldc, M, NF, KC, epi, s);        // 256 x 128
-    else if (bn == 128) GO(4, 2, 2);                              // 128 x 128
-    else if (bn == 64) GO(2, 2, 4);                               // 128 x 64
+    const int tile = split6_tile(BTR, M, NF, KC);
+    if (tile == 84) launch_wide<BTR, EPI>(A, lda, Bh, Bm, Bl, ldb, bias, C, ldc, M, NF, KC, epi, s);  // 256 x 128
+    else if (tile == 44) GO(4, 2, 2);                             // 128 x 128
+    else if (tile == 42) GO(2, 2, 4);                             // 128 x 64
     else if constexpr (!BTR) GO(1, 2, 8);                         // 128 x 32
 #undef GO
     DHZ_CHECK_LAUNCH(who);
@@ -878,6 +891,11 @@ extern "C" int dhz_linear_dgrad_split6(const float* dy, int ldy, const void* w_h
     // dx[T,K] = dy[T,N] w[N,K]: the contraction runs over the N rows of w (transposed reads), the output features are its K columns
     return dispatch<true>("dhz_linear_dgrad_split6", dy, ldy, (const uint16_t*)w_hi, (const uint16_t*)w_mid, (const uint16_t*)w_lo, K,
                           nullptr, dx, ldx, T, K, N, (hipStream_t)stream);
+}
+
+extern "C" int dhz_linear_split6_tile(int mode, int T, int N, int K) {
+    if (mode != 1 && mode != 2) return 0;
+    return mode == 1 ? split6_tile(false, T, N, K) : split6_tile(true, T, K, N);
 }
 
 extern "C" int dhz_linear_fwd_split6_res(const float* x, int ldx, const void* w_hi, const void* w_mid, const void* w_lo, const float* bias,

@@ -163,6 +163,7 @@ SIGNATURES = {
     "dhz_conv3x3_wgrad_parts": [c_i, c_i, c_i, c_i, c_i],
     "dhz_conv4s2_tile": [c_i, c_i, c_i, c_i, c_i, c_i],
     "dhz_linear_tile": [c_i, c_i],
+    "dhz_linear_split6_tile": [c_i, c_i, c_i, c_i],
     "dhz_conv3x3_wgrad": [c_f, c_f, c_f, c_f, c_f, ctypes.c_size_t, c_i, c_i, c_i, c_i, c_i, c_p],
 }
 _RESTYPE = {"dhz_last_error": ctypes.c_char_p, "dhz_build_id": ctypes.c_char_p, "dhz_conv3x3_wgrad_workspace_bytes": ctypes.c_size_t}

@@ -1,4 +1,5 @@
-"""Case tables of tests/test_tile_instances_host.py and tests/test_gpu_tile_instances.py (a plain helper module, not a conftest).
+"""Case tables of tests/test_tile_instances_host.py and tests/test_gpu_tile_instances.py, and (last section) of
+tests/test_split6_instances_host.py and tests/test_gpu_split6_instances.py (a plain helper module, not a conftest).
 
 csrc/conv_gemm.hip (dhz_conv4s2_fwd / _dgrad) and csrc/linear_gemm.hip (dhz_linear_fwd / _dgrad) pick a tile instance <WM, WN> from the
 problem size and the CU count: the first candidate, largest first, with at least 2 x CUs blocks, else the candidate with the most
@@ -88,3 +89,109 @@ def plan(instance, M, N, ncu):
 def first_candidate(cand, N):
     """the first tile of the candidate list that N admits, as an instance number"""
     return next(10 * a + b for a, b in cand if N % (32 * b) == 0)
+
+
+# ---- six-term plane GEMMs (csrc/split6_gemm.hip: dhz_linear_fwd_split6 / _dgrad_split6 / _fwd_split6_res).  Instances are written
+# 10 (tile rows / 32) + tile columns / 32, as dhz_linear_split6_tile answers: 84 = split6_wide_kernel (256 x 128, two-slot ring),
+# 44 / 42 / 41 = split6_gemm_kernel at 128 x 128 / 64 / 32 (three-slot ring, loop unrolled x 6).  Each runs as forward, backward-data
+# (features a multiple of 64: none at 41) and forward + residual epilogue: eleven instantiations.
+#
+# Levels: the whole device, grids sized for 8 and for 9 CUs, and deterministic mode at 8 and at 9 reserved CUs - there the CHOICE is
+# made for 256 CUs while the GRID is the reserved one (one workgroup per CU: grid = min(tiles, CUs)).
+#
+# Trip rule.  84, 42 and 41 can be given any number of tiles: their cases make three trips and more with a ragged last trip and a
+# ragged last row tile.  44 is chosen only when the 256-row tiles of the wide kernel number fewer than the CUs of the choice, so
+# outside deterministic mode it has fewer than 2 x CUs tiles and can never make more than two trips: its plain cases make two, the
+# second ragged; its many-trip cases (three and more, six and more for the one- and two-stage contractions) are deterministic ones.
+S6_LEVELS = ((None, False), (8, False), (9, False), (8, True), (9, True))       # (reserved CUs, deterministic mode)
+S6_TABLED = S6_LEVELS[1:]                      # the levels S6_TABLE makes claims for, in its column order
+S6_INSTANCES = (84, 44, 42, 41)
+S6_MODES = ("fwd", "dgrad", "epi")
+S6_CONTRACTIONS = (32, 64, 96, 160, 192, 224)  # 1, 2, 3, 5, 6, 7 stages of 32 per tile
+# S6_TABLE[(T, features)] = (instance, trips) at 8 CUs, at 9 CUs, deterministic at 8, deterministic at 9
+S6_TABLE = {
+    (7000, 128): ((84, 4), (84, 4), (44, 7), (44, 7)),     # 28 wide tiles, last trip 4 / 1, rows ragged by 88; det: 55 tiles, 7 trips
+    (8100, 128): ((84, 4), (84, 4), (42, 16), (42, 15)),   # 32 wide tiles: four full trips at 8 with the XCD remap on
+    (7104, 256): ((84, 7), (84, 7), (42, 28), (42, 25)),   # 56 wide tiles on two column tiles, seven trips (last 8 / 2), rows ragged by 192
+    (3520, 128): ((84, 2), (84, 2), (44, 4), (44, 4)),     # det: 28 tiles, four trips (last 4 / 1), rows ragged by 64
+    (3072, 128): ((84, 2), (84, 2), (44, 3), (44, 3)),     # det at 8: 24 tiles of 44, three full trips with the remap on
+    (1728, 128): ((44, 2), (44, 2), (44, 2), (44, 2)),     # 14 tiles: 8 + 6, 9 + 5; rows ragged by 64
+    (704, 256): ((44, 2), (44, 2), (44, 2), (44, 2)),      # 12 tiles on two column tiles: at 9 a workgroup changes column tile
+    (704, 128): ((42, 2), (42, 2), (44, 1), (44, 1)),      # 42 by demotion (6 tiles of 128 x 128 < CUs): 12 tiles
+    (2500, 192): ((42, 8), (42, 7), (42, 8), (42, 7)),     # 60 tiles on three column tiles, last trip 4 / 6, rows ragged by 68
+    (3072, 64): ((42, 3), (42, 3), (42, 3), (42, 3)),      # 24 tiles: three full trips at 8 with the remap on
+    (1216, 192): ((42, 4), (42, 4), (42, 4), (42, 4)),     # 30 tiles, rows ragged by 64
+    (1200, 160): ((41, 7), (41, 6), (41, 7), (41, 6)),     # 50 tiles on five column tiles, last trip 2 / 5, rows ragged by 48
+    (3072, 32): ((41, 3), (41, 3), (41, 3), (41, 3)),      # 24 tiles: three full trips at 8 with the remap on
+    (1216, 96): ((41, 4), (41, 4), (41, 4), (41, 4)),      # 30 tiles on three column tiles, rows ragged by 64
+}
+S6_MAX = (8100, 384, 224)                      # no case is larger than this many tokens, features, contraction elements
+
+
+def s6_modes(features):
+    """the modes a width runs in: backward-data needs a multiple of 64 output features"""
+    return tuple(m for m in S6_MODES if m != "dgrad" or features % 64 == 0)
+
+
+def s6_query(lib, mode, T, features, contraction):
+    """dhz_linear_split6_tile for `features` output columns: the forward has N = features, K = contraction, backward-data the reverse"""
+    return lib.dhz_linear_split6_tile(2, T, contraction, features) if mode == "dgrad" else lib.dhz_linear_split6_tile(1, T, features, contraction)
+
+
+def s6_plan(instance, T, features, ncu):
+    """(tiles, grid, trips, remap on) of the persistent launch of `instance` on grids sized for ncu CUs (launch / launch_wide)"""
+    bm, bn = 32 * (instance // 10), 32 * (instance % 10)
+    ntiles = -(-T // bm) * (features // bn)
+    grid = min(ntiles, ncu)
+    return ntiles, grid, -(-ntiles // grid), grid % 8 == 0 and ntiles % 8 == 0
+
+
+def s6_stream(instance, T, features, ncu, wg=0):
+    """the (row tile, column tile) pairs workgroup `wg` walks, in order (tile_of of both kernels, XCD remap included)"""
+    ntiles, grid, _, on = s6_plan(instance, T, features, ncu)
+    tiles_n = features // (32 * (instance % 10))
+    out = []
+    for lin in range(wg, ntiles, grid):
+        tile = (lin & 7) * (ntiles >> 3) + (lin >> 3) if on else lin
+        out.append(divmod(tile, tiles_n))
+    return out
+
+
+def s6_level(ncu, det):
+    """context: grids sized for ncu CUs (None: the whole device), in deterministic mode where det; both are given back on the way
+    out.  Yields the CU count the grids are sized for."""
+    import contextlib
+    from _grid import reserved_grid
+    from dehaze_hip import _lib as L
+
+    @contextlib.contextmanager
+    def level():
+        assert L.load().dhz_get_deterministic() == 0
+        with reserved_grid(ncu) as n:
+            try:
+                if det:
+                    L.call("dhz_set_deterministic", 1)
+                yield n
+            finally:
+                L.call("dhz_set_deterministic", 0)
+    return level()
+
+
+def s6_no_override():
+    """the tables describe the dispatch as it ships: the diagnostic override of tools/pmc_split6.sh must not be set"""
+    import os
+    assert "DHZ_S6_TILE" not in os.environ, ("DHZ_S6_TILE is set: it forces the tile of csrc/split6_gemm.hip (a diagnostic of "
+                                             "tools/pmc_split6.sh); unset it to run the instance tests")
+
+
+S6_BOUND, S6_FLOOR = 2.0 ** -21, 1e-7          # the six-term bound: |err| <= 2^-21 mag + 1e-7, mag = the reference over absolute values
+
+
+def s6_operands(T, features, contraction, device, seed):
+    """activations [T, contraction], weight [features, contraction] (rows of unit norm on average), bias [features], drawn on `device`"""
+    import torch
+    g = torch.Generator(device=device).manual_seed(seed)
+    x = torch.randn(T, contraction, generator=g, device=device)
+    w = torch.randn(features, contraction, generator=g, device=device) / contraction ** 0.5
+    b = torch.randn(features, generator=g, device=device)
+    return x, w, b

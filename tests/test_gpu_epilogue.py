@@ -20,14 +20,17 @@ def _window_reverse_roll(yw, B, H, W, shift):
     return y.reshape(B * H * W, C)
 
 
-# (B, H, W, K, N): shapes that reach each kernel of the dispatch - 256 x 128 tiles (wide), 128 x 128, 128 x 64, 128 x 32, and the
-# few-tile kernel of csrc/linear_split.hip (through its own entry point)
-SHAPES = [(8, 64, 64, 128, 128),      # T = 32768: wide
-          (2, 32, 32, 512, 128),      # T = 2048, N = 128: 128 x 64 tiles (few tiles), long contraction (LeFF linear2 shape)
-          (8, 16, 16, 256, 256),      # T = 2048: 128 x 64
-          (32, 16, 16, 512, 512),     # T = 8192, N = 512: 128 x 128
+# (B, H, W, K, N): token counts, widths and map geometries of the model's blocks, and the few-tile kernel of csrc/linear_split.hip
+# (through its own entry point).  The kernel of csrc/split6_gemm.hip named behind each shape is what dhz_linear_split6_tile answers on
+# the whole device (256 CUs): there these shapes never fill the 256 x 128 kernel and never meet the demotion to 128 x 64 -
+# tests/test_gpu_split6_instances.py runs every instance of that file, epilogue form included, under reserved grids.
+SHAPES = [(8, 64, 64, 128, 128),      # T = 32768: 128 x 128 (128 tiles of 256 rows < CUs)
+          (2, 32, 32, 512, 128),      # T = 2048, N = 128: 128 x 128, 16 tiles; long contraction (LeFF linear2 shape)
+          (8, 16, 16, 256, 256),      # T = 2048: 128 x 128, 32 tiles
+          (32, 16, 16, 512, 512),     # T = 8192, N = 512: 128 x 128, 256 tiles
           (4, 24, 40, 64, 96),        # N = 96: 128 x 32 tiles; a non-square, non-power-of-two map
-          (3, 8, 8, 128, 64)]         # a partial last tile (T = 192)
+          (3, 8, 8, 128, 64)]         # 128 x 64: two tiles, the last one partial (T = 192)
+SPLIT6_TILE_256 = dict(zip(SHAPES, (44, 44, 44, 44, 41, 42)))
 
 
 @pytest.mark.parametrize("windowed,shift,scaled", [(1, 0, False), (1, 4, True), (1, 3, True), (0, 0, True), (0, 0, False)])
@@ -53,6 +56,9 @@ def test_residual_epilogue_vs_fp64(B, H, W, K, N, windowed, shift, scaled):
         ref = res.double() + f * y64
         mag = f * mag + res.double().abs()
     hi, mid, lo = ops.split_planes(w)
+    lib = _lib.load()
+    if lib.dhz_grid_cus() + lib.dhz_get_reserved_cus() == 256:             # the instance comments over SHAPES hold for 256 CUs
+        assert lib.dhz_linear_split6_tile(1, T, N, K) == SPLIT6_TILE_256[(B, H, W, K, N)]
     out = torch.full((T, N), float("nan"), device=dev)
     _lib.call("dhz_linear_fwd_split6_res", x.data_ptr(), K, hi.data_ptr(), mid.data_ptr(), lo.data_ptr(), b.data_ptr(), res.data_ptr(),
               sc.data_ptr() if scaled else None, out.data_ptr(), N, T, N, K, H * W, H, W, shift, windowed, s)
