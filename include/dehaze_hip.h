@@ -718,6 +718,62 @@ int dhz_comm_init(void** comm, int rank, int nranks, const void* id128);
 int dhz_comm_allreduce_sum_f32(void* comm, float* buf, int64_t n, void* stream);
 int dhz_comm_destroy(void* comm);
 
+/* K13  FFA-Net's own layers (FFA = FFA_model/models/FFA.py) in the channel-blocked layout of K11, fp32, C = 64 (csrc/ffa_attn.hip):
+ *      channel attention CALayer (FFA:24-38: aten::mean -> 1x1 convolution -> relu_ -> 1x1 convolution -> sigmoid -> mul), pixel attention
+ *      PALayer (FFA:9-21: 1x1 convolution 64 -> 8 -> relu_ -> 1x1 convolution 8 -> 1 -> sigmoid -> mul) and the `res += x` of a Block
+ *      (FFA:54-56) with G = 1 map; the fusion head (FFA:105-108: aten::cat of the three group outputs -> mean -> the gate MLP -> three
+ *      slices, three mul, two add -> PALayer) with G = 3 maps m0, m1, m2 (m1, m2 are ignored for G = 1; no concatenated tensor exists).
+ *      Maps are [B][8][H][W][8]; H and W multiples of 16; 16-byte aligned pointers.
+ *        mean[b][g 64 + c] = (1 / HW) sum_p m_g[b][c][p]
+ *        hid = relu(Wa mean + ba)     Wa [hc][64 G], hc = 8 (G = 1, FFA:29) or 4 (G = 3, FFA:86)
+ *        ca  = sigmoid(Wb hid + bb)   Wb [64 G][hc]
+ *        t[b][c][p] = sum_g ca[b][g 64 + c] m_g[b][c][p]
+ *        h[b][i][p] = relu(sum_c Wp1[i][c] t[b][c][p] + bp1[i]), i < 8  (FFA:13);   pg[b][p] = sigmoid(sum_i wp2[i] h[b][i][p] + bp2)  (FFA:15)
+ *        out = t pg (+ res when res != NULL)
+ *      dhz_ffa_ca_fwd: mean [B][64 G], hid [B][hc], ca [B][64 G] are all written (the backward reads them).  Pooling in chunks of 1024
+ *        pixels, one partial vector per (image, group, chunk) in ws, summed per image in ascending chunk order.
+ *      dhz_ffa_gate_pa_fwd: t, h, pg and out in one pass; writes out only.
+ *      Backward of both (autograd of the sequences above), given dout, in three entries:
+ *        dhz_ffa_gate_pa_bwd_a recomputes t, h, pg from m_g and ca, writes dt (one map)
+ *              dpg = sum_c dout t;  dz = dpg pg (1 - pg);  dh_i = dz wp2[i] [h_i > 0];  dt_c = dout_c pg + sum_i Wp1[i][c] dh_i
+ *          and, per workgroup of 128 pixels, the partial sums of dca[b][g 64 + c] = sum_p dt_c m_g, dWp1[i][c] = sum dh_i t_c,
+ *          dbp1[i] = sum dh_i, dwp2[i] = sum dz h_i, dbp2 = sum dz to ws.
+ *        dhz_ffa_ca_bwd sums those partials in fixed order (16 consecutive workgroups, then the groups of 16, then the images, each
+ *          ascending) and runs the gate MLP backwards: dzb = dca ca (1 - ca); dWb = sum_b dzb (x) hid; dbb = sum_b dzb;
+ *          dhid = (Wb^T dzb) [hid > 0]; dWa = sum_b dhid (x) mean; dba = sum_b dhid; dmean [B][64 G] = Wa^T dhid.  ws must be the
+ *          workspace dhz_ffa_gate_pa_bwd_a has just filled for the same B, H, W, G.  It leaves the level-1 sums behind the partials, at
+ *          float offset B chunks (64 G + 532), chunks = H W / 128, as [B][ceil(chunks / 16)][64 G + 532]: the first 64 G floats of an
+ *          image's segments add up to dca[b] (tests read it there).
+ *        dhz_ffa_gate_pa_bwd_b writes dm_g = ca[b][g 64 + c] dt + dmean[b][g 64 + c] / HW for each g (dm1, dm2 ignored for G = 1).
+ *          The gradient of res is dout itself.
+ *      All parameter gradients (dWa, dba, dWb, dbb, dWp1, dbp1, dwp2, dbp2) are WRITTEN, not accumulated, as dhz_conv3x3_wgrad does.
+ *      No atomics; the cut of every reduction depends on the shapes alone: the same bits from run to run, under any
+ *      dhz_set_reserved_cus, with the deterministic mode on or off.
+ *      ws: dhz_ffa_workspace_bytes(B, H, W, G) bytes (one size for the three entries that take it; a function of the shapes alone; 0
+ *      for an unsupported shape), 16-byte aligned.  With dhz_set_deterministic on, the mode's workspace (dhz_set_det_workspace) is used
+ *      instead and ws may be NULL; dhz_ffa_ca_bwd must then follow its dhz_ffa_gate_pa_bwd_a with no other accumulating entry between.
+ *      Anything else - a null pointer, B < 1, H or W no multiple of 16, G outside {1, 3}, a missing or too small workspace, a pointer
+ *      that is not 16-byte aligned - is DHZ_EINVAL before any launch. */
+size_t dhz_ffa_workspace_bytes(int B, int H, int W, int G);
+int dhz_ffa_ca_fwd(const float* m0, const float* m1, const float* m2, const float* Wa, const float* ba, const float* Wb, const float* bb,
+                   float* mean, float* hid, float* ca, float* ws, size_t ws_bytes, int B, int H, int W, int G, void* stream);
+int dhz_ffa_gate_pa_fwd(const float* m0, const float* m1, const float* m2, const float* ca, const float* Wp1, const float* bp1,
+                        const float* wp2, const float* bp2, const float* res, float* out, int B, int H, int W, int G, void* stream);
+int dhz_ffa_gate_pa_bwd_a(const float* m0, const float* m1, const float* m2, const float* ca, const float* Wp1, const float* bp1,
+                          const float* wp2, const float* bp2, const float* dout, float* dt, float* ws, size_t ws_bytes, int B, int H, int W,
+                          int G, void* stream);
+int dhz_ffa_ca_bwd(float* ws, size_t ws_bytes, const float* Wa, const float* Wb, const float* mean, const float* hid, const float* ca,
+                   float* dWa, float* dba, float* dWb, float* dbb, float* dmean, float* dWp1, float* dbp1, float* dwp2, float* dbp2, int B,
+                   int H, int W, int G, void* stream);
+int dhz_ffa_gate_pa_bwd_b(const float* dt, const float* ca, const float* dmean, float* dm0, float* dm1, float* dm2, int B, int H, int W,
+                          int G, void* stream);
+/*      The two elementwise passes of a Block (FFA:51-56) over n floats (n % 4 == 0, any common element order):
+ *      dhz_ffa_add: y = a + x  (`res = res + x`, FFA:52: aten::add; also the group residual FFA:69 and the `+ x1` of FFA:110).
+ *      dhz_ffa_relu_bwd_add: dpre1 = a1 > 0 ? dr : 0 (aten::threshold_backward of act1 by the sign of the saved activation a1) and
+ *        s = dout + dr (the two gradients that reach the block input besides conv1's) in one pass. */
+int dhz_ffa_add(const float* a, const float* x, float* y, int64_t n, void* stream);
+int dhz_ffa_relu_bwd_add(const float* a1, const float* dr, const float* dout, float* dpre1, float* s, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

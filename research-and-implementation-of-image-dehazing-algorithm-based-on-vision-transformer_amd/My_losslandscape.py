@@ -25,6 +25,7 @@ from My_CR import ContrastLoss  # noqa: E402
 def main(argv=None):
     parser = options.Options().init(argparse.ArgumentParser(description='loss landscape of the dehazing model'))
     parser.add_argument('--synthetic', type=int, default=0, help='evaluate on N synthetic pairs instead of --train_dir')
+    parser.add_argument('--ffa_blocks', type=int, default=19, help='blocks per group of --arch FFA')
     parser.add_argument('--n_grid', type=int, default=21)
     parser.add_argument('--scale', type=float, default=1.0)
     parser.add_argument('--mixup', action='store_true', help='apply MixUp to every batch as the reference script does')

@@ -49,6 +49,7 @@ def main():
     parser = options.Options().init(argparse.ArgumentParser(description='remove the haze'))
     parser.add_argument('--synthetic', type=int, default=0, help='train on N synthetic pairs per epoch (HBM resident)')
     parser.add_argument('--val_synthetic', type=int, default=8)
+    parser.add_argument('--ffa_blocks', type=int, default=19, help='blocks per group of --arch FFA')
     parser.add_argument('--deterministic', action='store_true',
                         help='bit-reproducible steps: fixed-order reductions instead of fp32 atomics (fp32 storage, per process; slower)')
     parser.add_argument('--log_every', type=int, default=10, help='host sync cadence for the progress line')

@@ -165,8 +165,18 @@ SIGNATURES = {
     "dhz_linear_tile": [c_i, c_i],
     "dhz_linear_split6_tile": [c_i, c_i, c_i, c_i],
     "dhz_conv3x3_wgrad": [c_f, c_f, c_f, c_f, c_f, ctypes.c_size_t, c_i, c_i, c_i, c_i, c_i, c_p],
+    # FFA-Net's channel / pixel attention on the channel-blocked layout (csrc/ffa_attn.hip)
+    "dhz_ffa_workspace_bytes": [c_i, c_i, c_i, c_i],
+    "dhz_ffa_ca_fwd": [c_f] * 11 + [ctypes.c_size_t, c_i, c_i, c_i, c_i, c_p],
+    "dhz_ffa_gate_pa_fwd": [c_f] * 10 + [c_i, c_i, c_i, c_i, c_p],
+    "dhz_ffa_gate_pa_bwd_a": [c_f] * 11 + [ctypes.c_size_t, c_i, c_i, c_i, c_i, c_p],
+    "dhz_ffa_ca_bwd": [c_f, ctypes.c_size_t] + [c_f] * 14 + [c_i, c_i, c_i, c_i, c_p],
+    "dhz_ffa_gate_pa_bwd_b": [c_f] * 6 + [c_i, c_i, c_i, c_i, c_p],
+    "dhz_ffa_add": [c_f, c_f, c_f, c_l, c_p],
+    "dhz_ffa_relu_bwd_add": [c_f, c_f, c_f, c_f, c_f, c_l, c_p],
 }
-_RESTYPE = {"dhz_last_error": ctypes.c_char_p, "dhz_build_id": ctypes.c_char_p, "dhz_conv3x3_wgrad_workspace_bytes": ctypes.c_size_t}
+_RESTYPE = {"dhz_last_error": ctypes.c_char_p, "dhz_build_id": ctypes.c_char_p, "dhz_conv3x3_wgrad_workspace_bytes": ctypes.c_size_t,
+            "dhz_ffa_workspace_bytes": ctypes.c_size_t}
 
 _lib = None
 

@@ -150,4 +150,13 @@ def get_arch(opt):
         return Uformer(img_size=opt.train_ps, embed_dim=16, win_size=8, token_projection='linear', token_mlp='leff')
     if arch == 'Uformer32':
         return Uformer(img_size=opt.train_ps, embed_dim=32, win_size=8, token_projection='linear', token_mlp='leff')
+    if arch == 'FFA':
+        # FFA_model/models/FFA.py: three groups of `ffa_blocks` blocks (19 in the paper); the width is 64, opt.embed_dim does not apply.
+        # A script whose parser has no --ffa_blocks (test_long_GPU.py) takes the depth from DHZ_FFA_BLOCKS, so that a checkpoint trained
+        # at another depth can be evaluated: DHZ_FFA_BLOCKS=2 python test_long_GPU.py --arch FFA --weights ...
+        from dehaze_hip.ffa import FFA
+        blocks = getattr(opt, 'ffa_blocks', None)
+        if blocks is None:
+            blocks = int(os.environ.get('DHZ_FFA_BLOCKS', '19'))
+        return FFA(gps=3, blocks=blocks)
     raise Exception("Arch error!")
