@@ -467,6 +467,25 @@ int dhz_winograd43_conv3x3(const float* x, const float* upack, const float* bias
  * [B][K/8][H][W][8], needed only for C > 256 (partial sums of the accumulation chains), may be NULL otherwise. */
 int dhz_winograd43_conv3x3_pool(const float* x, const float* upack, const float* bias, float* ypool, float* scratch, int B, int H, int W,
                                 int C, int K, void* stream);
+/* K11c Channel slices for launches whose grid leaves CUs idle (the 8 x 8 and 16 x 16 maps of a 128 x 128 patch): the input-channel
+ *      contraction is cut into `slices` ranges of 8-channel groups, ONE grid of slices x (the plain grid) workgroups leaves the raw sums of
+ *      slice s in part s of workspace (slices * B * K * H * W floats, contents undefined before and after), and a second kernel adds the
+ *      parts in a fixed order - r = p_0 + ... + p_{S-2}, then (p_{S-1} + bias) + r - and applies the store epilogue (bias / ReLU, or
+ *      out_mask / out_addend).  No atomics: the same bits from run to run.  Other arguments as dhz_winograd_conv3x3 / dhz_winograd43_conv3x3.
+ *      dhz_winograd_conv3x3_slices: 1 <= slices <= C / 8 (uneven ranges allowed); slices == 1 is dhz_winograd_conv3x3 bit for bit and
+ *        takes no workspace; slices > 1 with a null workspace: DHZ_EINVAL.
+ *      dhz_winograd43_conv3x3_slices: slices >= 2, (C / 8) % slices == 0 and C / slices <= 256: every slice is one accumulation-chain link.
+ *        Two slices of 512 channels give the bits of dhz_winograd43_conv3x3 (the same links, added in the same order).
+ *      dhz_winograd_slices: the slice count the library recommends for dhz_winograd_conv3x3_slices - the largest S in {1, 2, 4} with
+ *        S x grid <= physical CUs (dhz_grid_cus() + dhz_get_reserved_cus(): these grids are not persistent) and at least 16 channel groups
+ *        per slice; 1 = the plain launch (also for a shape the entry refuses).  Host-side only. */
+int dhz_winograd_conv3x3_slices(const float* x, const float* upack, const float* bias, int relu, const float* out_mask,
+                                const float* out_addend, float* y, float* workspace, int slices, int B, int H, int W, int C, int K,
+                                void* stream);
+int dhz_winograd43_conv3x3_slices(const float* x, const float* upack, const float* bias, int relu, const float* out_mask,
+                                  const float* out_addend, float* y, float* workspace, int slices, int B, int H, int W, int C, int K,
+                                  void* stream);
+int dhz_winograd_slices(int B, int H, int W, int C, int K);
 int dhz_maxpool2x2_blocked_fwd(const float* x, float* y, int N, int H, int W, void* stream);
 int dhz_maxpool2x2_blocked_bwd(const float* gy, const float* act, float* gx, int N, int H, int W, void* stream);
 int dhz_layout_blocked8(const float* src, float* dst, int B, int C, int HW, int to_blocked, const float* bias, int relu,

@@ -73,6 +73,10 @@ __device__ __forceinline__ void dhz_accum(float* p, float v) {
     else atomicAdd(p, v);
 }
 
+// csrc/winograd_conv.hip: y = store epilogue(sum of the `slices` raw parts in ws) of a sliced Winograd launch, F(2x2) or F(4x4)
+int dhz_wino_slices_epilogue(const char* who, const float* ws, int slices, const float* bias, int relu, const float* out_mask,
+                             const float* out_addend, float* y, int B, int H, int W, int K, hipStream_t s);
+
 #define DHZ_REQUIRE(cond, ...)            \
     do {                                  \
         if (!(cond)) {                    \

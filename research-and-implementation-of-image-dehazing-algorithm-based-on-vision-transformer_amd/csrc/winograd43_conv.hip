@@ -134,7 +134,11 @@ __global__ __launch_bounds__(256, 1) void winograd43_conv3x3_kernel(const float*
                                                                     int W, int C, int K, int nblk, int xcd_group, int cb0, int ncb,
                                                                     int chain, float* __restrict__ ypool) {
     // cb0, ncb: the channel groups [cb0, cb0 + ncb) this launch accumulates; chain bit 0: add the partial sums an earlier launch left
-    // in y, bit 1: leave raw partial sums in y (no bias / ReLU / mask / addend) for a later launch - see dhz_winograd43_conv3x3
+    // in y, bit 1: leave raw partial sums in y (no bias / ReLU / mask / addend) for a later launch - see dhz_winograd43_conv3x3;
+    // blockIdx.y = sl (dhz_winograd43_conv3x3_slices; 0 in every other launch): the grid is gridDim.y copies of the plain grid, copy sl is the
+    // raw link (chain = 2) over the groups [cb0 + sl ncb, cb0 + (sl + 1) ncb) and stores to part sl of y.  The slice is folded into the operand
+    // bases and the output image index below (part stride = nblk 256 K floats = the images of one part), so nothing new lives across the
+    // channel loop; a workgroup's XCD is blockIdx.x & 7 in every slice, since the renumbering needs gridDim.x % 8 == 0.
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int t = threadIdx.x, lane = t & 63;
     const int w = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -144,6 +148,8 @@ __global__ __launch_bounds__(256, 1) void winograd43_conv3x3_kernel(const float*
     float* const pw = smem + NUBUF * UF + w * PFLOATS;             // this wave's patch slot
     float* const bias_s = smem + NUBUF * UF + 4 * PFLOATS;
     const int KBn = K / KB, CBn = C / CC;
+    const int sl = blockIdx.y;
+    cb0 += sl * ncb;
     int lid = blockIdx.x;
     if (xcd_group) lid = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
     const int kb = lid % KBn;
@@ -151,7 +157,8 @@ __global__ __launch_bounds__(256, 1) void winograd43_conv3x3_kernel(const float*
     const bool live = blk < nblk;                                  // ragged last workgroup: the extra waves recompute, store nothing
     if (!live) blk = nblk - 1;
     const int bx_n = W / 16, by_n = H / 16;
-    const int bimg = blk / (bx_n * by_n);
+    const int bimg_in = blk / (bx_n * by_n);
+    const int bimg = bimg_in + sl * (nblk / (bx_n * by_n));        // the image index of the STORE: part sl of y for a sliced launch
     const int by = (blk / bx_n) % by_n, bx = blk % bx_n;
     const int oy0 = by * 16, ox0 = bx * 16;                        // the wave's output block; patch origin (oy0 - 1, ox0 - 1)
     const size_t plane = (size_t)H * W * 8;                        // floats per (image, channel-group) plane
@@ -179,7 +186,7 @@ __global__ __launch_bounds__(256, 1) void winograd43_conv3x3_kernel(const float*
     }
     // request addresses as (wave-uniform base) + (unsigned 32-bit lane offset): the form global_load_lds takes with its base in SGPRs - no
     // vector instruction per request (a 64-bit vector add between two MFMAs costs its whole latency of matrix-pipe time: tools/ubench/overlap.hip)
-    const char* const xbase = reinterpret_cast<const char*>(x + ((size_t)bimg * CBn + cb0) * plane);
+    const char* const xbase = reinterpret_cast<const char*>(x + ((size_t)bimg_in * CBn + cb0) * plane);
     const char* const ubase = reinterpret_cast<const char*>(upack + ((size_t)kb * CBn + cb0) * UF);
     const unsigned lane16 = lane * 16;
     auto dma_patch_run = [&](int cb, int r) {
@@ -477,6 +484,36 @@ static int winograd43_launch(const char* who, const float* x, const float* upack
 #undef GO
     DHZ_CHECK_LAUNCH(who);
     return DHZ_OK;
+}
+
+// The accumulation chain links side by side: ONE grid of (the plain grid) x slices workgroups, slice s the raw link over the channel groups
+// [s CBn / slices, (s + 1) CBn / slices) into part s of workspace (slices * B * K * H * W floats), then the epilogue kernel of
+// csrc/winograd_conv.hip, which adds the parts in the chain's order: for two slices of 512 channels, the bits of dhz_winograd43_conv3x3.
+// For grids of half a round of workgroups or less (16 x 16 maps of 32 images).
+extern "C" int dhz_winograd43_conv3x3_slices(const float* x, const float* upack, const float* bias, int relu, const float* out_mask,
+                                             const float* out_addend, float* y, float* workspace, int slices, int B, int H, int W, int C,
+                                             int K, void* stream) {
+    const char* who = "dhz_winograd43_conv3x3_slices";
+    DHZ_REQUIRE(x && upack && y && workspace, "%s: null pointer", who);
+    DHZ_REQUIRE(B > 0 && H % 16 == 0 && W % 16 == 0 && H >= 16 && W >= 16 && C > 0 && K > 0 && C % 16 == 0 && K % KB == 0,
+                "%s: unsupported shape B=%d H=%d W=%d C=%d K=%d", who, B, H, W, C, K);
+    const bool fwd = !(out_mask || out_addend);
+    DHZ_REQUIRE(fwd || !(bias || relu), "%s: bias/relu and out_mask/out_addend are exclusive", who);
+    DHZ_REQUIRE((long long)H * W * 8 * (C / 8) < (1ll << 31), "%s: image too large", who);
+    const int CBn = C / CC;
+    DHZ_REQUIRE(slices >= 2 && slices <= 64 && CBn % slices == 0 && CBn / slices <= CHAIN_GROUPS,
+                "%s: slices=%d of %d channel groups (equal ranges of at most %d)", who, slices, CBn, CHAIN_GROUPS);
+    const long long nblk = (long long)B * (H / 16) * (W / 16);
+    const long long grid1 = ((nblk + 3) / 4) * (K / KB);
+    DHZ_REQUIRE(grid1 * slices < (1ll << 31) && nblk * slices < (1ll << 31) / 4, "%s: grid too large", who);
+    const int xcd_group = (grid1 % 8 == 0) ? 1 : 0;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&winograd43_conv3x3_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)W43_SMEM);
+    // the backward instance with neither mask nor addend: chain bit 1 makes both instances the same raw store
+    hipLaunchKernelGGL((winograd43_conv3x3_kernel<false>), dim3((unsigned)grid1, (unsigned)slices), dim3(256), W43_SMEM, (hipStream_t)stream,
+                       x, upack, nullptr, 0, nullptr, nullptr, workspace, H, W, C, K, (int)nblk, xcd_group, 0, CBn / slices, 2, nullptr);
+    DHZ_CHECK_LAUNCH(who);
+    return dhz_wino_slices_epilogue(who, workspace, slices, bias, relu, out_mask, out_addend, y, B, H, W, K, (hipStream_t)stream);
 }
 
 extern "C" int dhz_winograd43_conv3x3(const float* x, const float* upack, const float* bias, int relu, const float* out_mask,

@@ -70,15 +70,20 @@ __device__ __forceinline__ void wave_sync() {
 // LEAKY (dhz_winograd_conv3x3_act, the UNet baseline's ConvBlock M1:28-40): LeakyReLU(0.01) instead of ReLU.  Forward
 // y = leaky(conv(x) + bias) [+ addend] (the block's conv11 branch joins in the store); backward y = (conv(x) + addend) * (mask > 0 ? 1 : 0.01).
 // The instances without it are the ones that existed before: same code, same bits.
+//
+// RAW (dhz_winograd_conv3x3_slices, slices > 1): the grid is `slices` copies of the plain grid; copy s accumulates the channel groups
+// [s CBn / slices, (s + 1) CBn / slices) and stores its inverse-transformed sums, with no epilogue, to part s of a workspace at the addresses
+// the plain store uses; winograd_slices_epilogue_kernel adds the parts.  For launches whose plain grid leaves CUs idle: what such a launch
+// costs is the serial walk of one workgroup over the channel groups.  The instances without it see slices = 1 as a constant: same code.
 constexpr float LEAKY_SLOPE = 0.01f;
-template <bool FWD, bool Q8, bool LEAKY = false>
+template <bool FWD, bool Q8, bool LEAKY = false, bool RAW = false>
 __global__ __launch_bounds__(512) void winograd_conv3x3_kernel(const float* __restrict__ x,
                                                            const float* __restrict__ upack,
                                                            const float* __restrict__ bias, int relu,
                                                            const float* __restrict__ out_mask,
                                                            const float* __restrict__ out_addend,
                                                            float* __restrict__ y, int H, int W, int C, int K, int nblk, int xcd_group,
-                                                           int nimg) {
+                                                           int nimg, int slices) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, half = w >> 2, wl = w & 3;
     const int i16 = lane & 15, g = lane >> 4;
@@ -89,8 +94,13 @@ __global__ __launch_bounds__(512) void winograd_conv3x3_kernel(const float* __re
     // Workgroups are dealt round-robin over the 8 XCDs (private L2s).  xcd_group != 0: renumber so that consecutive
     // logical ids - the K/32 output-channel blocks of one spatial block pair, which read the same input patches - run on
     // the same XCD and the patch comes from HBM once instead of once per XCD.
-    int lid = blockIdx.x;
-    if (xcd_group) lid = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+    static_assert(!RAW || (!FWD && !LEAKY), "the raw store is the backward instance without mask and addend");
+    const int grid1 = RAW ? (int)gridDim.x / slices : (int)gridDim.x;      // the plain grid; RAW: slice sl = one copy of it
+    const int sl = RAW ? (int)blockIdx.x / grid1 : 0;
+    int lid = RAW ? (int)blockIdx.x - sl * grid1 : (int)blockIdx.x;
+    if (xcd_group) lid = (lid & 7) * (grid1 >> 3) + (lid >> 3);            // grid1 % 8 == 0: the XCD of a workgroup is lid & 7 in every slice
+    const int cbs = RAW ? sl * CBn / slices : 0;                           // this workgroup walks the groups [cbs, cbs + NG)
+    const int NG = RAW ? (sl + 1) * CBn / slices - cbs : CBn;
     const int kb = lid % KBn;
     int blk = (lid / KBn) * 2 + half;
     const bool live = blk < nblk;                       // odd block count: the last workgroup's second half recomputes, stores nothing
@@ -133,8 +143,8 @@ __global__ __launch_bounds__(512) void winograd_conv3x3_kernel(const float* __re
     }
     float4 rp[NP4];
     float4 ru0, ru1;                                     // UF / 4 / 512 = 2 filter float4 per thread
-    const float* xbase = x + (size_t)bimg * CBn * plane;
-    const float4* ubase = reinterpret_cast<const float4*>(upack + (size_t)kb * CBn * UF) + t;
+    const float* xbase = x + ((size_t)bimg * CBn + cbs) * plane;
+    const float4* ubase = reinterpret_cast<const float4*>(upack + ((size_t)kb * CBn + cbs) * UF) + t;
     auto gload_patch = [&](int cb) {
         const float* xp = xbase + (size_t)cb * plane;
 #pragma unroll
@@ -205,7 +215,7 @@ __global__ __launch_bounds__(512) void winograd_conv3x3_kernel(const float* __re
 #pragma unroll
     for (int i = 0; i < NP4; ++i) write_patch_slot(i);
     write_u(0);
-    { const int c1 = CBn > 1 ? 1 : 0; gload_patch(c1); gload_u(c1); }
+    { const int c1 = NG > 1 ? 1 : 0; gload_patch(c1); gload_u(c1); }
     wave_sync();
 #pragma unroll
     for (int a = 0; a < 4; ++a) read_row(a);
@@ -223,7 +233,7 @@ __global__ __launch_bounds__(512) void winograd_conv3x3_kernel(const float* __re
         constexpr bool WITH_NEXT = decltype(with_next)::value;
         const float* up = ufrag + (cb % NUBUF) * UF;
         const int nbuf = (cb + 1) % NUBUF;
-        const int cb2 = cb + 2 < CBn ? cb + 2 : CBn - 1;      // loads past the last group re-read it (never stored to LDS)
+        const int cb2 = cb + 2 < NG ? cb + 2 : NG - 1;      // loads past the last group re-read it (never stored to LDS)
         auto slot = [&](int sidx) {
             if (!WITH_NEXT) return;
             if ((WINO_ABL & 1) && sidx >= 13 && sidx <= 21) return;
@@ -308,8 +318,8 @@ __global__ __launch_bounds__(512) void winograd_conv3x3_kernel(const float* __re
         if (WITH_NEXT && !(WINO_ABL & 8)) { write_v2(12); write_v2(14); }
         wave_sync();
     };
-    for (int cb = 0; cb + 1 < CBn; ++cb) group(cb, std::true_type{});
-    group(CBn - 1, std::false_type{});
+    for (int cb = 0; cb + 1 < NG; ++cb) group(cb, std::true_type{});
+    group(NG - 1, std::false_type{});
 
     // ---- epilogue, wave-local: Y = A^T M A (lane-local), + bias, ReLU -> staging [32 k][4 x 16 px] over the wave's own
     //      V/patch region; then 32-byte-group stores, 512 contiguous bytes per (channel group, row)
@@ -346,6 +356,7 @@ __global__ __launch_bounds__(512) void winograd_conv3x3_kernel(const float* __re
     wave_sync();
     if (live) {
         const int KG = K / 8;
+        if (RAW) y += (size_t)sl * nimg * K * H * W;     // part sl of the workspace
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const int e = lane + 64 * i;
@@ -377,6 +388,45 @@ __global__ __launch_bounds__(512) void winograd_conv3x3_kernel(const float* __re
             *reinterpret_cast<float4*>(y + o) = v4;
         }
     }
+}
+
+// Sum of the `slices` raw parts a sliced launch (RAW above, or the F(4x4) kernel's parallel chain links) left in ws ([slices][n4] float4, each
+// part in the NCHW8c layout of y), then the store epilogue of the convolution kernels.  Order, fixed: r = p_0 + p_1 + ... + p_{S-2}, then
+// v = (p_{S-1} + bias) + r - the arithmetic of the F(4x4) accumulation chain, whose last link adds its bias and then the sums the earlier
+// links left (csrc/winograd43_conv.hip), so that two parallel links of 256 channels give the bits of the two chained launches.  One owner
+// lane per float4, no atomics: the same bits from run to run.
+template <bool FWD>
+__global__ __launch_bounds__(256) void winograd_slices_epilogue_kernel(const float4* __restrict__ ws, size_t n4, int slices,
+                                                                       const float* __restrict__ bias, int relu,
+                                                                       const float4* __restrict__ out_mask,
+                                                                       const float4* __restrict__ out_addend, float4* __restrict__ y,
+                                                                       int HW, int KG) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;          // float4 index: [b][k / 8][hw][half]
+    if (e >= n4) return;
+    float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (slices > 1) r = ws[e];
+    for (int s = 1; s + 1 < slices; ++s) {
+        const float4 p = ws[(size_t)s * n4 + e];
+        r.x += p.x; r.y += p.y; r.z += p.z; r.w += p.w;
+    }
+    float4 v = ws[(size_t)(slices - 1) * n4 + e];
+    if (FWD) {
+        float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (bias) b = *reinterpret_cast<const float4*>(bias + ((e >> 1) / HW % KG) * 8 + (e & 1) * 4);
+        v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w;
+    }
+    if (slices > 1) { v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w; }
+    if (FWD) {
+        const float lo = relu ? 0.f : -__builtin_inff();
+        v.x = fmaxf(v.x, lo); v.y = fmaxf(v.y, lo); v.z = fmaxf(v.z, lo); v.w = fmaxf(v.w, lo);
+    } else {
+        if (out_addend) { const float4 ad = out_addend[e]; v.x += ad.x; v.y += ad.y; v.z += ad.z; v.w += ad.w; }
+        if (out_mask) {
+            const float4 m = out_mask[e];
+            v.x = m.x > 0.f ? v.x : 0.f; v.y = m.y > 0.f ? v.y : 0.f; v.z = m.z > 0.f ? v.z : 0.f; v.w = m.w > 0.f ? v.w : 0.f;
+        }
+    }
+    y[e] = v;
 }
 
 // U = G g G^T for every (k, c), packed [k/32][c/8][xi 16][(c%8)/2][k%16][(k%32)/16][c%2] (the kernel's LDS order);
@@ -541,14 +591,44 @@ extern "C" int dhz_winograd_prepack(const float* weight, float* upack, int Kout,
     return DHZ_OK;
 }
 
-extern "C" int dhz_winograd_conv3x3(const float* x, const float* upack, const float* bias, int relu, const float* out_mask,
-                                    const float* out_addend, float* y, int B, int H, int W, int C, int K, void* stream) {
-    DHZ_REQUIRE(x && upack && y, "dhz_winograd_conv3x3: null pointer");
+// the epilogue of a sliced launch (also behind dhz_winograd43_conv3x3_slices): y = epilogue(sum of the parts in ws), see the kernel
+int dhz_wino_slices_epilogue(const char* who, const float* ws, int slices, const float* bias, int relu, const float* out_mask,
+                             const float* out_addend, float* y, int B, int H, int W, int K, hipStream_t s) {
+    const size_t n4 = (size_t)B * K * H * W / 4;
+    const dim3 grid((unsigned)((n4 + 255) / 256));
+    if (!(out_mask || out_addend))
+        hipLaunchKernelGGL(winograd_slices_epilogue_kernel<true>, grid, dim3(256), 0, s, reinterpret_cast<const float4*>(ws), n4, slices,
+                           bias, relu, nullptr, nullptr, reinterpret_cast<float4*>(y), H * W, K / 8);
+    else
+        hipLaunchKernelGGL(winograd_slices_epilogue_kernel<false>, grid, dim3(256), 0, s, reinterpret_cast<const float4*>(ws), n4, slices,
+                           nullptr, 0, reinterpret_cast<const float4*>(out_mask), reinterpret_cast<const float4*>(out_addend),
+                           reinterpret_cast<float4*>(y), H * W, K / 8);
+    DHZ_CHECK_LAUNCH(who);
+    return DHZ_OK;
+}
+
+// Slice count dhz_winograd_slices recommends: the largest S in {1, 2, 4} whose S copies of the plain grid fit the PHYSICAL CUs (these grids
+// are not persistent: a reservation does not shrink them) and leave every slice at least SLICE_MIN_GROUPS channel groups.
+// SLICE_MIN_GROUPS = 16: the shortest slice MEASURED to win (profiles/r08_wino_slices.txt, us per launch, sliced = launch + epilogue kernel):
+//     512 -> 512 on 8 x 8 maps      workgroups   plain    S = 2 (32 groups)   S = 4 (16 groups)
+//       64 images                      128       154.3         94.1            101.7  (512 workgroups: two rounds - the rule says 2)
+//       32 images, forward              64       149.1         86.2             54.2
+//       32 images, backward-data        64       153.1         87.8             55.3
+// The weight-gradient kernels' rule of 8 groups per part would only come into play for under-filled launches of 128 .. 256 channels, which
+// the step does not have and nobody has timed; a launch is about 25 us of prologue, epilogue and part traffic plus 2 us per group, so that
+// eight-group slices are expected to gain little - the constant stays at what the table shows.
+constexpr int SLICE_MIN_GROUPS = 16;
+
+static int winograd_launch(const char* who, const float* x, const float* upack, const float* bias, int relu, const float* out_mask,
+                           const float* out_addend, float* y, float* ws, int slices, int B, int H, int W, int C, int K, void* stream) {
+    DHZ_REQUIRE(x && upack && y, "%s: null pointer", who);
     const bool q8 = H == 8 && W == 8;                             // four 8 x 8 images per 16 x 16 block
     DHZ_REQUIRE(B > 0 && ((H % 16 == 0 && W % 16 == 0) || q8) && C % CC == 0 && K % KB == 0,
-                "dhz_winograd_conv3x3: unsupported shape B=%d H=%d W=%d C=%d K=%d", B, H, W, C, K);
+                "%s: unsupported shape B=%d H=%d W=%d C=%d K=%d", who, B, H, W, C, K);
     const bool fwd = !(out_mask || out_addend);
-    DHZ_REQUIRE(fwd || !(bias || relu), "dhz_winograd_conv3x3: bias/relu and out_mask/out_addend are exclusive");
+    DHZ_REQUIRE(fwd || !(bias || relu), "%s: bias/relu and out_mask/out_addend are exclusive", who);
+    DHZ_REQUIRE(slices >= 1 && slices <= C / CC && (slices == 1 || ws), "%s: slices=%d of %d channel groups, workspace %s", who, slices,
+                C / CC, ws ? "given" : "null");
     const int nblk = q8 ? (B + 3) / 4 : B * (H / 16) * (W / 16);  // 16x16-pixel output blocks, two per workgroup
     const int grid = ((nblk + 1) / 2) * (K / KB);
     hipStream_t s = (hipStream_t)stream;
@@ -566,13 +646,52 @@ extern "C" int dhz_winograd_conv3x3(const float* x, const float* upack, const fl
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&winograd_conv3x3_kernel<F, Q>),                   \
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)WINO_SMEM);                     \
         hipLaunchKernelGGL((winograd_conv3x3_kernel<F, Q>), dim3(grid), dim3(512), WINO_SMEM, s, x, upack, bias, relu, \
-                           out_mask, out_addend, y, H, W, C, K, nblk, xcd_group, B);                               \
+                           out_mask, out_addend, y, H, W, C, K, nblk, xcd_group, B, 1);                            \
     } while (0)
+#define GO_RAW(Q)                                                                                                  \
+    do {                                                                                                           \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&winograd_conv3x3_kernel<false, Q, false, true>),  \
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)WINO_SMEM);                     \
+        hipLaunchKernelGGL((winograd_conv3x3_kernel<false, Q, false, true>), dim3(grid * slices), dim3(512), WINO_SMEM, s, x, upack, \
+                           nullptr, 0, nullptr, nullptr, ws, H, W, C, K, nblk, xcd_group, B, slices);              \
+    } while (0)
+    if (slices > 1) {
+        DHZ_REQUIRE((long long)grid * slices < (1ll << 31), "%s: grid too large", who);
+        if (q8) GO_RAW(true); else GO_RAW(false);
+        DHZ_CHECK_LAUNCH(who);
+        return dhz_wino_slices_epilogue(who, ws, slices, bias, relu, out_mask, out_addend, y, B, H, W, K, s);
+    }
     if (q8) { if (fwd) GO(true, true); else GO(false, true); }
     else { if (fwd) GO(true, false); else GO(false, false); }
 #undef GO
-    DHZ_CHECK_LAUNCH("dhz_winograd_conv3x3");
+#undef GO_RAW
+    DHZ_CHECK_LAUNCH(who);
     return DHZ_OK;
+}
+
+extern "C" int dhz_winograd_conv3x3(const float* x, const float* upack, const float* bias, int relu, const float* out_mask,
+                                    const float* out_addend, float* y, int B, int H, int W, int C, int K, void* stream) {
+    return winograd_launch("dhz_winograd_conv3x3", x, upack, bias, relu, out_mask, out_addend, y, nullptr, 1, B, H, W, C, K, stream);
+}
+
+// The same convolution with the input-channel contraction cut into `slices` ranges of channel groups that run side by side (slices x the
+// plain grid) and leave raw sums in workspace (slices * B * K * H * W floats), then one epilogue kernel.  slices == 1 is the plain launch.
+extern "C" int dhz_winograd_conv3x3_slices(const float* x, const float* upack, const float* bias, int relu, const float* out_mask,
+                                           const float* out_addend, float* y, float* workspace, int slices, int B, int H, int W, int C,
+                                           int K, void* stream) {
+    return winograd_launch("dhz_winograd_conv3x3_slices", x, upack, bias, relu, out_mask, out_addend, y, workspace, slices, B, H, W, C, K,
+                           stream);
+}
+
+extern "C" int dhz_winograd_slices(int B, int H, int W, int C, int K) {
+    const bool q8 = H == 8 && W == 8;
+    if (B <= 0 || !((H % 16 == 0 && W % 16 == 0 && H > 0 && W > 0) || q8) || C <= 0 || K <= 0 || C % CC || K % KB) return 1;
+    const long long nblk = q8 ? (B + 3) / 4 : (long long)B * (H / 16) * (W / 16);
+    const long long grid = ((nblk + 1) / 2) * (K / KB);
+    const int cus = dhz_grid_cus() + dhz_get_reserved_cus();
+    for (int S = 4; S > 1; S >>= 1)
+        if (S * grid <= cus && (C / CC) / S >= SLICE_MIN_GROUPS) return S;
+    return 1;
 }
 
 // LeakyReLU(0.01) in the store.  backward != 0: y = (conv(x, W') + out_addend) * (out_mask > 0 ? 1 : 0.01) with out_mask the saved
@@ -594,7 +713,7 @@ extern "C" int dhz_winograd_conv3x3_act(const float* x, const float* upack, cons
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&winograd_conv3x3_kernel<F, Q, true>),                   \
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)WINO_SMEM);                           \
         hipLaunchKernelGGL((winograd_conv3x3_kernel<F, Q, true>), dim3(grid), dim3(512), WINO_SMEM, s, x, upack, bias, 0, \
-                           out_mask, out_addend, y, H, W, C, K, nblk, xcd_group, B);                                     \
+                           out_mask, out_addend, y, H, W, C, K, nblk, xcd_group, B, 1);                                  \
     } while (0)
     if (q8) { if (!backward) GO(true, true); else GO(false, true); }
     else { if (!backward) GO(true, false); else GO(false, false); }

@@ -7,6 +7,10 @@ images into one of its 16x16 blocks; for patch sizes whose conv-12 maps it does 
 falls back to the library).  The filters are frozen
 (My_CR.py:75-77), so their transform-domain forms (forward and backward-data) are prepacked once per device.
 
+Launches whose grid leaves CUs idle (the 8 x 8 maps; the 16 x 16 maps of the 32 differentiated images) run with their input-channel
+contraction cut into 2 or 4 slices side by side (dhz_winograd_conv3x3_slices, dhz_winograd43_conv3x3_slices) and one small kernel that adds
+the parts and applies the store epilogue - see SLICES_ON below (DHZ_WINO_SLICES=0: the plain launches).
+
 Forward-only passes (target / hazy input, My_CR.py:102) save nothing; the pass on the restored image is one autograd
 node whose backward walks the stack with the same kernel (rotated/transposed filters, ReLU mask fused into the patch
 load) - weight gradients are never formed (the reference freezes the VGG, My_CR.py:75-77).
@@ -94,6 +98,57 @@ def use_f43(B, H, W, Cin, Kout):
     return wgs >= 0.92 * rounds * cus          # the last round of workgroups nearly full
 
 
+# Channel slices (csrc/winograd_conv.hip RAW, csrc/winograd43_conv.hip SL): a launch whose grid leaves CUs idle - the 8 x 8 and 16 x 16 maps of
+# 32 or 64 images - costs the serial walk of ONE workgroup over all input-channel groups.  Such a launch runs as S copies of its grid, each over
+# 1 / S of the channel groups, into a workspace, and a small kernel adds the parts in a fixed order and applies the store epilogue.  Where
+# use_f43 refuses F(4x4) only because its grid is half a round or less, S parallel chain links fill the round (use_f43_slices); what is left
+# asks the library (dhz_winograd_slices) for the F(2x2) launch.  DHZ_WINO_SLICES=0 restores the plain launches (A/B switch).
+SLICES_ON = os.environ.get("DHZ_WINO_SLICES", "1") != "0"
+
+
+def _physical_cus():
+    return _lib.load().dhz_grid_cus() + _lib.load().dhz_get_reserved_cus()
+
+
+def f43_slices_rule(B, H, W, Cin, Kout, cus):
+    """Slice count (2 or 4; 0 = none) at which the F(4x4) kernel's parallel chain links fill one round of `cus` CUs where its plain grid is
+    half a round or less: the shape preconditions and the 0.92 rule of use_f43 on S x wgs <= cus workgroups, equal slices of SLICE_MIN_GROUPS
+    to 32 channel groups (one accumulation chain at the most).  The smallest such S: fewer parts to add, and S = 2 on 512 channels is the chained launch bit for bit."""
+    if H % 16 or W % 16 or H < 16 or W < 16 or Cin % 16 or Kout % 32:
+        return 0
+    wgs = (B * (H // 16) * (W // 16) + 3) // 4 * (Kout // 32)
+    rounds = (wgs + cus - 1) // cus
+    if wgs >= 0.92 * rounds * cus:                 # use_f43's own case: the plain launch
+        return 0
+    CBn = Cin // 8
+    for S in (2, 4):
+        # one round at the most: the parts travel through memory, which only pays for the small maps whose launch time is the serial walk
+        if CBn % S == 0 and SLICE_MIN_GROUPS <= CBn // S <= 32 and 0.92 * cus <= S * wgs <= cus:
+            return S
+    return 0
+
+
+def use_f43_slices(B, H, W, Cin, Kout):
+    return f43_slices_rule(B, H, W, Cin, Kout, _physical_cus()) if (F43_ON and SLICES_ON) else 0
+
+
+SLICE_MIN_GROUPS = 16         # csrc/winograd_conv.hip: the shortest slice measured to win
+
+
+def wino_slices_rule(B, H, W, C, K, cus):
+    """The rule of dhz_winograd_slices (the F(2x2) launch), restated for the host tests: the largest S in {1, 2, 4} whose S copies of the
+    plain grid fit `cus` CUs with at least SLICE_MIN_GROUPS channel groups per slice.  The dispatch asks the library."""
+    q8 = H == 8 and W == 8
+    if B <= 0 or not ((H % 16 == 0 and W % 16 == 0 and H > 0) or q8) or C % 8 or K % 32:
+        return 1
+    nblk = (B + 3) // 4 if q8 else B * (H // 16) * (W // 16)
+    grid = (nblk + 1) // 2 * (K // 32)
+    for S in (4, 2):
+        if S * grid <= cus and (C // 8) // S >= SLICE_MIN_GROUPS:
+            return S
+    return 1
+
+
 class VggEngine:
     def __init__(self, convs):
         """convs: the 13 nn.Conv2d modules of vgg19.features[0:30]."""
@@ -137,7 +192,9 @@ class VggEngine:
         B, CG, H, W, _ = xb.shape
         C, K = CONVS[i]
         f43 = allow43 and use_f43(B, H, W, C, K)
-        uf, _ = self.packed43(i, xb.device) if f43 else self.packed(i, xb.device)
+        s43 = use_f43_slices(B, H, W, C, K) if (allow43 and not f43) else 0
+        s22 = _lib.load().dhz_winograd_slices(B, H, W, C, K) if (SLICES_ON and not f43 and not s43) else 1
+        uf, _ = self.packed43(i, xb.device) if (f43 or s43) else self.packed(i, xb.device)
         if pool and f43:
             yp = torch.empty((B, K // 8, H // 2, W // 2, 8), device=xb.device, dtype=torch.float32)
             scratch = torch.empty((B, K // 8, H, W, 8), device=xb.device, dtype=torch.float32) if C > 256 else None
@@ -148,9 +205,14 @@ class VggEngine:
             return yp
         yb = torch.empty((B, K // 8, H, W, 8), device=xb.device, dtype=torch.float32)
         ev = ops._timed("dhz_winograd_conv3x3")
-        _lib.call("dhz_winograd43_conv3x3" if f43 else "dhz_winograd_conv3x3", _p(xb), _p(uf), _p(self.convs[i].bias), 1, None, None,
-                  _p(yb), B, H, W, C, K, _stream())
-        _timing_end(ev, B, H, W, C, K, f43)
+        if s43 or s22 > 1:
+            ws = torch.empty((s43 or s22, B, K // 8, H, W, 8), device=xb.device, dtype=torch.float32)
+            _lib.call("dhz_winograd43_conv3x3_slices" if s43 else "dhz_winograd_conv3x3_slices", _p(xb), _p(uf), _p(self.convs[i].bias), 1,
+                      None, None, _p(yb), _p(ws), s43 or s22, B, H, W, C, K, _stream())
+        else:
+            _lib.call("dhz_winograd43_conv3x3" if f43 else "dhz_winograd_conv3x3", _p(xb), _p(uf), _p(self.convs[i].bias), 1, None, None,
+                      _p(yb), B, H, W, C, K, _stream())
+        _timing_end(ev, B, H, W, C, K, f43 or bool(s43))
         return pool_fwd(yb) if pool else yb
 
     def conv_dgrad(self, i, gb, below_act=None, addend=None):
@@ -160,13 +222,21 @@ class VggEngine:
         B, KG, H, W, _ = gb.shape
         C, K = CONVS[i]
         f43 = use_f43(B, H, W, K, C)                       # the backward-data form: K input channels, C outputs
-        _, ub = self.packed43(i, gb.device) if f43 else self.packed(i, gb.device)
+        s43 = 0 if f43 else use_f43_slices(B, H, W, K, C)
+        s22 = _lib.load().dhz_winograd_slices(B, H, W, K, C) if (SLICES_ON and not f43 and not s43) else 1
+        _, ub = self.packed43(i, gb.device) if (f43 or s43) else self.packed(i, gb.device)
         dxb = torch.empty((B, C // 8, H, W, 8), device=gb.device, dtype=torch.float32)
+        mask = _p(below_act) if below_act is not None else None
+        add = addend.contiguous() if addend is not None else None
         ev = ops._timed("dhz_winograd_conv3x3")
-        _lib.call("dhz_winograd43_conv3x3" if f43 else "dhz_winograd_conv3x3", _p(gb), _p(ub), None, 0,
-                  _p(below_act) if below_act is not None else None,
-                  _p(addend.contiguous()) if addend is not None else None, _p(dxb), B, H, W, K, C, _stream())
-        _timing_end(ev, B, H, W, K, C, f43)
+        if s43 or s22 > 1:
+            ws = torch.empty((s43 or s22, B, C // 8, H, W, 8), device=gb.device, dtype=torch.float32)
+            _lib.call("dhz_winograd43_conv3x3_slices" if s43 else "dhz_winograd_conv3x3_slices", _p(gb), _p(ub), None, 0, mask,
+                      _p(add) if add is not None else None, _p(dxb), _p(ws), s43 or s22, B, H, W, K, C, _stream())
+        else:
+            _lib.call("dhz_winograd43_conv3x3" if f43 else "dhz_winograd_conv3x3", _p(gb), _p(ub), None, 0, mask,
+                      _p(add) if add is not None else None, _p(dxb), B, H, W, K, C, _stream())
+        _timing_end(ev, B, H, W, K, C, f43 or bool(s43))
         return dxb
 
     # ---- full stack, forward only
