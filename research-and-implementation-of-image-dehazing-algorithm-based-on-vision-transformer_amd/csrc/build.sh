@@ -19,7 +19,7 @@ objs=()
 pids=()
 for f in "$HERE"/*.hip; do
   o="$HERE/build/$(basename "${f%.hip}").o"
-  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ "$HERE/common.h" -nt "$o" ] || [ "$HERE/tok_epilogue.h" -nt "$o" ] || [ "$ROOT/include/dehaze_hip.h" -nt "$o" ] \
+  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ -n "$(find "$HERE" -maxdepth 1 -name '*.h' -newer "$o")" ] || [ "$ROOT/include/dehaze_hip.h" -nt "$o" ] \
      || { [ "$(basename "$f")" = api.hip ] && [ "$HERE/build/build_id.h" -nt "$o" ]; }; then
     echo "hipcc -c $(basename "$f")"
     rm -f "$o"                                   # a failed compile must not leave the previous object behind

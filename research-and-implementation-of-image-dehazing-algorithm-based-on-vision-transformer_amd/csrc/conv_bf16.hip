@@ -9,11 +9,9 @@
 //     weight grad    dWp += dy^T . col, db += column sums of dy                        dhz_linear_wgrad_bf16
 // At bf16 matrix rates these GEMMs are HBM-bound anyway (K = 16 Cin >= 1024); the patch matrix costs 4x the input in bf16 =
 // 2x the input in fp32 terms, written once and read by two of the GEMMs.
-#include "common.h"
+#include "bf16_pipe.h"
 
 namespace {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // one thread per 16-byte chunk (8 channels) of the patch matrix
 __global__ __launch_bounds__(256) void im2col_k4s2_bf16_kernel(const uint16_t* __restrict__ x, uint16_t* __restrict__ col, int B,
@@ -29,14 +27,14 @@ __global__ __launch_bounds__(256) void im2col_k4s2_bf16_kernel(const uint16_t* _
         r /= Wo;
         const int ho = (int)(r % Ho), b = (int)(r / Ho);
         const int hi = 2 * ho + (tap >> 2) - 1, wi = 2 * wo + (tap & 3) - 1;
-        u32x4 v = {0u, 0u, 0u, 0u};
+        dhz_u32x4 v = {0u, 0u, 0u, 0u};
         if (hi >= 0 && hi < H && wi >= 0 && wi < W)
-            v = *reinterpret_cast<const u32x4*>(x + (((size_t)b * H + hi) * W + wi) * Cin + 8 * c8);
-        *reinterpret_cast<u32x4*>(col + e * 8) = v;
+            v = *reinterpret_cast<const dhz_u32x4*>(x + (((size_t)b * H + hi) * W + wi) * Cin + 8 * c8);
+        *reinterpret_cast<dhz_u32x4*>(col + e * 8) = v;
     }
 }
 
-__device__ __forceinline__ void acc8(float (&s)[8], u32x4 v) {
+__device__ __forceinline__ void acc8(float (&s)[8], dhz_u32x4 v) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         s[2 * i] += __uint_as_float(v[i] << 16);
@@ -66,13 +64,13 @@ __global__ __launch_bounds__(256) void col2im_k4s2_bf16_kernel(const uint16_t* _
                 const int kx = ((w + 1) & 1) + 2 * c, wo = (w + 1 - kx) >> 1;
                 if (w + 1 - kx < 0 || wo >= Wo) continue;
                 const size_t row = ((size_t)b * Ho + ho) * Wo + wo;
-                acc8(s, *reinterpret_cast<const u32x4*>(dcol + (row * 16 + ky * 4 + kx) * Cin + 8 * c8));
+                acc8(s, *reinterpret_cast<const dhz_u32x4*>(dcol + (row * 16 + ky * 4 + kx) * Cin + 8 * c8));
             }
         }
-        u32x4 o;
+        dhz_u32x4 o;
 #pragma unroll
         for (int i = 0; i < 4; ++i) o[i] = (uint32_t)f32_to_bf16(s[2 * i]) | ((uint32_t)f32_to_bf16(s[2 * i + 1]) << 16);
-        *reinterpret_cast<u32x4*>(dx + e * 8) = o;
+        *reinterpret_cast<dhz_u32x4*>(dx + e * 8) = o;
     }
 }
 

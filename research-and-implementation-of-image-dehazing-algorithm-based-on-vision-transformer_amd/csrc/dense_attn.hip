@@ -229,12 +229,6 @@ __global__ __launch_bounds__(256) void dense_attn_bwd_kernel(
     }
 }
 
-template <typename Kern>
-void allow_smem(Kern kern, size_t bytes) {
-    if (bytes > 48 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
 }  // namespace
 
 extern "C" int dhz_dense_attn_fwd(const float* q, const float* k, const float* v, int ld, const float* bias,
@@ -250,11 +244,11 @@ extern "C" int dhz_dense_attn_fwd(const float* q, const float* k, const float* v
         hipLaunchKernelGGL(dense_attn_fwd_kernel<16>, dim3(B_ * H), dim3(256), sizeof(DenseFwdSmem<16>), s, q, k, v, ld,
                            bias, mask, out, ldo, H, nW, scale);
     } else if (d == 32) {
-        allow_smem(&dense_attn_fwd_kernel<32>, sizeof(DenseFwdSmem<32>));
+        dhz_allow_smem(&dense_attn_fwd_kernel<32>, sizeof(DenseFwdSmem<32>));
         hipLaunchKernelGGL(dense_attn_fwd_kernel<32>, dim3(B_ * H), dim3(256), sizeof(DenseFwdSmem<32>), s, q, k, v, ld,
                            bias, mask, out, ldo, H, nW, scale);
     } else {
-        allow_smem(&dense_attn_fwd_kernel<64>, sizeof(DenseFwdSmem<64>));
+        dhz_allow_smem(&dense_attn_fwd_kernel<64>, sizeof(DenseFwdSmem<64>));
         hipLaunchKernelGGL(dense_attn_fwd_kernel<64>, dim3(B_ * H), dim3(256), sizeof(DenseFwdSmem<64>), s, q, k, v, ld,
                            bias, mask, out, ldo, H, nW, scale);
     }
@@ -275,7 +269,7 @@ extern "C" int dhz_dense_attn_bwd(const float* q, const float* k, const float* v
     const int parts = dhz_ps_attn_bwd_parts(B_, H);
 #define LAUNCH(DD, HB)                                                                                              \
     do {                                                                                                            \
-        allow_smem(&dense_attn_bwd_kernel<DD, HB>, sizeof(DenseBwdSmem<DD>));                                       \
+        dhz_allow_smem(&dense_attn_bwd_kernel<DD, HB>, sizeof(DenseBwdSmem<DD>));                                   \
         hipLaunchKernelGGL((dense_attn_bwd_kernel<DD, HB>), dim3(parts), dim3(256), sizeof(DenseBwdSmem<DD>), s, q, \
                            k, v, ld, bias, mask, dout, ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW, scale);         \
     } while (0)

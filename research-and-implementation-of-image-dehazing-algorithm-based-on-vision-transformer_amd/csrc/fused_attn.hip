@@ -19,7 +19,7 @@
 // traffic per token instead of the 15C of the unfused forward chain; in inference mode only x is read and
 // out written (2C per token) and the kernel is bound by the fp32 MFMA rate (AI 50.7 FLOP/B at C = 32).
 #include <stdlib.h>
-#include "common.h"
+#include "bf16_pipe.h"
 
 namespace {
 
@@ -50,29 +50,6 @@ __device__ __forceinline__ float r8sum(float v) { v = r4sum(v); return v + dpp<0
 
 // ---- six-term projections (P6): the QKV product of a head on the bf16 matrix pipe, fp32-class (csrc/split6_gemm.hip's arithmetic:
 // three bf16 truncation pieces per operand value, products hh hm mh hl lh mm, dropped terms <= 2^-24 relative, fp32 accumulation)
-typedef __bf16 bf16x8_ __attribute__((ext_vector_type(8)));
-typedef short s16x8_ __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4_ __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void_;
-typedef const __attribute__((address_space(1))) void glb_void_;
-__device__ __forceinline__ f32x4 mfma_b16(u32x4_ a, u32x4_ b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_, a), __builtin_bit_cast(bf16x8_, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ uint32_t pack_top_(float x1, float x0) {              // (x1 & 0xffff0000) | (x0 >> 16)
-    return __builtin_amdgcn_perm(__float_as_uint(x1), __float_as_uint(x0), 0x07060302u);
-}
-// eight fp32 values -> their three bf16 pieces (hi + mid + lo == x exactly), packed as MFMA operands
-__device__ __forceinline__ void split8x3_(const float* x, u32x4_& hi, u32x4_& mid, u32x4_& lo) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float x0 = x[2 * i], x1 = x[2 * i + 1];
-        const float r0 = x0 - __uint_as_float(__float_as_uint(x0) & 0xffff0000u), r1 = x1 - __uint_as_float(__float_as_uint(x1) & 0xffff0000u);
-        const float q0 = r0 - __uint_as_float(__float_as_uint(r0) & 0xffff0000u), q1 = r1 - __uint_as_float(__float_as_uint(r1) & 0xffff0000u);
-        hi[i] = pack_top_(x1, x0);
-        mid[i] = pack_top_(r1, r0);
-        lo[i] = pack_top_(q1, q0);
-    }
-}
 constexpr int P6_RUNS = 36;            // 1 KiB runs (one per wave-wide 16-byte fragment read) of a head's QKV planes per 64 channels:
                                        // 6 column tiles x 2 k-blocks of 32 x 3 pieces
 
@@ -159,7 +136,7 @@ __global__ __launch_bounds__(256 * NW, NW == 2 ? 1 : (C == 64 ? 3 : (C == 128 ? 
     constexpr bool WREG = (C == 32) && FUSED_PERSIST_C32;
     constexpr bool WREG6 = WREG && P6;         // C = 32 with six-term products: the bf16 planes of all four weights live in registers (24 KiB per wave-set)
     float4 wr_qkv[(WREG && !P6) ? 12 : 1], wr_o[(WREG && !P6) ? 4 : 1];
-    u32x4_ w6r[WREG6 ? 6 : 1][3], wo6r[WREG6 ? 2 : 1][3];
+    dhz_u32x4 w6r[WREG6 ? 6 : 1][3], wo6r[WREG6 ? 2 : 1][3];
     if constexpr (WREG6) {
         // planes of dhz_fused_attn_prepack6 at C = 32: run ((j 3) + piece) for the six Q / K / V column tiles, then ((6 + tn) 3 + piece) for the
         // out-projection's two
@@ -167,11 +144,11 @@ __global__ __launch_bounds__(256 * NW, NW == 2 ? 1 : (C == 64 ? 3 : (C == 128 ? 
 #pragma unroll
         for (int j = 0; j < 6; ++j)
 #pragma unroll
-            for (int pc = 0; pc < 3; ++pc) w6r[j][pc] = *reinterpret_cast<const u32x4_*>(pl + (j * 3 + pc) * 1024);
+            for (int pc = 0; pc < 3; ++pc) w6r[j][pc] = *reinterpret_cast<const dhz_u32x4*>(pl + (j * 3 + pc) * 1024);
 #pragma unroll
         for (int tn = 0; tn < 2; ++tn)
 #pragma unroll
-            for (int pc = 0; pc < 3; ++pc) wo6r[tn][pc] = *reinterpret_cast<const u32x4_*>(pl + ((6 + tn) * 3 + pc) * 1024);
+            for (int pc = 0; pc < 3; ++pc) wo6r[tn][pc] = *reinterpret_cast<const dhz_u32x4*>(pl + ((6 + tn) * 3 + pc) * 1024);
     } else if constexpr (WREG) {
 #pragma unroll
         for (int i = 0; i < 12; ++i) wr_qkv[i] = wqkv_p[i * 64 + lane];
@@ -230,10 +207,10 @@ __global__ __launch_bounds__(256 * NW, NW == 2 ? 1 : (C == 64 ? 3 : (C == 128 ? 
         }
         // P6: the lane's A fragments as bf16 pieces; k-block kb (32 channels of the contraction, 8 per lane group) <-> channels
         // g C/4 + 8 kb + e - the same (arbitrary, consistent) order the planes are packed in
-        u32x4_ a6[P6 ? KS / 8 : 1][3];
+        dhz_u32x4 a6[P6 ? KS / 8 : 1][3];
         if constexpr (P6) {
 #pragma unroll
-            for (int kb = 0; kb < KS / 8; ++kb) split8x3_(&xa[8 * kb], a6[kb][0], a6[kb][1], a6[kb][2]);
+            for (int kb = 0; kb < KS / 8; ++kb) dhz_split8x3(&xa[8 * kb], a6[kb][0], a6[kb][1], a6[kb][2]);
         }
         f32x4 oacc[C / 16];                    // out-projection accumulators: rows 16w.., all C columns
 #pragma unroll
@@ -255,7 +232,7 @@ __global__ __launch_bounds__(256 * NW, NW == 2 ? 1 : (C == 64 ? 3 : (C == 128 ? 
 #pragma unroll
                     for (int term = 0; term < 6; ++term)
 #pragma unroll
-                        for (int j = 0; j < 6; ++j) acc[j] = mfma_b16(a6[0][TA[term]], w6r[j][TB[term]], acc[j]);
+                        for (int j = 0; j < 6; ++j) acc[j] = dhz_mfma_bf16(a6[0][TA[term]], w6r[j][TB[term]], acc[j]);
                 } else if constexpr (P6) {
                     unsigned char* const Bimg = reinterpret_cast<unsigned char*>(sm.q);       // q | k | v | s: 45 KiB contiguous, dead here
                     const unsigned char* const planes = reinterpret_cast<const unsigned char*>(wqkv_p);
@@ -266,7 +243,7 @@ __global__ __launch_bounds__(256 * NW, NW == 2 ? 1 : (C == 64 ? 3 : (C == 128 ? 
                         const unsigned char* src = planes + ((size_t)(h * (C / 64) + ch) * P6_RUNS) * 1024 + lane * 16;
 #pragma unroll
                         for (int r = 0; r < P6_RUNS / 4; ++r)
-                            __builtin_amdgcn_global_load_lds((glb_void_*)(src + (w + 4 * r) * 1024), (lds_void_*)(Bimg + (w + 4 * r) * 1024), 16, 0, 0);
+                            dhz_dma16(src + (w + 4 * r) * 1024, Bimg + (w + 4 * r) * 1024);
                         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                         __syncthreads();
 #pragma unroll
@@ -274,17 +251,17 @@ __global__ __launch_bounds__(256 * NW, NW == 2 ? 1 : (C == 64 ? 3 : (C == 128 ? 
                             const int kb = 2 * ch + kbl;
 #pragma unroll
                             for (int jg = 0; jg < 6; jg += 3) {                        // three column tiles at a time: 9 fragment reads, 18 MFMAs,
-                                u32x4_ bq[3][3];                                       // term-major (an accumulator is reused three MFMAs later)
+                                dhz_u32x4 bq[3][3];                                       // term-major (an accumulator is reused three MFMAs later)
 #pragma unroll
                                 for (int jj = 0; jj < 3; ++jj)
 #pragma unroll
                                     for (int pc = 0; pc < 3; ++pc)
-                                        bq[jj][pc] = *reinterpret_cast<const u32x4_*>(Bimg + (((jg + jj) * 2 + kbl) * 3 + pc) * 1024 + lane * 16);
+                                        bq[jj][pc] = *reinterpret_cast<const dhz_u32x4*>(Bimg + (((jg + jj) * 2 + kbl) * 3 + pc) * 1024 + lane * 16);
                                 constexpr int TA[6] = {2, 0, 1, 0, 1, 0}, TB[6] = {0, 2, 1, 1, 0, 0};      // (token piece, weight piece): lh hl mm hm mh hh
 #pragma unroll
                                 for (int term = 0; term < 6; ++term)
 #pragma unroll
-                                    for (int jj = 0; jj < 3; ++jj) acc[jg + jj] = mfma_b16(a6[kb][TA[term]], bq[jj][TB[term]], acc[jg + jj]);
+                                    for (int jj = 0; jj < 3; ++jj) acc[jg + jj] = dhz_mfma_bf16(a6[kb][TA[term]], bq[jj][TB[term]], acc[jg + jj]);
                             }
                         }
                     }
@@ -503,8 +480,7 @@ __global__ __launch_bounds__(256 * NW, NW == 2 ? 1 : (C == 64 ? 3 : (C == 128 ? 
                 const unsigned char* src = reinterpret_cast<const unsigned char*>(wqkv_p) + P6_QKV_BYTES + (size_t)h * P6O_RUNS * 1024 + lane * 16;
 #pragma unroll
                 for (int r = 0; r < P6O_RUNS / 4; ++r)
-                    __builtin_amdgcn_global_load_lds((glb_void_*)(src + (w + 4 * r) * 1024),
-                                                     (lds_void_*)(reinterpret_cast<unsigned char*>(sm.s) + (w + 4 * r) * 1024), 16, 0, 0);
+                    dhz_dma16(src + (w + 4 * r) * 1024, reinterpret_cast<unsigned char*>(sm.s) + (w + 4 * r) * 1024);
             }
             // ---- 2e. O_h = P V_h (32 x 32): one 16x16 tile per wave, into the dead Q tile
             float* O = sm.q;                       // 32 x HS (Q_h was last read before the first barrier of this head)
@@ -529,27 +505,27 @@ __global__ __launch_bounds__(256 * NW, NW == 2 ? 1 : (C == 64 ? 3 : (C == 128 ? 
                 ld4(&O[srow * HS + 8 * g], &a[0]);
                 ld4(&O[srow * HS + 8 * g + 4], &a[4]);
                 if constexpr (WREG6) {
-                    u32x4_ ao[3];
-                    split8x3_(a, ao[0], ao[1], ao[2]);
+                    dhz_u32x4 ao[3];
+                    dhz_split8x3(a, ao[0], ao[1], ao[2]);
                     constexpr int TA[6] = {2, 0, 1, 0, 1, 0}, TB[6] = {0, 2, 1, 1, 0, 0};
 #pragma unroll
                     for (int term = 0; term < 6; ++term)
 #pragma unroll
-                        for (int tn = 0; tn < 2; ++tn) oacc[tn] = mfma_b16(ao[TA[term]], wo6r[tn][TB[term]], oacc[tn]);
+                        for (int tn = 0; tn < 2; ++tn) oacc[tn] = dhz_mfma_bf16(ao[TA[term]], wo6r[tn][TB[term]], oacc[tn]);
                 } else if constexpr (P6O) {
-                    u32x4_ ao[3];
-                    split8x3_(a, ao[0], ao[1], ao[2]);                 // the lane's 8 consecutive k of its context row ARE a bf16 A fragment
+                    dhz_u32x4 ao[3];
+                    dhz_split8x3(a, ao[0], ao[1], ao[2]);                 // the lane's 8 consecutive k of its context row ARE a bf16 A fragment
                     const unsigned char* const Wimg = reinterpret_cast<const unsigned char*>(sm.s);
-                    u32x4_ bo6[C / 16][3];
+                    dhz_u32x4 bo6[C / 16][3];
 #pragma unroll
                     for (int tn = 0; tn < C / 16; ++tn)
 #pragma unroll
-                        for (int pc = 0; pc < 3; ++pc) bo6[tn][pc] = *reinterpret_cast<const u32x4_*>(Wimg + (tn * 3 + pc) * 1024 + lane * 16);
+                        for (int pc = 0; pc < 3; ++pc) bo6[tn][pc] = *reinterpret_cast<const dhz_u32x4*>(Wimg + (tn * 3 + pc) * 1024 + lane * 16);
                     constexpr int TA[6] = {2, 0, 1, 0, 1, 0}, TB[6] = {0, 2, 1, 1, 0, 0};
 #pragma unroll
                     for (int term = 0; term < 6; ++term)
 #pragma unroll
-                        for (int tn = 0; tn < C / 16; ++tn) oacc[tn] = mfma_b16(ao[TA[term]], bo6[tn][TB[term]], oacc[tn]);
+                        for (int tn = 0; tn < C / 16; ++tn) oacc[tn] = dhz_mfma_bf16(ao[TA[term]], bo6[tn][TB[term]], oacc[tn]);
                 } else if constexpr (WREG) {
 #pragma unroll
                     for (int s4 = 0; s4 < 2; ++s4) {

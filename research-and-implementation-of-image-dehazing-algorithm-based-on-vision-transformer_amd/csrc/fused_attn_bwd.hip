@@ -16,33 +16,23 @@
 // LDS 75 KB (two workgroups per CU): the regions of the attention-core backward (csrc/ps_attn.hip) with the projection phases
 // overlaid on them once they are dead, + the two backward-orientation weight images (16 KB).
 #include <stdlib.h>
-#include "common.h"
+#include "bf16_pipe.h"
 
 namespace {
 
 constexpr int NT = 64, NU = 25, SS = 68, DS = 36, C = 32;
 static_assert(NU + 1 + 4 <= 32, "the four waves' partials of the unselected sum sit in spare dO rows");
 
-__device__ __forceinline__ float row8_max(float v) {
-    v = fmaxf(v, __shfl_xor(v, 1));
-    v = fmaxf(v, __shfl_xor(v, 2));
-    return fmaxf(v, __shfl_xor(v, 4));
-}
-__device__ __forceinline__ float row8_sum(float v) {
-    v += __shfl_xor(v, 1);
-    v += __shfl_xor(v, 2);
-    return v + __shfl_xor(v, 4);
-}
 // the forward kernel's double softmax (csrc/fused_attn.hip step 2d), 8 columns per thread; scores arrive scaled
 __device__ __forceinline__ void double_softmax8(const float* x, const float* brow, const float* mrow, float* p1, float* p2) {
     float mx = x[0];
 #pragma unroll
     for (int i = 1; i < 8; ++i) mx = fmaxf(mx, x[i]);
-    mx = row8_max(mx);
+    mx = dhz_row8_max(mx);
     float e[8], sum = 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) { e[i] = __expf(x[i] - mx); sum += e[i]; }
-    sum = __builtin_amdgcn_rcpf(row8_sum(sum));
+    sum = __builtin_amdgcn_rcpf(dhz_row8_sum(sum));
     float a[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) { p1[i] = e[i] * sum; a[i] = p1[i]; }
@@ -57,11 +47,11 @@ __device__ __forceinline__ void double_softmax8(const float* x, const float* bro
     float mx2 = a[0];
 #pragma unroll
     for (int i = 1; i < 8; ++i) mx2 = fmaxf(mx2, a[i]);
-    mx2 = row8_max(mx2);
+    mx2 = dhz_row8_max(mx2);
     float sum2 = 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) { e[i] = __expf(a[i] - mx2); sum2 += e[i]; }
-    sum2 = __builtin_amdgcn_rcpf(row8_sum(sum2));
+    sum2 = __builtin_amdgcn_rcpf(dhz_row8_sum(sum2));
 #pragma unroll
     for (int i = 0; i < 8; ++i) p2[i] = e[i] * sum2;
 }
@@ -341,11 +331,11 @@ __global__ __launch_bounds__(256, 2) void fused_window_attn_bwd_c32_kernel(
                 dp[i] = sm.dsb[r * SS + c0 + i]; p1[i] = sm.p1[r * SS + c0 + i]; p2[i] = sm.p2[r * SS + c0 + i];
                 dot2 += dp[i] * p2[i];
             }
-            dot2 = row8_sum(dot2);
+            dot2 = dhz_row8_sum(dot2);
             float da[8], dot1 = 0.f;
 #pragma unroll
             for (int i = 0; i < 8; ++i) { da[i] = p2[i] * (dp[i] - dot2); dot1 += da[i] * p1[i]; }
-            dot1 = row8_sum(dot1);
+            dot1 = dhz_row8_sum(dot1);
             if (HAS_BIAS) {
 #pragma unroll
                 for (int i = 0; i < 8; ++i) sm.p2[r * SS + c0 + i] = da[i];

@@ -17,7 +17,7 @@
 //   * the MFMAs take the weight fragment as their first operand (a 16 x 16 block arrives transposed) and the weight rows are read in a
 //     permuted order, so a lane owns 8 consecutive features of a token: 16-byte bf16 stores (as csrc/linear_bf16.hip).
 #include <stdlib.h>
-#include "common.h"
+#include "bf16_pipe.h"
 #include "tok_epilogue.h"
 
 #ifndef BFP_ABL
@@ -25,12 +25,6 @@
 #endif
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void glb_void;
 
 constexpr int NCOMP = 8;                               // multiplying waves (4 x 2)
 constexpr int BM = 256, BN = 128, BKS = 64;            // tile; contraction elements per stage (two 32-element halves)
@@ -40,12 +34,6 @@ constexpr int SLOT = 2 * (A_HALF + B_HALF);            // 48 KB
 constexpr int RING = 3;
 constexpr int NSUB = (BM + BN) / 16;                   // 16-row groups per stage (one DMA instruction per group and half): 24
 
-__device__ __forceinline__ f32x4 mfma_bf16(s16x8 a, s16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ void dma16(const void* g, void* l) {
-    __builtin_amdgcn_global_load_lds((glb_void*)g, (lds_void*)l, 16, 0, 0);
-}
 // 64-byte-row images: the four 16-byte chunks of a row are XORed with P[key], P = {0, 2, 3, 1}.  Token image: key = (row >> 2) & 3 -
 // the 16 consecutive rows of a fragment read land on 16 different 16-byte bank groups.  Weight image: its fragment reads take the
 // rows base + 8 q + p (q, p in 0..3; perm_row below), so the key is (row >> 3) & 3.
@@ -138,8 +126,8 @@ __global__ __launch_bounds__(64 * (NCOMP + NLOAD), 1) void gemm_bf16_pipe_kernel
 #pragma unroll
             for (int u = 0; u < SPL; ++u) {
                 const bool tok = (lw + NLOAD * u) < BM / 16;
-                dma16(dp[u] + k0, S + d_dst[u]);
-                dma16(dp[u] + k0 + 32, S + d_dst[u] + (tok ? A_HALF : B_HALF));
+                dhz_dma16(dp[u] + k0, S + d_dst[u]);
+                dhz_dma16(dp[u] + k0 + 32, S + d_dst[u] + (tok ? A_HALF : B_HALF));
             }
         };
         dma_stage(p0, 0);
@@ -206,12 +194,12 @@ __global__ __launch_bounds__(64 * (NCOMP + NLOAD), 1) void gemm_bf16_pipe_kernel
             for (int h = 0; h < WN / 2; ++h) {
                 const f32x4 v0 = acc[a][2 * h] + *reinterpret_cast<const f32x4*>(bsm + n0 + 32 * h);
                 const f32x4 v1 = acc[a][2 * h + 1] + *reinterpret_cast<const f32x4*>(bsm + n0 + 32 * h + 4);
-                u32x4 r;
+                dhz_u32x4 r;
                 r[0] = (uint32_t)f32_to_bf16(v0[0]) | ((uint32_t)f32_to_bf16(v0[1]) << 16);
                 r[1] = (uint32_t)f32_to_bf16(v0[2]) | ((uint32_t)f32_to_bf16(v0[3]) << 16);
                 r[2] = (uint32_t)f32_to_bf16(v1[0]) | ((uint32_t)f32_to_bf16(v1[1]) << 16);
                 r[3] = (uint32_t)f32_to_bf16(v1[2]) | ((uint32_t)f32_to_bf16(v1[3]) << 16);
-                u32x4* dst = reinterpret_cast<u32x4*>(c0 + (size_t)(16 * a) * ldc + 32 * h);
+                dhz_u32x4* dst = reinterpret_cast<dhz_u32x4*>(c0 + (size_t)(16 * a) * ldc + 32 * h);
                 if (BFP_ABL & 1) { if (r[0] == 0x12345678u) *dst = r; }            // (keeps the results alive)
                 else if (full || m0 + 16 * a < M) {
                     if constexpr (NTS) __builtin_nontemporal_store(r, dst);
@@ -231,14 +219,14 @@ __global__ __launch_bounds__(64 * (NCOMP + NLOAD), 1) void gemm_bf16_pipe_kernel
         const unsigned char* S = smem + slot * SLOT;
         // fragments: the weight side of both halves (2 x 4), the token side two at a time (the next one is read while the current one
         // multiplies) - 40 registers instead of 64 for everything at once
-        s16x8 bf[2][WN], af[2];
+        dhz_s16x8 bf[2][WN], af[2];
         auto rd_b = [&](int h, int b) {
-            if constexpr (BFP_ABL & 8) bf[h][b] = s16x8{(short)lane, 1, 2, 3, 4, 5, 6, 7};
-            else bf[h][b] = *reinterpret_cast<const s16x8*>(S + h * B_HALF + fb[b]);
+            if constexpr (BFP_ABL & 8) bf[h][b] = dhz_s16x8{(short)lane, 1, 2, 3, 4, 5, 6, 7};
+            else bf[h][b] = *reinterpret_cast<const dhz_s16x8*>(S + h * B_HALF + fb[b]);
         };
         auto rd_a = [&](int k) {                        // step k = 4 h + a
-            if constexpr (BFP_ABL & 8) af[k & 1] = s16x8{(short)lane, 1, 2, 3, 4, 5, 6, 7};
-            else af[k & 1] = *reinterpret_cast<const s16x8*>(S + (k >> 2) * A_HALF + fa[k & 3]);
+            if constexpr (BFP_ABL & 8) af[k & 1] = dhz_s16x8{(short)lane, 1, 2, 3, 4, 5, 6, 7};
+            else af[k & 1] = *reinterpret_cast<const dhz_s16x8*>(S + (k >> 2) * A_HALF + fa[k & 3]);
         };
 #pragma unroll
         for (int b = 0; b < WN; ++b) rd_b(0, b);
@@ -251,7 +239,7 @@ __global__ __launch_bounds__(64 * (NCOMP + NLOAD), 1) void gemm_bf16_pipe_kernel
 #pragma unroll
             for (int b = 0; b < WN; ++b) {
                 if constexpr (BFP_ABL & 2) asm volatile("" : "+v"(acc[k & 3][b]) : "v"(bf[k >> 2][b]), "v"(af[k & 1]));
-                else acc[k & 3][b] = mfma_bf16(bf[k >> 2][b], af[k & 1], acc[k & 3][b]);
+                else acc[k & 3][b] = dhz_mfma_bf16(bf[k >> 2][b], af[k & 1], acc[k & 3][b]);
             }
         }
         __builtin_amdgcn_sched_group_barrier(0x100, 5, 0);

@@ -17,7 +17,7 @@
 // Grid numbering: the 4C / 32 channel groups of a tile all read the same rows of dy; workgroups are dealt round-robin to the 8 XCDs and
 // are renumbered (as leff_dwconv_fwd_kernel does) so that a tile's channel groups share one XCD's L2.  DHZ_DWZ_PLAIN_ORDER in the
 // environment keeps the plain order (diagnostics, tools/bench_leff_bwd_dz.py).
-#include "common.h"
+#include "bf16_pipe.h"
 #include <stdlib.h>
 
 namespace {

@@ -18,7 +18,7 @@
 // on one of the two GEMMs) - the price of never writing u or z for the consumer to read back.
 // LDS images of MFMA operands are [row][k] with the 16-byte k-quads XOR-swizzled (swz below) so that a lane's four
 // consecutive k come from one ds_read_b128; MFMA j of a 16-deep step contracts over k = 16 s + 4 (lane >> 4) + j.
-#include "common.h"
+#include "bf16_pipe.h"
 
 namespace {
 

@@ -14,7 +14,7 @@
 //     lane 4 q + p of a 16-lane group addresses row r0 + q, columns 4 p .. 4 p + 3 of a 4 x 16 block and receives column
 //     (lane & 15), rows r0 .. r0 + 3.
 // Forward / backward-data: persistent workgroups pipelined across tiles (as csrc/linear_gemm.hip); outputs leave as bf16.
-#include "common.h"
+#include "bf16_pipe.h"
 #include "tok_epilogue.h"
 
 #ifndef BF_ABL
@@ -25,11 +25,6 @@ bool dhz_gemm_bf16_pipe_try(const uint16_t* A, int lda, const uint16_t* B, int l
                             int KC, hipStream_t s, const TokEpi* epi);          // csrc/gemm_bf16_pipe.hip (epi: residual epilogue or null)
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BK = 64;
 #ifndef BF_WABL
@@ -45,9 +40,6 @@ constexpr int BK = 64;
 #define BF_WSPLIT 2     // workgroups per CU the token split aims at
 #endif
 
-__device__ __forceinline__ f32x4 mfma_bf16(s16x8 a, s16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 // byte offset of 16-byte chunk ch of row `row` in a K-contiguous image (128-B rows)
 __device__ __forceinline__ int off_row(int row, int ch) { return row * 128 + 16 * (ch ^ ((row >> 1) & 7)); }
 // The same for the feature-major B image of the forward / backward-data kernels, whose rows are read in the order
@@ -58,21 +50,6 @@ __device__ __forceinline__ int off_row(int row, int ch) { return row * 128 + 16 
 // (row >> 1) & 7 does for 16 consecutive rows.
 __device__ __forceinline__ int off_rowp(int row, int ch) { return row * 128 + 16 * (ch ^ ((((row >> 3) & 3) << 1) | ((row >> 1) & 1))); }
 __device__ __forceinline__ int perm_row(int b, int r) { return 32 * (b >> 1) + 8 * (r >> 2) + 4 * (b & 1) + (r & 3); }
-// byte offset of 16-byte chunk ch of contraction row `row` in a contraction-major image with F features per row
-template <int F>
-__device__ __forceinline__ int off_tr(int row, int ch) {
-    if (F == 128) return row * 256 + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
-    return row * 128 + 16 * (ch ^ ((row & 2) | ((row & 8) >> 1)));
-}
-// fragment (8 contraction rows r0 .. r0 + 7 of feature column 16 cb + (lane & 15)) from a contraction-major image
-template <int F>
-__device__ __forceinline__ s16x8 tr_frag(const unsigned char* img, int r0, int cb, int lane) {
-    const int m = lane & 15, q = m >> 2, p = m & 3;
-    typedef s16x4 __attribute__((address_space(3))) * lds_ptr;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(img + off_tr<F>(r0 + q, 2 * cb + (p >> 1)) + 8 * (p & 1)));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(img + off_tr<F>(r0 + 4 + q, 2 * cb + (p >> 1)) + 8 * (p & 1)));
-    return s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
 
 // ------------------------------------------------------------------------------------------------ forward / backward-data
 // C[M,N] = A[M,K] . op(B) (+ bias), A K-contiguous.  BTR = false: B is [N][K] (forward); true: B is [K][N] (backward-data).
@@ -104,7 +81,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(const uint16_t* __restri
 #pragma unroll
         for (int b = 0; b < WN; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    u32x4 ra[NA], rb[NB];
+    dhz_u32x4 ra[NA], rb[NB];
     const uint16_t* pa[NA];
     const uint16_t* pb[NB];
     auto set_tile = [&](int tile) {
@@ -125,9 +102,9 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(const uint16_t* __restri
     auto gload = [&](int k0) {
         if (BF_ABL & 4) return;
 #pragma unroll
-        for (int i = 0; i < NA; ++i) ra[i] = *reinterpret_cast<const u32x4*>(pa[i] + k0);
+        for (int i = 0; i < NA; ++i) ra[i] = *reinterpret_cast<const dhz_u32x4*>(pa[i] + k0);
 #pragma unroll
-        for (int i = 0; i < NB; ++i) rb[i] = *reinterpret_cast<const u32x4*>(pb[i] + (BTR ? (size_t)k0 * ldb : (size_t)k0));
+        for (int i = 0; i < NB; ++i) rb[i] = *reinterpret_cast<const dhz_u32x4*>(pb[i] + (BTR ? (size_t)k0 * ldb : (size_t)k0));
     };
     auto swrite = [&](int buf) {
         unsigned char* As = smem + buf * STAGE;
@@ -135,7 +112,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(const uint16_t* __restri
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
             const int e = t + 256 * i;
-            *reinterpret_cast<u32x4*>(As + off_row(e >> 3, e & 7)) = ra[i];
+            *reinterpret_cast<dhz_u32x4*>(As + off_row(e >> 3, e & 7)) = ra[i];
         }
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
@@ -145,11 +122,11 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(const uint16_t* __restri
                 // (physical columns 32 B + 4 q + p and 32 B + 16 + 4 q + p): two 8-byte writes
                 const int kr = e / (BN / 8), fc = e % (BN / 8);
                 const int B2 = fc >> 2, q = fc & 3;
-                unsigned char* d0 = Bs + off_tr<BN>(kr, 4 * B2 + (q >> 1)) + 8 * (q & 1);
-                unsigned char* d1 = Bs + off_tr<BN>(kr, 4 * B2 + 2 + (q >> 1)) + 8 * (q & 1);
+                unsigned char* d0 = Bs + dhz_off_tr<BN>(kr, 4 * B2 + (q >> 1)) + 8 * (q & 1);
+                unsigned char* d1 = Bs + dhz_off_tr<BN>(kr, 4 * B2 + 2 + (q >> 1)) + 8 * (q & 1);
                 *reinterpret_cast<uint2*>(d0) = uint2{rb[i][0], rb[i][1]};
                 *reinterpret_cast<uint2*>(d1) = uint2{rb[i][2], rb[i][3]};
-            } else *reinterpret_cast<u32x4*>(Bs + off_rowp(e >> 3, e & 7)) = rb[i];
+            } else *reinterpret_cast<dhz_u32x4*>(Bs + off_rowp(e >> 3, e & 7)) = rb[i];
         }
     };
 
@@ -178,21 +155,21 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(const uint16_t* __restri
             const unsigned char* Bs = As + A_BYTES;
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
-                s16x8 af[WM], bf[WN];
+                dhz_s16x8 af[WM], bf[WN];
 #pragma unroll
                 for (int a = 0; a < WM; ++a)
-                    af[a] = *reinterpret_cast<const s16x8*>(As + (wm * WM * 16 + a * 16 + i16) * 128 + 16 * ((4 * s + g) ^ sw));
+                    af[a] = *reinterpret_cast<const dhz_s16x8*>(As + (wm * WM * 16 + a * 16 + i16) * 128 + 16 * ((4 * s + g) ^ sw));
 #pragma unroll
                 for (int b = 0; b < WN; ++b) {
-                    if (BTR) bf[b] = tr_frag<BN>(Bs, 32 * s + 8 * g, wn * WN + b, lane);
-                    else bf[b] = *reinterpret_cast<const s16x8*>(Bs + off_rowp(wn * WN * 16 + perm_row(b, i16), 4 * s + g));
+                    if (BTR) bf[b] = dhz_tr_frag<BN>(Bs, 32 * s + 8 * g, wn * WN + b, lane);
+                    else bf[b] = *reinterpret_cast<const dhz_s16x8*>(Bs + off_rowp(wn * WN * 16 + perm_row(b, i16), 4 * s + g));
                 }
 #pragma unroll
                 for (int a = 0; a < WM; ++a)
 #pragma unroll
                     for (int b = 0; b < WN; ++b) {
                         if (BF_ABL & 2) acc[a][b][0] += (float)(af[a][0] + bf[b][0]);
-                        else acc[a][b] = mfma_bf16(bf[b], af[a], acc[a][b]);    // D = C^T block (epilogue)
+                        else acc[a][b] = dhz_mfma_bf16(bf[b], af[a], acc[a][b]);    // D = C^T block (epilogue)
                     }
             }
             if (more) {
@@ -211,7 +188,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(const uint16_t* __restri
             uint16_t* c0 = C + (size_t)m0 * ldc + n0;
             auto pack = [&](int a, int h) {
                 const f32x4 v0 = acc[a][2 * h] + bv[2 * h], v1 = acc[a][2 * h + 1] + bv[2 * h + 1];
-                u32x4 r;
+                dhz_u32x4 r;
                 r[0] = (uint32_t)f32_to_bf16(v0[0]) | ((uint32_t)f32_to_bf16(v0[1]) << 16);
                 r[1] = (uint32_t)f32_to_bf16(v0[2]) | ((uint32_t)f32_to_bf16(v0[3]) << 16);
                 r[2] = (uint32_t)f32_to_bf16(v1[0]) | ((uint32_t)f32_to_bf16(v1[1]) << 16);
@@ -235,13 +212,13 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(const uint16_t* __restri
                 for (int a = 0; a < WM; ++a)
 #pragma unroll
                     for (int h = 0; h < WN / 2; ++h)
-                        if (!(BF_ABL & 1) || acc[a][0][0] == 12345.678f) *reinterpret_cast<u32x4*>(c0 + (size_t)(16 * a) * ldc + 32 * h) = pack(a, h);
+                        if (!(BF_ABL & 1) || acc[a][0][0] == 12345.678f) *reinterpret_cast<dhz_u32x4*>(c0 + (size_t)(16 * a) * ldc + 32 * h) = pack(a, h);
             } else {
 #pragma unroll
                 for (int a = 0; a < WM; ++a)
                     if (m0 + 16 * a < M) {
 #pragma unroll
-                        for (int h = 0; h < WN / 2; ++h) *reinterpret_cast<u32x4*>(c0 + (size_t)(16 * a) * ldc + 32 * h) = pack(a, h);
+                        for (int h = 0; h < WN / 2; ++h) *reinterpret_cast<dhz_u32x4*>(c0 + (size_t)(16 * a) * ldc + 32 * h) = pack(a, h);
                     }
             }
 #pragma unroll
@@ -353,7 +330,7 @@ __global__ __launch_bounds__(256 * G) void wgrad_bf16_kernel(const uint16_t* __r
     for (int a = 0; a < WM; ++a)
 #pragma unroll
         for (int b = 0; b < WN; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-    u32x4 ra[NA], rb[NB];
+    dhz_u32x4 ra[NA], rb[NB];
     float dbacc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};     // column sums of this thread's 8 dy columns (chunk t % (FM/8))
     const bool do_db = (db != nullptr) && (tn == 0);
 
@@ -362,12 +339,12 @@ __global__ __launch_bounds__(256 * G) void wgrad_bf16_kernel(const uint16_t* __r
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
             const int e = t + 256 * i;
-            ra[i] = *reinterpret_cast<const u32x4*>(dy + (tok0 + e / (FM / 8)) * ldy + n0 + 8 * (e % (FM / 8)));
+            ra[i] = *reinterpret_cast<const dhz_u32x4*>(dy + (tok0 + e / (FM / 8)) * ldy + n0 + 8 * (e % (FM / 8)));
         }
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
             const int e = t + 256 * i;
-            rb[i] = *reinterpret_cast<const u32x4*>(x + (tok0 + e / (FN / 8)) * ldx + k0 + 8 * (e % (FN / 8)));
+            rb[i] = *reinterpret_cast<const dhz_u32x4*>(x + (tok0 + e / (FN / 8)) * ldx + k0 + 8 * (e % (FN / 8)));
         }
     };
     auto swrite = [&](int buf) {
@@ -376,7 +353,7 @@ __global__ __launch_bounds__(256 * G) void wgrad_bf16_kernel(const uint16_t* __r
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
             const int e = t + 256 * i;
-            *reinterpret_cast<u32x4*>(As + off_tr<FM>(e / (FM / 8), e % (FM / 8))) = ra[i];
+            *reinterpret_cast<dhz_u32x4*>(As + dhz_off_tr<FM>(e / (FM / 8), e % (FM / 8))) = ra[i];
             if (do_db) {
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
@@ -388,7 +365,7 @@ __global__ __launch_bounds__(256 * G) void wgrad_bf16_kernel(const uint16_t* __r
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
             const int e = t + 256 * i;
-            *reinterpret_cast<u32x4*>(Bs + off_tr<FN>(e / (FN / 8), e % (FN / 8))) = rb[i];
+            *reinterpret_cast<dhz_u32x4*>(Bs + dhz_off_tr<FN>(e / (FN / 8), e % (FN / 8))) = rb[i];
         }
     };
 
@@ -407,15 +384,15 @@ __global__ __launch_bounds__(256 * G) void wgrad_bf16_kernel(const uint16_t* __r
         if (have) {
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
-                s16x8 af[WM], bf[WN];
+                dhz_s16x8 af[WM], bf[WN];
 #pragma unroll
-                for (int a = 0; a < WM; ++a) af[a] = tr_frag<FM>(As, 32 * s + 8 * g, wm * WM + a, lane);
+                for (int a = 0; a < WM; ++a) af[a] = dhz_tr_frag<FM>(As, 32 * s + 8 * g, wm * WM + a, lane);
 #pragma unroll
-                for (int b = 0; b < WN; ++b) bf[b] = tr_frag<FN>(Bs, 32 * s + 8 * g, wn * WN + b, lane);
+                for (int b = 0; b < WN; ++b) bf[b] = dhz_tr_frag<FN>(Bs, 32 * s + 8 * g, wn * WN + b, lane);
 #pragma unroll
                 for (int a = 0; a < WM; ++a)
 #pragma unroll
-                    for (int b = 0; b < WN; ++b) { if (!(BF_WABL & 1)) acc[a][b] = mfma_bf16(af[a], bf[b], acc[a][b]); }
+                    for (int b = 0; b < WN; ++b) { if (!(BF_WABL & 1)) acc[a][b] = dhz_mfma_bf16(af[a], bf[b], acc[a][b]); }
             }
         }
         if (more) swrite(buf ^ 1);

@@ -31,7 +31,7 @@
 // Workgroups are persistent (two per CU) and treat their (tile, stage) pairs as one stream.
 #include <stdio.h>
 #include <stdlib.h>
-#include "common.h"
+#include "bf16_pipe.h"
 
 namespace {
 
@@ -43,12 +43,6 @@ constexpr int BK = 32;
 #ifndef DHZ_GEMM_PRIO
 #define DHZ_GEMM_PRIO 0          // experiment switch: 1 = s_setprio 1 in the first half of a stage (no DMA), 0 in the second; 2 = the reverse
 #endif
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void glb_void;
-// 16 bytes per lane, global -> LDS: the LDS address is wave-uniform (M0) + 16 * lane, the global address is per lane
-__device__ __forceinline__ void dma16(const float* g, float* l) {
-    __builtin_amdgcn_global_load_lds((glb_void*)g, (lds_void*)l, 16, 0, 0);
-}
 
 #ifdef DHZ_GEMM_STAMP      // timing diagnostics only (tools/micro/stamp_gemm.py builds its own copy): s_memtime at the phase boundaries,
                            // kept in LDS (a global store per stamp would sit in vmcnt and be waited for) and dumped at the end
@@ -163,10 +157,10 @@ __global__ __launch_bounds__(256) void linear_gemm_kernel(const float* __restric
                 const int row = 8 * (w * WM + idx) + lrow;
                 off += (min(src.m0 + row, M - 1) - src.m0 - row) * lda;
             }
-            dma16(src.a + off, As + (w * WM + idx) * 256);
+            dhz_dma16(src.a + off, As + (w * WM + idx) * 256);
         } else {
             const int i = idx - WM;
-            dma16(src.b + offB[i < WN ? i : 0], As + A_FLOATS + (w * WN + i) * 256);
+            dhz_dma16(src.b + offB[i < WN ? i : 0], As + A_FLOATS + (w * WN + i) * 256);
         }
     };
 

@@ -16,100 +16,14 @@
 // LDS images and fragment reads are those of csrc/linear_bf16.hip (one hi and one lo image per operand); operands and results stay
 // fp32 in HBM.
 #include <stdlib.h>
-#include "common.h"
+#include "bf16_pipe.h"
 #include "tok_epilogue.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int BK = 64;
 
-__device__ __forceinline__ f32x4 mfma_bf16(s16x8 a, s16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 __device__ __forceinline__ int off_row(int row, int ch) { return row * 128 + 16 * (ch ^ ((row >> 1) & 7)); }
-template <int F>
-__device__ __forceinline__ int off_tr(int row, int ch) {
-    if (F >= 128) return row * (2 * F) + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));   // 256 / 512-byte rows: XOR on the low four chunk bits
-    return row * 128 + 16 * (ch ^ ((row & 2) | ((row & 8) >> 1)));
-}
-template <int F>
-__device__ __forceinline__ s16x8 tr_frag(const unsigned char* img, int r0, int cb, int lane) {
-    const int m = lane & 15, q = m >> 2, p = m & 3;
-    typedef s16x4 __attribute__((address_space(3))) * lds_ptr;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(img + off_tr<F>(r0 + q, 2 * cb + (p >> 1)) + 8 * (p & 1)));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(img + off_tr<F>(r0 + 4 + q, 2 * cb + (p >> 1)) + 8 * (p & 1)));
-    return s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
-
-// eight fp32 values -> their bf16 heads and the bf16 of what the heads leave
-__device__ __forceinline__ void split8(const f32x4 a, const f32x4 b, u32x4& hi, u32x4& lo) {
-    const float x[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    uint32_t h[8], l[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        h[i] = f32_to_bf16(x[i]);
-        l[i] = f32_to_bf16(x[i] - __uint_as_float(h[i] << 16));
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        hi[i] = h[2 * i] | (h[2 * i + 1] << 16);
-        lo[i] = l[2 * i] | (l[2 * i + 1] << 16);
-    }
-}
-
-// ... and into three pieces by TRUNCATION: a bf16 is the top 16 bits of the fp32 pattern, so each piece takes the next eight
-// significant bits of what is left (x - hi and r - mid are exact) and three pieces hold all 24.  Per pair of elements: two masks
-// and one packed subtraction per level, one v_perm_b32 per piece to pack the two top halves - 4.5 VALU instructions per element.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pack_top(float x1, float x0) {              // (x1 & 0xffff0000) | (x0 >> 16)
-    return __builtin_amdgcn_perm(__float_as_uint(x1), __float_as_uint(x0), 0x07060302u);
-}
-__device__ __forceinline__ f32x2 top16(f32x2 v) {
-    return f32x2{__uint_as_float(__float_as_uint(v[0]) & 0xffff0000u), __uint_as_float(__float_as_uint(v[1]) & 0xffff0000u)};
-}
-__device__ __forceinline__ void split8x3(const f32x4 a, const f32x4 b, u32x4& hi, u32x4& mid, u32x4& lo) {
-    const f32x2 x[4] = {{a[0], a[1]}, {a[2], a[3]}, {b[0], b[1]}, {b[2], b[3]}};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const f32x2 r1 = x[i] - top16(x[i]);
-        const f32x2 r2 = r1 - top16(r1);
-        hi[i] = pack_top(x[i][1], x[i][0]);
-        mid[i] = pack_top(r1[1], r1[0]);
-        lo[i] = pack_top(r2[1], r2[0]);
-    }
-}
-
-// The same split with SCALAR-lane subtractions (11 instructions per pair instead of 9), for loops that multiply on the bf16 matrix pipe
-// while they split: a packed fp32 instruction between two MFMAs costs 7 - 17 cycles of matrix-pipe time, the first two plain vector
-// instructions behind a bf16 MFMA cost nothing and further ones 4 cycles each (tools/ubench/interleave.hip).  Inline asm: left as C,
-// hipcc's SLP vectoriser re-packs the subtractions.
-__device__ __forceinline__ float sub_np(float a, float b) {
-    float r;
-    asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ float mul_np(float a, float b) {
-    float r;
-    asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ void split8x3_np(const f32x4 a, const f32x4 b, u32x4& hi, u32x4& mid, u32x4& lo) {
-    const float x[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float x0 = x[2 * i], x1 = x[2 * i + 1];
-        const float r0 = sub_np(x0, __uint_as_float(__float_as_uint(x0) & 0xffff0000u)), r1 = sub_np(x1, __uint_as_float(__float_as_uint(x1) & 0xffff0000u));
-        const float q0 = sub_np(r0, __uint_as_float(__float_as_uint(r0) & 0xffff0000u)), q1 = sub_np(r1, __uint_as_float(__float_as_uint(r1) & 0xffff0000u));
-        hi[i] = pack_top(x1, x0);
-        mid[i] = pack_top(r1, r0);
-        lo[i] = pack_top(q1, q0);
-    }
-}
 
 // C[M,NF] = A[M,KC] . op(B) (+ bias).  BTR = false: B is [NF][KC] (forward); true: B is [KC][NF] (backward-data).
 template <int WM, int WN, bool BTR, bool SIX>
@@ -180,24 +94,24 @@ __global__ __launch_bounds__(256, 2) void gemm_split_kernel(const float* __restr
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
             const int e = t + 256 * i;
-            u32x4 hi, mid, lo;
-            if (SIX) split8x3(ra[i][0], ra[i][1], hi, mid, lo);
-            else split8(ra[i][0], ra[i][1], hi, lo);
+            dhz_u32x4 hi, mid, lo;
+            if (SIX) dhz_split8x3_pk(ra[i][0], ra[i][1], hi, mid, lo);
+            else dhz_split8(ra[i][0], ra[i][1], hi, lo);
             const int o = off_row(e >> 3, e & 7);
-            *reinterpret_cast<u32x4*>(Ah + o) = hi;
-            if (SIX) *reinterpret_cast<u32x4*>(Am + o) = mid;
-            *reinterpret_cast<u32x4*>(Al + o) = lo;
+            *reinterpret_cast<dhz_u32x4*>(Ah + o) = hi;
+            if (SIX) *reinterpret_cast<dhz_u32x4*>(Am + o) = mid;
+            *reinterpret_cast<dhz_u32x4*>(Al + o) = lo;
         }
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
             const int e = t + 256 * i;
-            u32x4 hi, mid, lo;
-            if (SIX) split8x3(rb[i][0], rb[i][1], hi, mid, lo);
-            else split8(rb[i][0], rb[i][1], hi, lo);
-            const int o = BTR ? off_tr<BN>(e / (BN / 8), e % (BN / 8)) : off_row(e >> 3, e & 7);
-            *reinterpret_cast<u32x4*>(Bh + o) = hi;
-            if (SIX) *reinterpret_cast<u32x4*>(Bm + o) = mid;
-            *reinterpret_cast<u32x4*>(Bl + o) = lo;
+            dhz_u32x4 hi, mid, lo;
+            if (SIX) dhz_split8x3_pk(rb[i][0], rb[i][1], hi, mid, lo);
+            else dhz_split8(rb[i][0], rb[i][1], hi, lo);
+            const int o = BTR ? dhz_off_tr<BN>(e / (BN / 8), e % (BN / 8)) : off_row(e >> 3, e & 7);
+            *reinterpret_cast<dhz_u32x4*>(Bh + o) = hi;
+            if (SIX) *reinterpret_cast<dhz_u32x4*>(Bm + o) = mid;
+            *reinterpret_cast<dhz_u32x4*>(Bl + o) = lo;
         }
     };
 
@@ -218,39 +132,39 @@ __global__ __launch_bounds__(256, 2) void gemm_split_kernel(const float* __restr
             else if (ntile >= 0) { set_tile(ntile); gload(0); }
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
-                s16x8 ah[WM], am[SIX ? WM : 1], al[WM], bh[WN], bm[SIX ? WN : 1], bl[WN];
+                dhz_s16x8 ah[WM], am[SIX ? WM : 1], al[WM], bh[WN], bm[SIX ? WN : 1], bl[WN];
 #pragma unroll
                 for (int a = 0; a < WM; ++a) {
                     const int o = (wm * WM * 16 + a * 16 + i16) * 128 + 16 * ((4 * s + g) ^ sw);
-                    ah[a] = *reinterpret_cast<const s16x8*>(Ah + o);
-                    if (SIX) am[a] = *reinterpret_cast<const s16x8*>(Am + o);
-                    al[a] = *reinterpret_cast<const s16x8*>(Al + o);
+                    ah[a] = *reinterpret_cast<const dhz_s16x8*>(Ah + o);
+                    if (SIX) am[a] = *reinterpret_cast<const dhz_s16x8*>(Am + o);
+                    al[a] = *reinterpret_cast<const dhz_s16x8*>(Al + o);
                 }
 #pragma unroll
                 for (int b = 0; b < WN; ++b) {
                     if (BTR) {
-                        bh[b] = tr_frag<BN>(Bh, 32 * s + 8 * g, wn * WN + b, lane);
-                        if (SIX) bm[b] = tr_frag<BN>(Bm, 32 * s + 8 * g, wn * WN + b, lane);
-                        bl[b] = tr_frag<BN>(Bl, 32 * s + 8 * g, wn * WN + b, lane);
+                        bh[b] = dhz_tr_frag<BN>(Bh, 32 * s + 8 * g, wn * WN + b, lane);
+                        if (SIX) bm[b] = dhz_tr_frag<BN>(Bm, 32 * s + 8 * g, wn * WN + b, lane);
+                        bl[b] = dhz_tr_frag<BN>(Bl, 32 * s + 8 * g, wn * WN + b, lane);
                     } else {
                         const int o = ((wn * WN + b) * 16 + i16) * 128 + 16 * ((4 * s + g) ^ sw);
-                        bh[b] = *reinterpret_cast<const s16x8*>(Bh + o);
-                        if (SIX) bm[b] = *reinterpret_cast<const s16x8*>(Bm + o);
-                        bl[b] = *reinterpret_cast<const s16x8*>(Bl + o);
+                        bh[b] = *reinterpret_cast<const dhz_s16x8*>(Bh + o);
+                        if (SIX) bm[b] = *reinterpret_cast<const dhz_s16x8*>(Bm + o);
+                        bl[b] = *reinterpret_cast<const dhz_s16x8*>(Bl + o);
                     }
                 }
 #pragma unroll
                 for (int a = 0; a < WM; ++a)
 #pragma unroll
                     for (int b = 0; b < WN; ++b) {                           // D = C^T block (epilogue); small terms first
-                        acc[a][b] = mfma_bf16(bl[b], ah[a], acc[a][b]);
-                        acc[a][b] = mfma_bf16(bh[b], al[a], acc[a][b]);
+                        acc[a][b] = dhz_mfma_bf16(bl[b], ah[a], acc[a][b]);
+                        acc[a][b] = dhz_mfma_bf16(bh[b], al[a], acc[a][b]);
                         if (SIX) {
-                            acc[a][b] = mfma_bf16(bm[b], am[a], acc[a][b]);
-                            acc[a][b] = mfma_bf16(bm[b], ah[a], acc[a][b]);
-                            acc[a][b] = mfma_bf16(bh[b], am[a], acc[a][b]);
+                            acc[a][b] = dhz_mfma_bf16(bm[b], am[a], acc[a][b]);
+                            acc[a][b] = dhz_mfma_bf16(bm[b], ah[a], acc[a][b]);
+                            acc[a][b] = dhz_mfma_bf16(bh[b], am[a], acc[a][b]);
                         }
-                        acc[a][b] = mfma_bf16(bh[b], ah[a], acc[a][b]);
+                        acc[a][b] = dhz_mfma_bf16(bh[b], ah[a], acc[a][b]);
                     }
             }
             if (more) {
@@ -424,13 +338,13 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(const float* __rest
         for (int i = 0; i < NA; ++i) {
             const int e = t + 256 * i;
             const f32x4 v0 = ra[i][0] * rs[i], v1 = ra[i][1] * rs[i];
-            u32x4 hi, mid, lo;
-            if (SIX) split8x3(v0, v1, hi, mid, lo);
-            else split8(v0, v1, hi, lo);
-            const int o = off_tr<FM>(e / (FM / 8), e % (FM / 8));
-            *reinterpret_cast<u32x4*>(Ah + o) = hi;
-            if (SIX) *reinterpret_cast<u32x4*>(Am + o) = mid;
-            *reinterpret_cast<u32x4*>(Al + o) = lo;
+            dhz_u32x4 hi, mid, lo;
+            if (SIX) dhz_split8x3_pk(v0, v1, hi, mid, lo);
+            else dhz_split8(v0, v1, hi, lo);
+            const int o = dhz_off_tr<FM>(e / (FM / 8), e % (FM / 8));
+            *reinterpret_cast<dhz_u32x4*>(Ah + o) = hi;
+            if (SIX) *reinterpret_cast<dhz_u32x4*>(Am + o) = mid;
+            *reinterpret_cast<dhz_u32x4*>(Al + o) = lo;
             if (do_db) {
 #pragma unroll
                 for (int c = 0; c < 4; ++c) { dbacc[c] += v0[c]; dbacc[4 + c] += v1[c]; }
@@ -439,13 +353,13 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(const float* __rest
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
             const int e = t + 256 * i;
-            u32x4 hi, mid, lo;
-            if (SIX) split8x3(rb[i][0], rb[i][1], hi, mid, lo);
-            else split8(rb[i][0], rb[i][1], hi, lo);
-            const int o = off_tr<FN>(e / (FN / 8), e % (FN / 8));
-            *reinterpret_cast<u32x4*>(Bh + o) = hi;
-            if (SIX) *reinterpret_cast<u32x4*>(Bm + o) = mid;
-            *reinterpret_cast<u32x4*>(Bl + o) = lo;
+            dhz_u32x4 hi, mid, lo;
+            if (SIX) dhz_split8x3_pk(rb[i][0], rb[i][1], hi, mid, lo);
+            else dhz_split8(rb[i][0], rb[i][1], hi, lo);
+            const int o = dhz_off_tr<FN>(e / (FN / 8), e % (FN / 8));
+            *reinterpret_cast<dhz_u32x4*>(Bh + o) = hi;
+            if (SIX) *reinterpret_cast<dhz_u32x4*>(Bm + o) = mid;
+            *reinterpret_cast<dhz_u32x4*>(Bl + o) = lo;
         }
     };
 
@@ -459,31 +373,31 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(const float* __rest
         if (more) gload(st + 1);
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            s16x8 ah[WM], am[SIX ? WM : 1], al[WM], bh[WN], bm[SIX ? WN : 1], bl[WN];
+            dhz_s16x8 ah[WM], am[SIX ? WM : 1], al[WM], bh[WN], bm[SIX ? WN : 1], bl[WN];
 #pragma unroll
             for (int a = 0; a < WM; ++a) {
-                ah[a] = tr_frag<FM>(Ah, 32 * s + 8 * g, wm * WM + a, lane);
-                if (SIX) am[a] = tr_frag<FM>(Am, 32 * s + 8 * g, wm * WM + a, lane);
-                al[a] = tr_frag<FM>(Al, 32 * s + 8 * g, wm * WM + a, lane);
+                ah[a] = dhz_tr_frag<FM>(Ah, 32 * s + 8 * g, wm * WM + a, lane);
+                if (SIX) am[a] = dhz_tr_frag<FM>(Am, 32 * s + 8 * g, wm * WM + a, lane);
+                al[a] = dhz_tr_frag<FM>(Al, 32 * s + 8 * g, wm * WM + a, lane);
             }
 #pragma unroll
             for (int b = 0; b < WN; ++b) {
-                bh[b] = tr_frag<FN>(Bh, 32 * s + 8 * g, wn * WN + b, lane);
-                if (SIX) bm[b] = tr_frag<FN>(Bm, 32 * s + 8 * g, wn * WN + b, lane);
-                bl[b] = tr_frag<FN>(Bl, 32 * s + 8 * g, wn * WN + b, lane);
+                bh[b] = dhz_tr_frag<FN>(Bh, 32 * s + 8 * g, wn * WN + b, lane);
+                if (SIX) bm[b] = dhz_tr_frag<FN>(Bm, 32 * s + 8 * g, wn * WN + b, lane);
+                bl[b] = dhz_tr_frag<FN>(Bl, 32 * s + 8 * g, wn * WN + b, lane);
             }
 #pragma unroll
             for (int a = 0; a < WM; ++a)
 #pragma unroll
                 for (int b = 0; b < WN; ++b) {
-                    acc[a][b] = mfma_bf16(al[a], bh[b], acc[a][b]);
-                    acc[a][b] = mfma_bf16(ah[a], bl[b], acc[a][b]);
+                    acc[a][b] = dhz_mfma_bf16(al[a], bh[b], acc[a][b]);
+                    acc[a][b] = dhz_mfma_bf16(ah[a], bl[b], acc[a][b]);
                     if (SIX) {
-                        acc[a][b] = mfma_bf16(am[a], bm[b], acc[a][b]);
-                        acc[a][b] = mfma_bf16(am[a], bh[b], acc[a][b]);
-                        acc[a][b] = mfma_bf16(ah[a], bm[b], acc[a][b]);
+                        acc[a][b] = dhz_mfma_bf16(am[a], bm[b], acc[a][b]);
+                        acc[a][b] = dhz_mfma_bf16(am[a], bh[b], acc[a][b]);
+                        acc[a][b] = dhz_mfma_bf16(ah[a], bm[b], acc[a][b]);
                     }
-                    acc[a][b] = mfma_bf16(ah[a], bh[b], acc[a][b]);
+                    acc[a][b] = dhz_mfma_bf16(ah[a], bh[b], acc[a][b]);
                 }
         }
         __syncthreads();
@@ -598,13 +512,13 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * G, WAVES_M * WAVES_N == 4 
 #pragma unroll
     for (int i = 0; i < NA; ++i) {
         const int e = t + NT * i;
-        a_off[i] = off_tr<FM>(e / (FM / 8), e % (FM / 8));
+        a_off[i] = dhz_off_tr<FM>(e / (FM / 8), e % (FM / 8));
         pa[i] = (unsigned)(((e / (FM / 8)) * ldy + 8 * (e % (FM / 8))) * 4);
     }
 #pragma unroll
     for (int i = 0; i < NB; ++i) {
         const int e = t + NT * i;
-        b_off[i] = off_tr<FN>(e / (FN / 8), e % (FN / 8));
+        b_off[i] = dhz_off_tr<FN>(e / (FN / 8), e % (FN / 8));
         pb[i] = (unsigned)(((e / (FN / 8)) * ldx + 8 * (e % (FN / 8))) * 4);
     }
     const char* const dyb = reinterpret_cast<const char*>(dy + n0);
@@ -638,16 +552,16 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * G, WAVES_M * WAVES_N == 4 
             f32x4 v0 = ra[i][0], v1 = ra[i][1];
             if (row_scale) {
 #pragma unroll
-                for (int c = 0; c < 4; ++c) { v0[c] = mul_np(v0[c], rs); v1[c] = mul_np(v1[c], rs); }
+                for (int c = 0; c < 4; ++c) { v0[c] = dhz_mul_np(v0[c], rs); v1[c] = dhz_mul_np(v1[c], rs); }
             }
-            u32x4 hi, mid, lo;
-            if constexpr (DHZ_W6_ABL & 2) { hi = __builtin_bit_cast(u32x4, v0); mid = __builtin_bit_cast(u32x4, v1); lo = hi ^ mid; }
-            else split8x3_np(v0, v1, hi, mid, lo);
+            dhz_u32x4 hi, mid, lo;
+            if constexpr (DHZ_W6_ABL & 2) { hi = __builtin_bit_cast(dhz_u32x4, v0); mid = __builtin_bit_cast(dhz_u32x4, v1); lo = hi ^ mid; }
+            else dhz_split8x3_np(v0, v1, hi, mid, lo);
             if constexpr (DHZ_W6_ABL & 4) { asm volatile("" :: "v"(hi), "v"(mid), "v"(lo)); }
             else {
-            *reinterpret_cast<u32x4*>(As + a_off[i]) = hi;
-            *reinterpret_cast<u32x4*>(As + A_BYTES + a_off[i]) = mid;
-            *reinterpret_cast<u32x4*>(As + 2 * A_BYTES + a_off[i]) = lo;
+            *reinterpret_cast<dhz_u32x4*>(As + a_off[i]) = hi;
+            *reinterpret_cast<dhz_u32x4*>(As + A_BYTES + a_off[i]) = mid;
+            *reinterpret_cast<dhz_u32x4*>(As + 2 * A_BYTES + a_off[i]) = lo;
             }
             if (do_db) {
 #pragma unroll
@@ -656,14 +570,14 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * G, WAVES_M * WAVES_N == 4 
         }
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
-            u32x4 hi, mid, lo;
-            if constexpr (DHZ_W6_ABL & 2) { hi = __builtin_bit_cast(u32x4, rb[i][0]); mid = __builtin_bit_cast(u32x4, rb[i][1]); lo = hi ^ mid; }
-            else split8x3_np(rb[i][0], rb[i][1], hi, mid, lo);
+            dhz_u32x4 hi, mid, lo;
+            if constexpr (DHZ_W6_ABL & 2) { hi = __builtin_bit_cast(dhz_u32x4, rb[i][0]); mid = __builtin_bit_cast(dhz_u32x4, rb[i][1]); lo = hi ^ mid; }
+            else dhz_split8x3_np(rb[i][0], rb[i][1], hi, mid, lo);
             if constexpr (DHZ_W6_ABL & 4) { asm volatile("" :: "v"(hi), "v"(mid), "v"(lo)); }
             else {
-            *reinterpret_cast<u32x4*>(Bs + b_off[i]) = hi;
-            *reinterpret_cast<u32x4*>(Bs + B_BYTES + b_off[i]) = mid;
-            *reinterpret_cast<u32x4*>(Bs + 2 * B_BYTES + b_off[i]) = lo;
+            *reinterpret_cast<dhz_u32x4*>(Bs + b_off[i]) = hi;
+            *reinterpret_cast<dhz_u32x4*>(Bs + B_BYTES + b_off[i]) = mid;
+            *reinterpret_cast<dhz_u32x4*>(Bs + 2 * B_BYTES + b_off[i]) = lo;
             }
         }
     };
@@ -677,18 +591,18 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * G, WAVES_M * WAVES_N == 4 
         const int buf = st & 1;
         const unsigned char* As = smem + buf * STAGE;
         const unsigned char* Bs = As + 3 * A_BYTES;
-        s16x8 af[3][WM], bf[3][WN];
+        dhz_s16x8 af[3][WM], bf[3][WN];
 #pragma unroll
         for (int pc = 0; pc < 3; ++pc) {
 #pragma unroll
             for (int a = 0; a < WM; ++a) {
-                if constexpr (DHZ_W6_ABL & 8) { af[pc][a] = s16x8{(short)lane, 1, 2, 3, 4, 5, 6, (short)st}; asm volatile("" : "+v"(af[pc][a])); }
-                else af[pc][a] = tr_frag<FM>(As + pc * A_BYTES, 8 * g, wm * WM + a, lane);
+                if constexpr (DHZ_W6_ABL & 8) { af[pc][a] = dhz_s16x8{(short)lane, 1, 2, 3, 4, 5, 6, (short)st}; asm volatile("" : "+v"(af[pc][a])); }
+                else af[pc][a] = dhz_tr_frag<FM>(As + pc * A_BYTES, 8 * g, wm * WM + a, lane);
             }
 #pragma unroll
             for (int b = 0; b < WN; ++b) {
-                if constexpr (DHZ_W6_ABL & 8) { bf[pc][b] = s16x8{(short)lane, 1, 2, 3, 4, 5, 6, (short)st}; asm volatile("" : "+v"(bf[pc][b])); }
-                else bf[pc][b] = tr_frag<FN>(Bs + pc * B_BYTES, 8 * g, wn * WN + b, lane);
+                if constexpr (DHZ_W6_ABL & 8) { bf[pc][b] = dhz_s16x8{(short)lane, 1, 2, 3, 4, 5, 6, (short)st}; asm volatile("" : "+v"(bf[pc][b])); }
+                else bf[pc][b] = dhz_tr_frag<FN>(Bs + pc * B_BYTES, 8 * g, wn * WN + b, lane);
             }
         }
         // ---- one stream: the stage's MFMAs (term-major: consecutive ones never share an accumulator), between them the split and
@@ -701,7 +615,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * G, WAVES_M * WAVES_N == 4 
 #pragma unroll
                 for (int b = 0; b < WN; ++b) {
                     if constexpr (DHZ_W6_ABL & 16) { if (term == 0) asm volatile("" : "+v"(acc[a][b]) : "v"(af[0][a]), "v"(af[1][a]), "v"(af[2][a]), "v"(bf[0][b]), "v"(bf[1][b]), "v"(bf[2][b])); }
-                    else acc[a][b] = mfma_bf16(af[TA[term]][a], bf[TB[term]][b], acc[a][b]);
+                    else acc[a][b] = dhz_mfma_bf16(af[TA[term]][a], bf[TB[term]][b], acc[a][b]);
                 }
         if (st + 1 < st1) swrite(buf ^ 1);
 #pragma unroll

@@ -12,7 +12,7 @@
 //                             reference's two score products collapse into one MFMA product.
 //   O  = P V     (32x64xd)  - 25 selected rows padded to 32; row 25 of P is the constant 1/64 so that
 //                             row 25 of O is mean(V) (ATT:168-172) for free.
-#include "common.h"
+#include "bf16_pipe.h"
 
 namespace {
 
@@ -27,21 +27,16 @@ constexpr int SS = 68;     // row stride of the 64-wide score tiles
 #define PSF_WG64 3        // config 4: 44.19 ms per step against 44.52 with two
 #endif
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint32_t pack_top16(float x1, float x0) {           // bf16(x1) : bf16(x0) of bf16-representable values
-    return __builtin_amdgcn_perm(__float_as_uint(x1), __float_as_uint(x0), 0x07060302u);
-}
 // 16 x 16 tile of A . B^T over a contraction of 64 for two row-major fp32 LDS tiles that hold bf16-representable values (bf16
 // storage: Q, K, V, dO rows): the products on v_mfma_f32_16x16x32_bf16, exact, fp32 accumulation.  Rows that hold other fp32
 // values (the summed dO row of the mean(V) path) are TRUNCATED to bf16 - only where the result is not used.
-__device__ __forceinline__ bf16x8_t frag_bf16(const float* row, int half, int g) {
+__device__ __forceinline__ dhz_bf16x8 frag_bf16(const float* row, int half, int g) {
     const f32x4 lo = *reinterpret_cast<const f32x4*>(row + 32 * half + 8 * g);
     const f32x4 hi = *reinterpret_cast<const f32x4*>(row + 32 * half + 8 * g + 4);
-    u32x4_t r;
-    r[0] = pack_top16(lo[1], lo[0]); r[1] = pack_top16(lo[3], lo[2]);
-    r[2] = pack_top16(hi[1], hi[0]); r[3] = pack_top16(hi[3], hi[2]);
-    return __builtin_bit_cast(bf16x8_t, r);
+    dhz_u32x4 r;
+    r[0] = dhz_pack_top(lo[1], lo[0]); r[1] = dhz_pack_top(lo[3], lo[2]);
+    r[2] = dhz_pack_top(hi[1], hi[0]); r[3] = dhz_pack_top(hi[3], hi[2]);
+    return __builtin_bit_cast(dhz_bf16x8, r);
 }
 __device__ __forceinline__ f32x4 tile_mma_bf16_k64(const float* A, int lda, const float* B, int ldb, int i16, int g, f32x4 acc) {
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_bf16(A + i16 * lda, 0, g), frag_bf16(B + i16 * ldb, 0, g), acc, 0, 0, 0);
@@ -62,19 +57,6 @@ struct FwdSmem {
     uint8_t rank[NT];
 };                         // 45.5 KB at d = 32, 52.7 KB at d = 64 (66.6 before Q / P shared tiles): three workgroups per CU
 
-__device__ __forceinline__ float row8_max(float v) {
-    v = fmaxf(v, __shfl_xor(v, 1));
-    v = fmaxf(v, __shfl_xor(v, 2));
-    v = fmaxf(v, __shfl_xor(v, 4));
-    return v;
-}
-__device__ __forceinline__ float row8_sum(float v) {
-    v += __shfl_xor(v, 1);
-    v += __shfl_xor(v, 2);
-    v += __shfl_xor(v, 4);
-    return v;
-}
-
 // Double softmax of one selected row, 8 columns per thread (8 threads per row):
 //   p1 = softmax(x);  a = p1 + bias + mask;  p2 = softmax(a)          (ATT:195, 229, 251-258, 262)
 // PAD: the padding word pw of the window (bit j: token j is padding) adds -100 where query qrow AND key c0 + i are padding.  The term is
@@ -86,11 +68,11 @@ __device__ __forceinline__ void double_softmax8(const float* x, const float* bro
     float mx = x[0];
 #pragma unroll
     for (int i = 1; i < 8; ++i) mx = fmaxf(mx, x[i]);
-    mx = row8_max(mx);
+    mx = dhz_row8_max(mx);
     float e[8], sum = 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) { e[i] = __expf(x[i] - mx); sum += e[i]; }
-    sum = __builtin_amdgcn_rcpf(row8_sum(sum));          // v_exp_f32 / v_rcp_f32: ~1 ulp each, 10x fewer instructions
+    sum = __builtin_amdgcn_rcpf(dhz_row8_sum(sum));          // v_exp_f32 / v_rcp_f32: ~1 ulp each, 10x fewer instructions
     float a[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) { p1[i] = e[i] * sum; a[i] = p1[i]; }
@@ -115,11 +97,11 @@ __device__ __forceinline__ void double_softmax8(const float* x, const float* bro
     float mx2 = a[0];
 #pragma unroll
     for (int i = 1; i < 8; ++i) mx2 = fmaxf(mx2, a[i]);
-    mx2 = row8_max(mx2);
+    mx2 = dhz_row8_max(mx2);
     float sum2 = 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) { e[i] = __expf(a[i] - mx2); sum2 += e[i]; }
-    sum2 = __builtin_amdgcn_rcpf(row8_sum(sum2));
+    sum2 = __builtin_amdgcn_rcpf(dhz_row8_sum(sum2));
 #pragma unroll
     for (int i = 0; i < 8; ++i) p2[i] = e[i] * sum2;
 }
@@ -185,7 +167,7 @@ __global__ __launch_bounds__(256) void ps_attn_fwd_kernel(const T* __restrict__ 
         // lane is 8 consecutive channels of its row, packed from the top halves of the fp32 words
         const int i = lane & 15, g = lane >> 4;
         auto frag = [&](const float* row, int half) { return frag_bf16(row, half, g); };
-        const bf16x8_t qa0 = frag(&sm.s[(16 * w + i) * DS], 0), qa1 = frag(&sm.s[(16 * w + i) * DS], 1);
+        const dhz_bf16x8 qa0 = frag(&sm.s[(16 * w + i) * DS], 0), qa1 = frag(&sm.s[(16 * w + i) * DS], 1);
         __syncthreads();                               // every wave holds its Q fragments: the tile is free for S
 #pragma unroll
         for (int tc = 0; tc < 4; ++tc) {
@@ -510,11 +492,11 @@ __global__ __launch_bounds__(256) void ps_attn_bwd_kernel(
                 dp[i] = sm.ds[r * SS + c0 + i]; p1[i] = sm.p1[r * SS + c0 + i]; p2[i] = sm.p2[r * SS + c0 + i];
                 dot2 += dp[i] * p2[i];
             }
-            dot2 = row8_sum(dot2);
+            dot2 = dhz_row8_sum(dot2);
             float da[8], dot1 = 0.f;
 #pragma unroll
             for (int i = 0; i < 8; ++i) { da[i] = p2[i] * (dp[i] - dot2); dot1 += da[i] * p1[i]; }
-            dot1 = row8_sum(dot1);
+            dot1 = dhz_row8_sum(dot1);
             if (HAS_BIAS && REG_ACC) {                    // dA over the P2 values this thread has just read: picked up by the owners below
 #pragma unroll
                 for (int i = 0; i < 8; ++i) sm.p2[r * SS + c0 + i] = da[i];
@@ -737,20 +719,15 @@ __global__ void shift_mask_kernel(float* __restrict__ mask, int Hres, int Wres, 
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ C ABI
-// LDS above 64 KiB per workgroup needs an explicit opt-in; idempotent and cheap, so done per launch.
-static void allow_smem(const void* fn, size_t bytes) {
-    if (bytes > 48 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
 template <int D, typename T>
 static void launch_fwd(int grid, hipStream_t s, const T* q, const T* k, const T* v, int ld, const uint8_t* idx, const float* bias,
                        const float* mask, const uint64_t* pad, T* out, int ldo, uint8_t* rank, int H, int nW, int nwh) {
     if (pad) {
-        allow_smem(reinterpret_cast<const void*>(&ps_attn_fwd_kernel<D, T, true>), sizeof(FwdSmem<D>));
+        dhz_allow_smem(&ps_attn_fwd_kernel<D, T, true>, sizeof(FwdSmem<D>));
         hipLaunchKernelGGL((ps_attn_fwd_kernel<D, T, true>), dim3(grid), dim3(256), sizeof(FwdSmem<D>), s, q, k, v, ld, idx,
                            bias, mask, out, ldo, rank, H, nW, nwh, PadArg<true>{pad});
     } else {
-        allow_smem(reinterpret_cast<const void*>(&ps_attn_fwd_kernel<D, T>), sizeof(FwdSmem<D>));
+        dhz_allow_smem(&ps_attn_fwd_kernel<D, T>, sizeof(FwdSmem<D>));
         hipLaunchKernelGGL((ps_attn_fwd_kernel<D, T>), dim3(grid), dim3(256), sizeof(FwdSmem<D>), s, q, k, v, ld, idx,
                            bias, mask, out, ldo, rank, H, nW, nwh, PadArg<false>{});
     }
@@ -826,12 +803,12 @@ static void launch_bwd(int parts, hipStream_t s, const T* q, const T* k, const T
                        T* dq, T* dk, T* dv, int ldg, float* dbias_part, int B_, int H, int nW, const uint64_t* pad) {
     const size_t smem = sizeof(BwdSmem<D>);
     if (pad) {
-        allow_smem(reinterpret_cast<const void*>(&ps_attn_bwd_kernel<D, HB, T, true>), smem);
+        dhz_allow_smem(&ps_attn_bwd_kernel<D, HB, T, true>, smem);
         hipLaunchKernelGGL((ps_attn_bwd_kernel<D, HB, T, true>), dim3(parts), dim3(256), smem, s, q, k, v, ld, bias, mask, rank,
                            dout, ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW, PadArg<true>{pad});
         return;
     }
-    allow_smem(reinterpret_cast<const void*>(&ps_attn_bwd_kernel<D, HB, T>), smem);
+    dhz_allow_smem(&ps_attn_bwd_kernel<D, HB, T>, smem);
     hipLaunchKernelGGL((ps_attn_bwd_kernel<D, HB, T>), dim3(parts), dim3(256), smem, s, q, k, v, ld, bias, mask, rank,
                        dout, ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW, PadArg<false>{});
 }

@@ -3,7 +3,7 @@
 //
 // A 16-token window-head is ONE 16 x 16 score tile, so one wave64 owns a window-head from its loads to its stores and a 256-thread
 // workgroup runs four independent window-heads.  The waves of a workgroup share no data: every phase boundary is a wave-level
-// ordering point (wave_sync), there is no workgroup barrier in this file, and waves without work simply leave.
+// ordering point (dhz_wave_sync), there is no workgroup barrier in this file, and waves without work simply leave.
 // Persistent grid: wave gw = 4 blockIdx.x + w walks window-heads gw, gw + 4 gridDim.x, ...; the Q, K, V (and dO) rows of the next
 // window-head are fetched into registers while the current one computes, as in ps_attn.hip.
 //
@@ -14,7 +14,7 @@
 // u = n_top(16) = 15 of 16 queries are selected.  bf16 storage: the staged fp32 values are the bf16 values; same fp32 products.
 // No float atomic anywhere: a wave keeps the 16 x 16 bias-gradient sum of its window-heads in 4 registers per lane and stores it
 // as its own partial; the table gradient is a fixed-order sum.  Deterministic mode needs no separate path.
-#include "common.h"
+#include "bf16_pipe.h"
 
 namespace {
 
@@ -28,13 +28,6 @@ constexpr int SS = 20;     // row stride of the 16-wide score tiles (float4-alig
 #ifndef PS16_BWD_WG
 #define PS16_BWD_WG(d) ((d) == 64 ? 1 : 2)      // backward (79.9 KB at d = 64, 47.1 KB at d = 32)
 #endif
-
-__device__ __forceinline__ void wave_sync() {
-    // LDS operations of one wave execute in order; only the compiler must not move accesses across phase boundaries
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 __device__ __forceinline__ float q4_max(float v) {
     v = fmaxf(v, __shfl_xor(v, 1));
@@ -144,7 +137,7 @@ __global__ __launch_bounds__(256) void attn16_fwd_kernel(const T* __restrict__ q
         const size_t tok0 = (size_t)b * NT;
         uint64_t pw = 0;
         if constexpr (PAD) pw = pad.words[b] & 0xffffull;
-        wave_sync();                                       // the previous window-head's stores have read O / rank
+        dhz_wave_sync();                                       // the previous window-head's stores have read O / rank
 #pragma unroll
         for (int p = 0; p < NR; ++p) {
             const int e = p * 64 + lane, o = (e / F) * DS + (e % F) * 4;
@@ -153,7 +146,7 @@ __global__ __launch_bounds__(256) void attn16_fwd_kernel(const T* __restrict__ q
             *reinterpret_cast<f32x4*>(&sm.v[o]) = pv[p];
         }
         if (wh + stride < nwh) prefetch(wh + stride);      // in flight during the rest of this window-head
-        wave_sync();
+        dhz_wave_sync();
 
         // ---- S = Q K^T
         {
@@ -163,7 +156,7 @@ __global__ __launch_bounds__(256) void attn16_fwd_kernel(const T* __restrict__ q
 #pragma unroll
             for (int j = 0; j < 4; ++j) sm.s[(4 * g + j) * SS + i] = acc[j];
         }
-        wave_sync();
+        dhz_wave_sync();
 
         if (!DENSE) {
             // ---- sparsity measure M[q] = max_s S[q, idx[q, s]] - sum_s S[q, idx[q, s]] / 16      (ATT:117), 4 lanes per query
@@ -182,7 +175,7 @@ __global__ __launch_bounds__(256) void attn16_fwd_kernel(const T* __restrict__ q
                 su = q4_sum(su);
                 if ((lane & 3) == 0) sm.m[qi] = mx - su * (1.0f / NT);
             }
-            wave_sync();
+            dhz_wave_sync();
             // ---- rank[q] = #{j : M[j] > M[q] or (M[j] == M[q] and j < q)}; the 15 lowest ranks are selected      (ATT:122)
             {
                 const float m = sm.m[i];
@@ -194,7 +187,7 @@ __global__ __launch_bounds__(256) void attn16_fwd_kernel(const T* __restrict__ q
                 }
                 if (lane < NT) sm.rank[lane] = cnt < NU ? (uint8_t)cnt : (uint8_t)255;
             }
-            wave_sync();
+            dhz_wave_sync();
         }
 
         // ---- P in place over S: lane = (row r, columns c0 .. c0 + 3)
@@ -208,7 +201,7 @@ __global__ __launch_bounds__(256) void attn16_fwd_kernel(const T* __restrict__ q
             probs16<DENSE, PAD>(x, brow, mrow, DENSE || sm.rank[r] != 255, p1, p2, pw, r, c0);
             *reinterpret_cast<float4*>(&sm.s[r * SS + c0]) = make_float4(p2[0], p2[1], p2[2], p2[3]);
         }
-        wave_sync();
+        dhz_wave_sync();
 
         // ---- O = P V over the dead Q tile
 #pragma unroll
@@ -219,7 +212,7 @@ __global__ __launch_bounds__(256) void attn16_fwd_kernel(const T* __restrict__ q
 #pragma unroll
             for (int j = 0; j < 4; ++j) sm.q[(4 * g + j) * DS + 16 * tc + i] = acc[j];
         }
-        wave_sync();
+        dhz_wave_sync();
 #pragma unroll
         for (int p = 0; p < NR; ++p) {
             const int e = p * 64 + lane, row = e / F, c4 = e % F;
@@ -285,7 +278,7 @@ __global__ __launch_bounds__(256) void attn16_bwd_kernel(const T* __restrict__ q
         const size_t tok0 = (size_t)b * NT;
         uint64_t pw = 0;
         if constexpr (PAD) pw = pad.words[b] & 0xffffull;
-        wave_sync();                                       // the previous window-head's stores have read the staging tiles
+        dhz_wave_sync();                                       // the previous window-head's stores have read the staging tiles
 #pragma unroll
         for (int p = 0; p < NR; ++p) {
             const int e = p * 64 + lane, o = (e / F) * DS + (e % F) * 4;
@@ -296,7 +289,7 @@ __global__ __launch_bounds__(256) void attn16_bwd_kernel(const T* __restrict__ q
         }
         if (!DENSE && lane < NT) sm.rank[lane] = prank;
         if (b + bstep < B_) prefetch(b + bstep);
-        wave_sync();
+        dhz_wave_sync();
 
         // ---- recompute S = Q K^T
         {
@@ -306,7 +299,7 @@ __global__ __launch_bounds__(256) void attn16_bwd_kernel(const T* __restrict__ q
 #pragma unroll
             for (int j = 0; j < 4; ++j) sm.s[(4 * g + j) * SS + i] = acc[j];
         }
-        wave_sync();
+        dhz_wave_sync();
 
         // ---- P1 (stays in registers: the same lane runs the softmax backward of these elements), P2 -> LDS
         const int r = lane >> 2, c0 = (lane & 3) * 4;
@@ -320,7 +313,7 @@ __global__ __launch_bounds__(256) void attn16_bwd_kernel(const T* __restrict__ q
             probs16<DENSE, PAD>(x, brow, mrow, sel, p1, p2, pw, r, c0);
             *reinterpret_cast<float4*>(&sm.p[r * SS + c0]) = make_float4(p2[0], p2[1], p2[2], p2[3]);
         }
-        wave_sync();
+        dhz_wave_sync();
 
         // ---- dP2 = dO V^T (over S);  dV = P2^T dO (the 1/16 row of P2 carries the mean(V) path)
         f32x4 accv[D / 16];
@@ -338,7 +331,7 @@ __global__ __launch_bounds__(256) void attn16_bwd_kernel(const T* __restrict__ q
                     accv[tc] = mfma16(sm.p[(4 * s + g) * SS + i], sm.g[(4 * s + g) * DS + 16 * tc + i], accv[tc]);
             }
         }
-        wave_sync();                                       // V is dead: its tile takes dV
+        dhz_wave_sync();                                       // V is dead: its tile takes dV
 
         // ---- both softmax backward steps; the bias gradient is dA
         {
@@ -363,7 +356,7 @@ __global__ __launch_bounds__(256) void attn16_bwd_kernel(const T* __restrict__ q
             }
             *reinterpret_cast<float4*>(&sm.s[r * SS + c0]) = make_float4(ds[0], ds[1], ds[2], ds[3]);
         }
-        wave_sync();
+        dhz_wave_sync();
 
         // ---- dQ = dS K ; dK = dS^T Q
         f32x4 accq[D / 16], acck[D / 16];
@@ -377,7 +370,7 @@ __global__ __launch_bounds__(256) void attn16_bwd_kernel(const T* __restrict__ q
                 acck[tc] = mfma16(sm.s[(4 * s + g) * SS + i], sm.q[(4 * s + g) * DS + 16 * tc + i], acck[tc]);
             }
         }
-        wave_sync();                                       // all reads of Q / K done
+        dhz_wave_sync();                                       // all reads of Q / K done
 #pragma unroll
         for (int tc = 0; tc < D / 16; ++tc)
 #pragma unroll
@@ -385,7 +378,7 @@ __global__ __launch_bounds__(256) void attn16_bwd_kernel(const T* __restrict__ q
                 sm.q[(4 * g + j) * DS + 16 * tc + i] = accq[tc][j];
                 sm.k[(4 * g + j) * DS + 16 * tc + i] = acck[tc][j];
             }
-        wave_sync();
+        dhz_wave_sync();
 #pragma unroll
         for (int p = 0; p < NR; ++p) {
             const int e = p * 64 + lane, row = e / F, c4 = e % F;
@@ -486,12 +479,6 @@ __global__ __launch_bounds__(1024) void bias_table_grad16_kernel(const float* __
     }
 }
 
-template <typename Kern>
-void allow_smem(Kern kern, size_t bytes) {
-    if (bytes > 48 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
 int win_log2(int win) { return win == 4 ? 2 : (win == 8 ? 3 : -1); }
 
 #define DHZ_REQUIRE_WIN(who, win) DHZ_REQUIRE(win_log2(win) > 0, "%s: window %d unsupported (4 or 8)", who, win)
@@ -504,13 +491,13 @@ void launch_fwd16(hipStream_t s, const T* q, const T* k, const T* v, int ld, con
     const size_t smem = 4 * sizeof(Fwd16<D>);
     if constexpr (!DENSE) {
         if (pad) {
-            allow_smem(&attn16_fwd_kernel<D, T, false, true>, smem);
+            dhz_allow_smem(&attn16_fwd_kernel<D, T, false, true>, smem);
             hipLaunchKernelGGL((attn16_fwd_kernel<D, T, false, true>), dim3(wgs < resident ? wgs : resident), dim3(256), smem, s, q, k, v, ld, idx,
                                bias, mask, out, ldo, rank, H, nW, nwh, scale, PadArg<true>{pad});
             return;
         }
     }
-    allow_smem(&attn16_fwd_kernel<D, T, DENSE>, smem);
+    dhz_allow_smem(&attn16_fwd_kernel<D, T, DENSE>, smem);
     hipLaunchKernelGGL((attn16_fwd_kernel<D, T, DENSE>), dim3(wgs < resident ? wgs : resident), dim3(256), smem, s, q, k, v, ld, idx, bias,
                        mask, out, ldo, rank, H, nW, nwh, scale, PadArg<false>{});
 }
@@ -550,24 +537,24 @@ void launch_bwd16(hipStream_t s, const T* q, const T* k, const T* v, int ld, con
     const size_t smem = 4 * sizeof(Bwd16<D>);
     if constexpr (!DENSE) {
         if (pad && bias) {
-            allow_smem(&attn16_bwd_kernel<D, T, false, true, true>, smem);
+            dhz_allow_smem(&attn16_bwd_kernel<D, T, false, true, true>, smem);
             hipLaunchKernelGGL((attn16_bwd_kernel<D, T, false, true, true>), dim3((parts + 3) / 4), dim3(256), smem, s, q, k, v, ld, bias, mask, rank,
                                dout, ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW, parts, scale, PadArg<true>{pad});
             return;
         }
         if (pad) {
-            allow_smem(&attn16_bwd_kernel<D, T, false, false, true>, smem);
+            dhz_allow_smem(&attn16_bwd_kernel<D, T, false, false, true>, smem);
             hipLaunchKernelGGL((attn16_bwd_kernel<D, T, false, false, true>), dim3((parts + 3) / 4), dim3(256), smem, s, q, k, v, ld, bias, mask, rank,
                                dout, ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW, parts, scale, PadArg<true>{pad});
             return;
         }
     }
     if (bias) {
-        allow_smem(&attn16_bwd_kernel<D, T, DENSE, true>, smem);
+        dhz_allow_smem(&attn16_bwd_kernel<D, T, DENSE, true>, smem);
         hipLaunchKernelGGL((attn16_bwd_kernel<D, T, DENSE, true>), dim3((parts + 3) / 4), dim3(256), smem, s, q, k, v, ld, bias, mask, rank, dout,
                            ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW, parts, scale, PadArg<false>{});
     } else {
-        allow_smem(&attn16_bwd_kernel<D, T, DENSE, false>, smem);
+        dhz_allow_smem(&attn16_bwd_kernel<D, T, DENSE, false>, smem);
         hipLaunchKernelGGL((attn16_bwd_kernel<D, T, DENSE, false>), dim3((parts + 3) / 4), dim3(256), smem, s, q, k, v, ld, bias, mask, rank, dout,
                            ldo, dq, dk, dv, ldg, dbias_part, B_, H, nW, parts, scale, PadArg<false>{});
     }

@@ -26,18 +26,10 @@
 //     MI355X_MICROARCH.md).  Transposed form: [32 k][BN] bf16 with the 16-byte-chunk swizzles of csrc/linear_bf16.hip.
 #include <stdlib.h>
 #include <type_traits>
-#include "common.h"
+#include "bf16_pipe.h"
 #include "tok_epilogue.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void glb_void;
 
 constexpr int BK = 32;          // contraction elements per stage
 constexpr int NT = 512;         // threads per workgroup (8 waves)
@@ -46,61 +38,9 @@ constexpr int NT = 512;         // threads per workgroup (8 waves)
 #define DHZ_S6_ABL 0            // timing diagnostics: 1 = no stores, 2 = no MFMAs, 4 = no activation split, 8 = no weight DMA, 16 = no fragment reads
 #endif
 
-__device__ __forceinline__ f32x4 mfma_bf16(s16x8 a, s16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 // (Non-temporal result stores were tried on the 256 x 128 kernel for results of 192 MB and more: in isolation T = 524288, 64 -> 256:
 // 170 -> 146 us, backward-data 256 <- 64: 180 -> 154 - but the training step did not move (35.11 / 35.26 ms without, 35.17 / 35.30 with):
 // what the store saves, the kernel that reads the result next pays.  Not used.)
-__device__ __forceinline__ void dma16(const void* g, void* l) {
-    __builtin_amdgcn_global_load_lds((glb_void*)g, (lds_void*)l, 16, 0, 0);
-}
-// byte offset of 16-byte chunk ch (0..3) of row `row` in a 64-byte-row image
-__device__ __forceinline__ int swz64(int row) { return (0x78 >> (2 * ((row >> 2) & 3))) & 3; }
-__device__ __forceinline__ int off64(int row, int ch) { return row * 64 + 16 * (ch ^ swz64(row)); }
-// transposed images (rows = contraction index, F output features per row): swizzles of csrc/linear_bf16.hip
-template <int F>
-__device__ __forceinline__ int swz_tr(int row) {
-    if (F == 128) return ((row & 3) << 2) | ((row >> 2) & 3);
-    return (row & 2) | ((row & 8) >> 1);
-}
-template <int F>
-__device__ __forceinline__ int off_tr(int row, int ch) { return row * (2 * F) + 16 * (ch ^ swz_tr<F>(row)); }
-template <int F>
-__device__ __forceinline__ s16x8 tr_frag(const unsigned char* img, int r0, int cb, int lane) {
-    const int m = lane & 15, q = m >> 2, p = m & 3;
-    typedef s16x4 __attribute__((address_space(3))) * lds_ptr;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(img + off_tr<F>(r0 + q, 2 * cb + (p >> 1)) + 8 * (p & 1)));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(img + off_tr<F>(r0 + 4 + q, 2 * cb + (p >> 1)) + 8 * (p & 1)));
-    return s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
-
-// eight fp32 values -> three bf16 pieces each, by truncation: a bf16 is the top 16 bits of the fp32 pattern, so each piece
-// takes the next eight significant bits of what is left (x - hi and r - mid are exact).  Per pair of elements: two masks and two
-// subtractions per level, one v_perm_b32 per piece to pack the two top halves.
-__device__ __forceinline__ uint32_t pack_top(float x1, float x0) {              // (x1 & 0xffff0000) | (x0 >> 16)
-    return __builtin_amdgcn_perm(__float_as_uint(x1), __float_as_uint(x0), 0x07060302u);
-}
-// Between two bf16 MFMAs of a wave the first two plain vector instructions cost nothing and further ones 4 cycles each, a PACKED fp32
-// instruction 7 - 17 cycles of matrix-pipe time (tools/ubench/interleave.hip): the subtractions are therefore issued per lane - 11
-// instructions per pair of elements instead of 9 - through inline asm (left as C, hipcc's SLP vectoriser re-packs them).
-__device__ __forceinline__ float sub_np(float a, float b) {
-    float r;
-    asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ void split8x3(const f32x4 a, const f32x4 b, u32x4& hi, u32x4& mid, u32x4& lo) {
-    const float x[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float x0 = x[2 * i], x1 = x[2 * i + 1];
-        const float r0 = sub_np(x0, __uint_as_float(__float_as_uint(x0) & 0xffff0000u)), r1 = sub_np(x1, __uint_as_float(__float_as_uint(x1) & 0xffff0000u));
-        const float q0 = sub_np(r0, __uint_as_float(__float_as_uint(r0) & 0xffff0000u)), q1 = sub_np(r1, __uint_as_float(__float_as_uint(r1) & 0xffff0000u));
-        hi[i] = pack_top(x1, x0);
-        mid[i] = pack_top(r1, r0);
-        lo[i] = pack_top(q1, q0);
-    }
-}
 
 // Activation loads as inline assembly: hipcc's wait-count pass does not see them, so it cannot answer a use of their registers
 // with vmcnt(0) (which would also wait for the LDS-DMA issued since).  The wait is explicit and counted - wait_regs<N> leaves the
@@ -179,7 +119,7 @@ __global__ __launch_bounds__(NT, 1) void split6_gemm_kernel(const float* __restr
         const int c = t + NT * i;
         a_row[i] = c >> 2;
         a_kc[i] = c & 3;
-        a_lds[i] = off64(a_row[i], a_kc[i]);
+        a_lds[i] = dhz_off64(a_row[i], a_kc[i]);
     }
     // ---- weight operand: this wave's DMA instructions q = w + 8 j -> (piece, KiB of the piece image); per-lane source offset
     int b_off[DPW];                 // elements, relative to (n0, k0) of the stage
@@ -194,10 +134,10 @@ __global__ __launch_bounds__(NT, 1) void split6_gemm_kernel(const float* __restr
         if (BTR) {
             constexpr int CPR = BN / 8;                            // 16-byte chunks per image row
             const int row = sub * (64 / CPR) + lane / CPR, pch = lane % CPR;
-            b_off[j] = row * ldb + 8 * (pch ^ swz_tr<BN>(row));
+            b_off[j] = row * ldb + 8 * (pch ^ dhz_swz_tr<BN>(row));
         } else {
             const int row = 16 * sub + (lane >> 2), pch = lane & 3;
-            b_off[j] = row * ldb + 8 * (pch ^ swz64(row));
+            b_off[j] = row * ldb + 8 * (pch ^ dhz_swz64(row));
         }
     }
     const uint16_t* const planes[3] = {Bh, Bm, Bl};
@@ -242,11 +182,11 @@ __global__ __launch_bounds__(NT, 1) void split6_gemm_kernel(const float* __restr
         unsigned char* As = Aring + slot * A_SLOT;
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
-            u32x4 hi, mid, lo;
-            split8x3(ra[S][i][0], ra[S][i][1], hi, mid, lo);
-            *reinterpret_cast<u32x4*>(As + a_lds[i]) = hi;
-            *reinterpret_cast<u32x4*>(As + A_BYTES + a_lds[i]) = mid;
-            *reinterpret_cast<u32x4*>(As + 2 * A_BYTES + a_lds[i]) = lo;
+            dhz_u32x4 hi, mid, lo;
+            dhz_split8x3_np(ra[S][i][0], ra[S][i][1], hi, mid, lo);
+            *reinterpret_cast<dhz_u32x4*>(As + a_lds[i]) = hi;
+            *reinterpret_cast<dhz_u32x4*>(As + A_BYTES + a_lds[i]) = mid;
+            *reinterpret_cast<dhz_u32x4*>(As + 2 * A_BYTES + a_lds[i]) = lo;
         }
     };
     auto b_dma = [&](const Pos& q, int slot) {
@@ -255,7 +195,7 @@ __global__ __launch_bounds__(NT, 1) void split6_gemm_kernel(const float* __restr
         const size_t base = BTR ? (size_t)k0 * ldb + n0 : (size_t)n0 * ldb + k0;
         unsigned char* Bs = Bring + slot * B_SLOT;
 #pragma unroll
-        for (int j = 0; j < DPW; ++j) dma16(planes[b_piece[j]] + base + b_off[j], Bs + b_dst[j]);
+        for (int j = 0; j < DPW; ++j) dhz_dma16(planes[b_piece[j]] + base + b_off[j], Bs + b_dst[j]);
     };
 
     f32x4 acc[WM][WN];
@@ -266,7 +206,7 @@ __global__ __launch_bounds__(NT, 1) void split6_gemm_kernel(const float* __restr
     for (int i = t; i < NF; i += NT) bsm[i] = bias ? bias[i] : 0.f;     // visible after the first barrier below
 
     // fragment sets: [set][piece][tile row / column]
-    s16x8 af[2][3][WM] = {}, bf[2][3][WN] = {};
+    dhz_s16x8 af[2][3][WM] = {}, bf[2][3][WN] = {};
     auto read_a = [&](auto set, int slot, int a0, int a1) {
         constexpr int F = decltype(set)::value;
         if (abl & 16) return;
@@ -275,7 +215,7 @@ __global__ __launch_bounds__(NT, 1) void split6_gemm_kernel(const float* __restr
         for (int pc = 0; pc < 3; ++pc)
 #pragma unroll
             for (int a = a0; a < a1; ++a)
-                af[F][pc][a] = *reinterpret_cast<const s16x8*>(As + pc * A_BYTES + off64((wm * WM + a) * 16 + i16, g));
+                af[F][pc][a] = *reinterpret_cast<const dhz_s16x8*>(As + pc * A_BYTES + dhz_off64((wm * WM + a) * 16 + i16, g));
     };
     auto read_b = [&](auto set, int slot) {
         constexpr int F = decltype(set)::value;
@@ -285,8 +225,8 @@ __global__ __launch_bounds__(NT, 1) void split6_gemm_kernel(const float* __restr
         for (int pc = 0; pc < 3; ++pc)
 #pragma unroll
             for (int b = 0; b < WN; ++b) {
-                if (BTR) bf[F][pc][b] = tr_frag<BN>(Bs + pc * B_BYTES, 8 * g, wn * WN + b, lane);
-                else bf[F][pc][b] = *reinterpret_cast<const s16x8*>(Bs + pc * B_BYTES + off64((wn * WN + b) * 16 + i16, g));
+                if (BTR) bf[F][pc][b] = dhz_tr_frag<BN>(Bs + pc * B_BYTES, 8 * g, wn * WN + b, lane);
+                else bf[F][pc][b] = *reinterpret_cast<const dhz_s16x8*>(Bs + pc * B_BYTES + dhz_off64((wn * WN + b) * 16 + i16, g));
             }
     };
     // the six products of every tile of rows [a0, a1), small terms first; term-major, so that consecutive MFMAs never wait for one
@@ -301,7 +241,7 @@ __global__ __launch_bounds__(NT, 1) void split6_gemm_kernel(const float* __restr
 #pragma unroll
                 for (int b = 0; b < WN; ++b) {
                     if (abl & 2) { acc[a][b][0] += (float)(af[F][TA[term]][a][0] + bf[F][TB[term]][b][0]); continue; }
-                    acc[a][b] = mfma_bf16(bf[F][TB[term]][b], af[F][TA[term]][a], acc[a][b]);
+                    acc[a][b] = dhz_mfma_bf16(bf[F][TB[term]][b], af[F][TA[term]][a], acc[a][b]);
                 }
     };
     // acc[a][b][j] = C[token 16 a + i16][feature 16 b + 4 g + j]  (D = C^T block: the weight fragment is the first MFMA operand)
@@ -409,9 +349,9 @@ __global__ __launch_bounds__(NT, 1) void split6_gemm_kernel(const float* __restr
         const float* pa[NA];
 #pragma unroll
         for (int i = 0; i < NA; ++i) pa[i] = a_addr(valid(p4), i);
-        u32x4 sh[NA], sm[NA], sl[NA];
+        dhz_u32x4 sh[NA], sm[NA], sl[NA];
 #pragma unroll
-        for (int i = 0; i < NA; ++i) split8x3(ra[R & 1][i][0], ra[R & 1][i][1], sh[i], sm[i], sl[i]);
+        for (int i = 0; i < NA; ++i) dhz_split8x3_np(ra[R & 1][i][0], ra[R & 1][i][1], sh[i], sm[i], sl[i]);
         mma_rows(F{}, 0, HALF);
 #pragma unroll
         for (int i = 0; i < HALF * WN * 6; ++i) {
@@ -428,9 +368,9 @@ __global__ __launch_bounds__(NT, 1) void split6_gemm_kernel(const float* __restr
             unsigned char* As = Aring + S2 * A_SLOT;
 #pragma unroll
             for (int i = 0; i < NA; ++i) {
-                *reinterpret_cast<u32x4*>(As + a_lds[i]) = sh[i];
-                *reinterpret_cast<u32x4*>(As + A_BYTES + a_lds[i]) = sm[i];
-                *reinterpret_cast<u32x4*>(As + 2 * A_BYTES + a_lds[i]) = sl[i];
+                *reinterpret_cast<dhz_u32x4*>(As + a_lds[i]) = sh[i];
+                *reinterpret_cast<dhz_u32x4*>(As + A_BYTES + a_lds[i]) = sm[i];
+                *reinterpret_cast<dhz_u32x4*>(As + 2 * A_BYTES + a_lds[i]) = sl[i];
             }
         }
         read_b(FN{}, S1);
@@ -508,7 +448,7 @@ __global__ __launch_bounds__(NT, 1) void split6_wide_kernel(const float* __restr
         const int c = t + NT * i;
         a_row[i] = c >> 2;
         a_kc[i] = c & 3;
-        a_lds[i] = off64(a_row[i], a_kc[i]);
+        a_lds[i] = dhz_off64(a_row[i], a_kc[i]);
     }
     int b_off[DPW], b_dst[DPW], b_piece[DPW];
 #pragma unroll
@@ -520,10 +460,10 @@ __global__ __launch_bounds__(NT, 1) void split6_wide_kernel(const float* __restr
         if (BTR) {
             constexpr int CPR = BN / 8;
             const int row = sub * (64 / CPR) + lane / CPR, pch = lane % CPR;
-            b_off[j] = row * ldb + 8 * (pch ^ swz_tr<BN>(row));
+            b_off[j] = row * ldb + 8 * (pch ^ dhz_swz_tr<BN>(row));
         } else {
             const int row = 16 * sub + (lane >> 2), pch = lane & 3;
-            b_off[j] = row * ldb + 8 * (pch ^ swz64(row));
+            b_off[j] = row * ldb + 8 * (pch ^ dhz_swz64(row));
         }
     }
     const uint16_t* const planes[3] = {Bh, Bm, Bl};
@@ -554,15 +494,15 @@ __global__ __launch_bounds__(NT, 1) void split6_wide_kernel(const float* __restr
         const size_t base = BTR ? (size_t)k0 * ldb + n0 : (size_t)n0 * ldb + k0;
         unsigned char* Bs = smem + buf * SLOT;
 #pragma unroll
-        for (int j = 0; j < DPW; ++j) dma16(planes[b_piece[j]] + base + b_off[j], Bs + b_dst[j]);
+        for (int j = 0; j < DPW; ++j) dhz_dma16(planes[b_piece[j]] + base + b_off[j], Bs + b_dst[j]);
     };
-    auto a_write = [&](int buf, const u32x4 (&sh)[NA], const u32x4 (&sm)[NA], const u32x4 (&sl)[NA]) {
+    auto a_write = [&](int buf, const dhz_u32x4 (&sh)[NA], const dhz_u32x4 (&sm)[NA], const dhz_u32x4 (&sl)[NA]) {
         unsigned char* As = smem + buf * SLOT;
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
-            *reinterpret_cast<u32x4*>(As + a_lds[i]) = sh[i];
-            *reinterpret_cast<u32x4*>(As + A_BYTES + a_lds[i]) = sm[i];
-            *reinterpret_cast<u32x4*>(As + 2 * A_BYTES + a_lds[i]) = sl[i];
+            *reinterpret_cast<dhz_u32x4*>(As + a_lds[i]) = sh[i];
+            *reinterpret_cast<dhz_u32x4*>(As + A_BYTES + a_lds[i]) = sm[i];
+            *reinterpret_cast<dhz_u32x4*>(As + 2 * A_BYTES + a_lds[i]) = sl[i];
         }
     };
     f32x4 acc[WM][WN];
@@ -572,14 +512,14 @@ __global__ __launch_bounds__(NT, 1) void split6_wide_kernel(const float* __restr
         for (int b = 0; b < WN; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int i = t; i < NF; i += NT) bsm[i] = bias ? bias[i] : 0.f;
 
-    s16x8 af[3][WM], bf[3][WN];
+    dhz_s16x8 af[3][WM], bf[3][WN];
     auto read_a = [&](int buf, int a0, int a1) {
         const unsigned char* As = smem + buf * SLOT;
 #pragma unroll
         for (int pc = 0; pc < 3; ++pc)
 #pragma unroll
             for (int a = a0; a < a1; ++a)
-                af[pc][a] = *reinterpret_cast<const s16x8*>(As + pc * A_BYTES + off64((wm * WM + a) * 16 + i16, g));
+                af[pc][a] = *reinterpret_cast<const dhz_s16x8*>(As + pc * A_BYTES + dhz_off64((wm * WM + a) * 16 + i16, g));
     };
     auto read_b = [&](int buf) {
         const unsigned char* Bs = smem + buf * SLOT + 3 * A_BYTES;
@@ -587,8 +527,8 @@ __global__ __launch_bounds__(NT, 1) void split6_wide_kernel(const float* __restr
         for (int pc = 0; pc < 3; ++pc)
 #pragma unroll
             for (int b = 0; b < WN; ++b) {
-                if (BTR) bf[pc][b] = tr_frag<BN>(Bs + pc * B_BYTES, 8 * g, wn * WN + b, lane);
-                else bf[pc][b] = *reinterpret_cast<const s16x8*>(Bs + pc * B_BYTES + off64((wn * WN + b) * 16 + i16, g));
+                if (BTR) bf[pc][b] = dhz_tr_frag<BN>(Bs + pc * B_BYTES, 8 * g, wn * WN + b, lane);
+                else bf[pc][b] = *reinterpret_cast<const dhz_s16x8*>(Bs + pc * B_BYTES + dhz_off64((wn * WN + b) * 16 + i16, g));
             }
     };
     auto mma_rows = [&](int a0, int a1) {
@@ -598,7 +538,7 @@ __global__ __launch_bounds__(NT, 1) void split6_wide_kernel(const float* __restr
 #pragma unroll
             for (int term = 0; term < 6; ++term)
 #pragma unroll
-                for (int b = 0; b < WN; ++b) acc[a][b] = mfma_bf16(bf[TB[term]][b], af[TA[term]][a], acc[a][b]);
+                for (int b = 0; b < WN; ++b) acc[a][b] = dhz_mfma_bf16(bf[TB[term]][b], af[TA[term]][a], acc[a][b]);
     };
     auto epilogue = [&](int tile) -> bool {
         const int tn = tile % tiles_n, tm = tile / tiles_n;
@@ -666,9 +606,9 @@ __global__ __launch_bounds__(NT, 1) void split6_wide_kernel(const float* __restr
     for (int i = 0; i < NA; ++i) gload32(a_addr(p0, i), ra[i][0], ra[i][1]);
     a_wait0();
     {
-        u32x4 sh[NA], sm[NA], sl[NA];
+        dhz_u32x4 sh[NA], sm[NA], sl[NA];
 #pragma unroll
-        for (int i = 0; i < NA; ++i) split8x3(ra[i][0], ra[i][1], sh[i], sm[i], sl[i]);
+        for (int i = 0; i < NA; ++i) dhz_split8x3_np(ra[i][0], ra[i][1], sh[i], sm[i], sl[i]);
         a_write(0, sh, sm, sl);
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -688,9 +628,9 @@ __global__ __launch_bounds__(NT, 1) void split6_wide_kernel(const float* __restr
         a_waitN();                                                 // older than this stage's DMA (and the previous tile's stores)
         __builtin_amdgcn_sched_barrier(0);
         read_a(buf, 2, 4);
-        u32x4 sh[NA], sm[NA], sl[NA];
+        dhz_u32x4 sh[NA], sm[NA], sl[NA];
 #pragma unroll
-        for (int i = 0; i < NA; ++i) split8x3(ra[i][0], ra[i][1], sh[i], sm[i], sl[i]);
+        for (int i = 0; i < NA; ++i) dhz_split8x3_np(ra[i][0], ra[i][1], sh[i], sm[i], sl[i]);
         const float* pa[NA];
 #pragma unroll
         for (int i = 0; i < NA; ++i) pa[i] = a_addr(valid(p2), i);
@@ -809,11 +749,11 @@ __global__ __launch_bounds__(256) void split3_planes_kernel(const float* __restr
                                                             uint16_t* __restrict__ mid, uint16_t* __restrict__ lo) {
     for (long i = blockIdx.x * 256L + threadIdx.x; i < n8; i += (long)gridDim.x * 256) {
         const f32x4 a = *reinterpret_cast<const f32x4*>(src + 8 * i), b = *reinterpret_cast<const f32x4*>(src + 8 * i + 4);
-        u32x4 h, m, l;
-        split8x3(a, b, h, m, l);
-        *reinterpret_cast<u32x4*>(hi + 8 * i) = h;
-        *reinterpret_cast<u32x4*>(mid + 8 * i) = m;
-        *reinterpret_cast<u32x4*>(lo + 8 * i) = l;
+        dhz_u32x4 h, m, l;
+        dhz_split8x3_np(a, b, h, m, l);
+        *reinterpret_cast<dhz_u32x4*>(hi + 8 * i) = h;
+        *reinterpret_cast<dhz_u32x4*>(mid + 8 * i) = m;
+        *reinterpret_cast<dhz_u32x4*>(lo + 8 * i) = l;
     }
 }
 

@@ -14,19 +14,12 @@
 //                                                           act: the saved post-ReLU map that is this layer's input)
 // Also here: the 2x2 max pooling between stages (forward, and backward fused with the ReLU below it) and the two L1 distances of
 // one feature tap, on bf16 NHWC maps.
-#include "common.h"
+#include "bf16_pipe.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int BK = 64;
 
-__device__ __forceinline__ f32x4 mfma_bf16(s16x8 a, s16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 __device__ __forceinline__ int off_row(int row, int ch) { return row * 128 + 16 * (ch ^ ((row >> 1) & 7)); }
 // the filter (B) image is read in the row order of csrc/linear_bf16.hip::perm_row, so that a lane owns 8 consecutive output channels
 // per pair of fragment blocks (16-byte stores / mask / addend loads in 64-byte runs); its swizzle key follows that order
@@ -72,7 +65,7 @@ __global__ __launch_bounds__(256, 2) void conv3_bf16_kernel(const uint16_t* __re
     // to come back from L2 / HBM - one stage of look-ahead left the pipe waiting on every stage.  The request stream
     // is its own cursor over (tile, stage) and runs across tile boundaries; past the end of this workgroup's tiles it keeps
     // re-requesting its last position (unconditional loads keep the compiler's vmcnt accounting exact).
-    u32x4 ra[2][NA], rb[2][NB];
+    dhz_u32x4 ra[2][NA], rb[2][NB];
     const uint16_t* pa[NA];
     int pyx[NA];                                                 // (row << 16) | column of the pixel whose chunk this thread stages
     const uint16_t* pb[NB];
@@ -93,7 +86,7 @@ __global__ __launch_bounds__(256, 2) void conv3_bf16_kernel(const uint16_t* __re
             pb[i] = Wp + (size_t)(n0 + (e >> 3)) * K + 8 * (e & 7);
         }
     };
-    auto gload = [&](int k0, u32x4 (&A)[NA], u32x4 (&B)[NB]) {
+    auto gload = [&](int k0, dhz_u32x4 (&A)[NA], dhz_u32x4 (&B)[NB]) {
         const int tap = k0 >> lgC, c0 = k0 & (Cin - 1);
         const int dy = ((tap * 11) >> 5) - 1, dx = tap - 3 * (dy + 1) - 1;
         const int off = ((dy * W + dx) << lgC) + c0;             // elements; negative for the taps above / left
@@ -101,24 +94,24 @@ __global__ __launch_bounds__(256, 2) void conv3_bf16_kernel(const uint16_t* __re
         for (int i = 0; i < NA; ++i) {
             const int py = pyx[i] >> 16, px = pyx[i] & 0xffff;
             const bool ok = (unsigned)(py + dy) < (unsigned)H && (unsigned)(px + dx) < (unsigned)W;
-            const u32x4 v = *reinterpret_cast<const u32x4*>(ok ? pa[i] + off : pa[i]);
-            A[i] = ok ? v : u32x4{0u, 0u, 0u, 0u};
+            const dhz_u32x4 v = *reinterpret_cast<const dhz_u32x4*>(ok ? pa[i] + off : pa[i]);
+            A[i] = ok ? v : dhz_u32x4{0u, 0u, 0u, 0u};
         }
 #pragma unroll
-        for (int i = 0; i < NB; ++i) B[i] = *reinterpret_cast<const u32x4*>(pb[i] + k0);
+        for (int i = 0; i < NB; ++i) B[i] = *reinterpret_cast<const dhz_u32x4*>(pb[i] + k0);
     };
-    auto swrite = [&](int buf, const u32x4 (&A)[NA], const u32x4 (&B)[NB]) {
+    auto swrite = [&](int buf, const dhz_u32x4 (&A)[NA], const dhz_u32x4 (&B)[NB]) {
         unsigned char* As = smem + buf * STAGE;
         unsigned char* Bs = As + A_BYTES;
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
             const int e = t + 256 * i;
-            *reinterpret_cast<u32x4*>(As + off_row(e >> 3, e & 7)) = A[i];
+            *reinterpret_cast<dhz_u32x4*>(As + off_row(e >> 3, e & 7)) = A[i];
         }
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
             const int e = t + 256 * i;
-            *reinterpret_cast<u32x4*>(Bs + off_rowp(e >> 3, e & 7)) = B[i];
+            *reinterpret_cast<dhz_u32x4*>(Bs + off_rowp(e >> 3, e & 7)) = B[i];
         }
     };
 
@@ -128,7 +121,7 @@ __global__ __launch_bounds__(256, 2) void conv3_bf16_kernel(const uint16_t* __re
     const int total = mytiles * nst;                             // stages of this workgroup over all its tiles
     int l_ti = 0, l_st = 0;                                      // request cursor
     set_tile(tile);
-    auto request = [&](u32x4 (&A)[NA], u32x4 (&B)[NB]) {
+    auto request = [&](dhz_u32x4 (&A)[NA], dhz_u32x4 (&B)[NB]) {
         gload(l_st * BK, A, B);
         if (++l_st == nst) {
             const int nt = tile_of(l_ti + 1);
@@ -143,23 +136,23 @@ __global__ __launch_bounds__(256, 2) void conv3_bf16_kernel(const uint16_t* __re
     const int sw = (i16 >> 1) & 7;
     int buf = 0, st = 0, ti = 0;
     // one stage: request stage gs + 2 into the set stage gs came from, multiply stage gs, stage gs + 1 into the other LDS buffer
-    auto stage = [&](int gs, u32x4 (&Aq)[NA], u32x4 (&Bq)[NB], const u32x4 (&Aw)[NA], const u32x4 (&Bw)[NB]) {
+    auto stage = [&](int gs, dhz_u32x4 (&Aq)[NA], dhz_u32x4 (&Bq)[NB], const dhz_u32x4 (&Aw)[NA], const dhz_u32x4 (&Bw)[NB]) {
         request(Aq, Bq);
         const unsigned char* As = smem + buf * STAGE;
         const unsigned char* Bs = As + A_BYTES;
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            s16x8 af[WM], bf[WN];
+            dhz_s16x8 af[WM], bf[WN];
 #pragma unroll
             for (int a = 0; a < WM; ++a)
-                af[a] = *reinterpret_cast<const s16x8*>(As + (wm * WM * 16 + a * 16 + i16) * 128 + 16 * ((4 * s + g) ^ sw));
+                af[a] = *reinterpret_cast<const dhz_s16x8*>(As + (wm * WM * 16 + a * 16 + i16) * 128 + 16 * ((4 * s + g) ^ sw));
 #pragma unroll
             for (int b = 0; b < WN; ++b)
-                bf[b] = *reinterpret_cast<const s16x8*>(Bs + off_rowp(wn * WN * 16 + perm_row(b, i16), 4 * s + g));
+                bf[b] = *reinterpret_cast<const dhz_s16x8*>(Bs + off_rowp(wn * WN * 16 + perm_row(b, i16), 4 * s + g));
 #pragma unroll
             for (int a = 0; a < WM; ++a)
 #pragma unroll
-                for (int b = 0; b < WN; ++b) acc[a][b] = mfma_bf16(bf[b], af[a], acc[a][b]);     // D = C^T block (epilogue)
+                for (int b = 0; b < WN; ++b) acc[a][b] = dhz_mfma_bf16(bf[b], af[a], acc[a][b]);     // D = C^T block (epilogue)
         }
         if (gs + 1 < total) {
             swrite(buf ^ 1, Aw, Bw);
@@ -190,21 +183,21 @@ __global__ __launch_bounds__(256, 2) void conv3_bf16_kernel(const uint16_t* __re
                         }
                         if (act) {
                             if (addend) {
-                                const u32x4 ad = *reinterpret_cast<const u32x4*>(addend + o);
+                                const dhz_u32x4 ad = *reinterpret_cast<const dhz_u32x4*>(addend + o);
                                 v0 += unpack4(ad[0], ad[1]);
                                 v1 += unpack4(ad[2], ad[3]);
                             }
-                            const u32x4 mk = *reinterpret_cast<const u32x4*>(act + o);
+                            const dhz_u32x4 mk = *reinterpret_cast<const dhz_u32x4*>(act + o);
                             const f32x4 m0v = unpack4(mk[0], mk[1]), m1v = unpack4(mk[2], mk[3]);
                             v0 = f32x4{m0v[0] > 0.f ? v0[0] : 0.f, m0v[1] > 0.f ? v0[1] : 0.f, m0v[2] > 0.f ? v0[2] : 0.f, m0v[3] > 0.f ? v0[3] : 0.f};
                             v1 = f32x4{m1v[0] > 0.f ? v1[0] : 0.f, m1v[1] > 0.f ? v1[1] : 0.f, m1v[2] > 0.f ? v1[2] : 0.f, m1v[3] > 0.f ? v1[3] : 0.f};
                         }
-                        u32x4 r;
+                        dhz_u32x4 r;
                         r[0] = (uint32_t)f32_to_bf16(v0[0]) | ((uint32_t)f32_to_bf16(v0[1]) << 16);
                         r[1] = (uint32_t)f32_to_bf16(v0[2]) | ((uint32_t)f32_to_bf16(v0[3]) << 16);
                         r[2] = (uint32_t)f32_to_bf16(v1[0]) | ((uint32_t)f32_to_bf16(v1[1]) << 16);
                         r[3] = (uint32_t)f32_to_bf16(v1[2]) | ((uint32_t)f32_to_bf16(v1[3]) << 16);
-                        *reinterpret_cast<u32x4*>(Y + o) = r;
+                        *reinterpret_cast<dhz_u32x4*>(Y + o) = r;
                     }
                 }
             }
@@ -257,15 +250,15 @@ __global__ __launch_bounds__(256) void vgg_prepack_bf16_kernel(const float* __re
 }
 
 // ---- 2x2 / stride-2 max pooling of NHWC bf16 maps; one thread = 8 channels (16 bytes) of one pooled pixel
-__device__ __forceinline__ void unpack8(u32x4 v, float (&f)[8]) {
+__device__ __forceinline__ void unpack8(dhz_u32x4 v, float (&f)[8]) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         f[2 * i] = __uint_as_float(v[i] << 16);
         f[2 * i + 1] = __uint_as_float(v[i] & 0xffff0000u);
     }
 }
-__device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
-    u32x4 v;
+__device__ __forceinline__ dhz_u32x4 pack8(const float (&f)[8]) {
+    dhz_u32x4 v;
 #pragma unroll
     for (int i = 0; i < 4; ++i) v[i] = (uint32_t)f32_to_bf16(f[2 * i]) | ((uint32_t)f32_to_bf16(f[2 * i + 1]) << 16);
     return v;
@@ -284,13 +277,13 @@ __global__ __launch_bounds__(256) void maxpool2x2_nhwc_bf16_fwd_kernel(const uin
     const size_t rowb = (size_t)2 * Wo * C8 * 8;                         // elements per input row
     const uint16_t* src = x + ((size_t)(n * 2 * Ho + 2 * ho)) * rowb + (size_t)(2 * wo) * C8 * 8 + 8 * c8;
     float a[8], b[8], c[8], d[8], m[8];
-    unpack8(*reinterpret_cast<const u32x4*>(src), a);
-    unpack8(*reinterpret_cast<const u32x4*>(src + C8 * 8), b);
-    unpack8(*reinterpret_cast<const u32x4*>(src + rowb), c);
-    unpack8(*reinterpret_cast<const u32x4*>(src + rowb + C8 * 8), d);
+    unpack8(*reinterpret_cast<const dhz_u32x4*>(src), a);
+    unpack8(*reinterpret_cast<const dhz_u32x4*>(src + C8 * 8), b);
+    unpack8(*reinterpret_cast<const dhz_u32x4*>(src + rowb), c);
+    unpack8(*reinterpret_cast<const dhz_u32x4*>(src + rowb + C8 * 8), d);
 #pragma unroll
     for (int i = 0; i < 8; ++i) m[i] = fmaxf(fmaxf(a[i], b[i]), fmaxf(c[i], d[i]));
-    *reinterpret_cast<u32x4*>(y + e * 8) = pack8(m);
+    *reinterpret_cast<dhz_u32x4*>(y + e * 8) = pack8(m);
 }
 
 // Backward of the pooling of a post-ReLU map `act`: the gradient goes to the FIRST maximum of each window in scan order (the
@@ -309,11 +302,11 @@ __global__ __launch_bounds__(256) void maxpool2x2_nhwc_bf16_bwd_kernel(const uin
     const size_t rowb = (size_t)2 * Wo * C8 * 8;
     const size_t o = ((size_t)(n * 2 * Ho + 2 * ho)) * rowb + (size_t)(2 * wo) * C8 * 8 + 8 * c8;
     float a[8], b[8], c[8], d[8], g[8], ra[8], rb[8], rc[8], rd[8];
-    unpack8(*reinterpret_cast<const u32x4*>(act + o), a);
-    unpack8(*reinterpret_cast<const u32x4*>(act + o + C8 * 8), b);
-    unpack8(*reinterpret_cast<const u32x4*>(act + o + rowb), c);
-    unpack8(*reinterpret_cast<const u32x4*>(act + o + rowb + C8 * 8), d);
-    unpack8(*reinterpret_cast<const u32x4*>(gy + e * 8), g);
+    unpack8(*reinterpret_cast<const dhz_u32x4*>(act + o), a);
+    unpack8(*reinterpret_cast<const dhz_u32x4*>(act + o + C8 * 8), b);
+    unpack8(*reinterpret_cast<const dhz_u32x4*>(act + o + rowb), c);
+    unpack8(*reinterpret_cast<const dhz_u32x4*>(act + o + rowb + C8 * 8), d);
+    unpack8(*reinterpret_cast<const dhz_u32x4*>(gy + e * 8), g);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const float m = fmaxf(fmaxf(a[i], b[i]), fmaxf(c[i], d[i]));
@@ -324,10 +317,10 @@ __global__ __launch_bounds__(256) void maxpool2x2_nhwc_bf16_bwd_kernel(const uin
         rc[i] = ic ? gv : 0.f;
         rd[i] = (!ia && !ib && !ic) ? gv : 0.f;
     }
-    *reinterpret_cast<u32x4*>(gx + o) = pack8(ra);
-    *reinterpret_cast<u32x4*>(gx + o + C8 * 8) = pack8(rb);
-    *reinterpret_cast<u32x4*>(gx + o + rowb) = pack8(rc);
-    *reinterpret_cast<u32x4*>(gx + o + rowb + C8 * 8) = pack8(rd);
+    *reinterpret_cast<dhz_u32x4*>(gx + o) = pack8(ra);
+    *reinterpret_cast<dhz_u32x4*>(gx + o + C8 * 8) = pack8(rb);
+    *reinterpret_cast<dhz_u32x4*>(gx + o + rowb) = pack8(rc);
+    *reinterpret_cast<dhz_u32x4*>(gx + o + rowb + C8 * 8) = pack8(rd);
 }
 
 // ---- the two L1 distances of one feature tap (My_CR.py:108-112) on bf16 maps: fp32 differences and sums, 8 elements per lane
@@ -344,12 +337,12 @@ __global__ __launch_bounds__(256) void l1_pair_bf16_fwd_kernel(const uint16_t* _
     float sp = 0.f, sn = 0.f;
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n8; e += (int64_t)gridDim.x * 256) {
         float av[8], pv[8], nv[8];
-        unpack8(reinterpret_cast<const u32x4*>(a)[e], av);
-        unpack8(reinterpret_cast<const u32x4*>(p)[e], pv);
+        unpack8(reinterpret_cast<const dhz_u32x4*>(a)[e], av);
+        unpack8(reinterpret_cast<const dhz_u32x4*>(p)[e], pv);
 #pragma unroll
         for (int i = 0; i < 8; ++i) sp += fabsf(av[i] - pv[i]);
         if (n) {
-            unpack8(reinterpret_cast<const u32x4*>(n)[e], nv);
+            unpack8(reinterpret_cast<const dhz_u32x4*>(n)[e], nv);
 #pragma unroll
             for (int i = 0; i < 8; ++i) sn += fabsf(av[i] - nv[i]);
         }
@@ -371,16 +364,16 @@ __global__ __launch_bounds__(256) void l1_pair_bf16_bwd_kernel(const uint16_t* _
     auto sgn = [](float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); };
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n8; e += (int64_t)gridDim.x * 256) {
         float av[8], pv[8], nv[8], r[8];
-        unpack8(reinterpret_cast<const u32x4*>(a)[e], av);
-        unpack8(reinterpret_cast<const u32x4*>(p)[e], pv);
+        unpack8(reinterpret_cast<const dhz_u32x4*>(a)[e], av);
+        unpack8(reinterpret_cast<const dhz_u32x4*>(p)[e], pv);
 #pragma unroll
         for (int i = 0; i < 8; ++i) r[i] = cp * sgn(av[i] - pv[i]);
         if (n) {
-            unpack8(reinterpret_cast<const u32x4*>(n)[e], nv);
+            unpack8(reinterpret_cast<const dhz_u32x4*>(n)[e], nv);
 #pragma unroll
             for (int i = 0; i < 8; ++i) r[i] += cn * sgn(av[i] - nv[i]);
         }
-        reinterpret_cast<u32x4*>(da)[e] = pack8(r);
+        reinterpret_cast<dhz_u32x4*>(da)[e] = pack8(r);
     }
 }
 

@@ -39,17 +39,13 @@
 // roundings decide the ReLU masks of the backward pass) and uses this kernel for the no-gradient passes and the backward-data products.
 #include <stdlib.h>
 #include <type_traits>
-#include "common.h"
+#include "bf16_pipe.h"
 
 #ifndef W43_ABL
 #define W43_ABL 0       // timing diagnostics: 1 no input transform, 2 no DMA, 4 no MFMAs, 16 window reads but no transform arithmetic
 #endif
 
 namespace {
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void glb_void;
 
 constexpr int KB = 32;              // output channels per workgroup (= per wave)
 constexpr int CC = 8;               // input channels per group (the layout's channel block)
@@ -77,14 +73,11 @@ constexpr float PA = 0.75f, PB = 1.5f;
 constexpr float A2 = PA * PA, B2 = PB * PB, A2B2 = A2 * B2, SAB = A2 + B2, AB2 = PA * B2, A2B = A2 * PB;
 constexpr float A3 = A2 * PA, B3 = B2 * PB;
 
-__device__ __forceinline__ void dma16(const float* g, float* l) {
-    __builtin_amdgcn_global_load_lds((glb_void*)g, (lds_void*)l, 16, 0, 0);
-}
-// the same request with its address as (64-bit base in SGPRs) + (unsigned 32-bit byte offset per lane): hipcc selects the all-VGPR address
+// the dhz_dma16 request with its address as (64-bit base in SGPRs) + (unsigned 32-bit byte offset per lane): hipcc selects the all-VGPR address
 // form for the builtin (a 64-bit vector add per request); written out, the request needs no vector instruction at all
 __device__ __forceinline__ void dma16s(const char* sbase, unsigned voff, float* l) {
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-                 :: "v"(voff), "s"(sbase), "s"((unsigned)(size_t)(lds_void*)l) : "memory", "m0");
+                 :: "v"(voff), "s"(sbase), "s"((unsigned)(size_t)(dhz_lds_void*)l) : "memory", "m0");
 }
 
 // 288 accumulator registers against 256 AGPRs: left to itself hipcc keeps 240 in AGPRs, the rest in VGPRs, and SHUTTLES the latter through
@@ -108,12 +101,12 @@ __device__ __forceinline__ void mfma_acc_v(f32x4& acc, float a, float b) {
 // parts PA d3 - PA B2 d1 = PA (d3 - B2 d1) and PB (d3 - A2 d1) take their factor in the FMA that forms the +- rows (written as sums of
 // products hipcc emits 16 - the two extra multiplications of each of the twelve transforms were 12 % of the vector work of a group, and
 // vector work ADDS to the matrix time on this part: tools/ubench/overlap.hip)
-__device__ __forceinline__ f32x2 fma2(float a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(f32x2{a, a}, b, c); }
-__device__ __forceinline__ void bt6(f32x2& d0, f32x2& d1, f32x2& d2, f32x2& d3, f32x2& d4, f32x2& d5) {
-    const f32x2 ea = fma2(-B2, d2, d4), eb = fma2(-A2, d2, d4);
-    const f32x2 ua = fma2(-B2, d1, d3), ub = fma2(-A2, d1, d3);
-    const f32x2 t0 = fma2(A2B2, d0, fma2(-SAB, d2, d4));
-    const f32x2 t5 = fma2(A2B2, d1, fma2(-SAB, d3, d5));
+__device__ __forceinline__ dhz_f32x2 fma2(float a, dhz_f32x2 b, dhz_f32x2 c) { return __builtin_elementwise_fma(dhz_f32x2{a, a}, b, c); }
+__device__ __forceinline__ void bt6(dhz_f32x2& d0, dhz_f32x2& d1, dhz_f32x2& d2, dhz_f32x2& d3, dhz_f32x2& d4, dhz_f32x2& d5) {
+    const dhz_f32x2 ea = fma2(-B2, d2, d4), eb = fma2(-A2, d2, d4);
+    const dhz_f32x2 ua = fma2(-B2, d1, d3), ub = fma2(-A2, d1, d3);
+    const dhz_f32x2 t0 = fma2(A2B2, d0, fma2(-SAB, d2, d4));
+    const dhz_f32x2 t5 = fma2(A2B2, d1, fma2(-SAB, d3, d5));
     d0 = t0; d1 = fma2(PA, ua, ea); d2 = fma2(-PA, ua, ea); d3 = fma2(PB, ub, eb); d4 = fma2(-PB, ub, eb); d5 = t5;
 }
 // A^T m for one 6-vector -> 4 outputs
@@ -227,14 +220,14 @@ __global__ __launch_bounds__(256, 1) void winograd43_conv3x3_kernel(const float*
     // by the matrix phase in position order - and REFILLED with the next group's window as soon as its positions are dead (rows 0 .. 4 after
     // pair-step 14, row 5 after the last one): the 36 LDS reads of a group (18 KiB per wave, 580 cycles of the CU's LDS bandwidth with nothing
     // else to run beside them) now overlap the last matrix instructions of the group before
-    f32x2 v[6][6];
+    dhz_f32x2 v[6][6];
     auto read_rows = [&](int a0, int a1) {
 #pragma unroll
         for (int a = 0; a < 6; ++a) {
             if (a < a0 || a >= a1) continue;
             const float* p = pread0 + (a * 18 + (a >> 2)) * 4;
 #pragma unroll
-            for (int b = 0; b < 6; ++b) v[a][b] = *reinterpret_cast<const f32x2*>(p + 4 * b);
+            for (int b = 0; b < 6; ++b) v[a][b] = *reinterpret_cast<const dhz_f32x2*>(p + 4 * b);
         }
     };
     if (!(W43_ABL & 1)) read_rows(0, 6);
@@ -256,7 +249,7 @@ __global__ __launch_bounds__(256, 1) void winograd43_conv3x3_kernel(const float*
 #pragma unroll
             for (int a = 0; a < 6; ++a)
 #pragma unroll
-                for (int b = 0; b < 6; ++b) v[a][b] = f32x2{1.f, 1.f};
+                for (int b = 0; b < 6; ++b) v[a][b] = dhz_f32x2{1.f, 1.f};
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // my runs of filter slice cb have landed
         __syncthreads();
@@ -271,7 +264,7 @@ __global__ __launch_bounds__(256, 1) void winograd43_conv3x3_kernel(const float*
                 nhi = *reinterpret_cast<const f32x4*>(up + (j + 1) * 512 + 256);
             }
             const int xi = 2 * j;
-            const f32x2 v0 = v[xi / 6][xi % 6], v1 = v[(xi + 1) / 6][(xi + 1) % 6];
+            const dhz_f32x2 v0 = v[xi / 6][xi % 6], v1 = v[(xi + 1) / 6][(xi + 1) % 6];
             __builtin_amdgcn_sched_barrier(0);
             if (!(W43_ABL & 4)) {
                 if (xi < NXA) {                                   // (xi is a constant after unrolling; xi and xi + 1 are on the same side)

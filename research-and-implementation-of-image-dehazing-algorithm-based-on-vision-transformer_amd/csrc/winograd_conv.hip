@@ -30,15 +30,13 @@
 // weights are frozen, My_CR.py:75-77) and the ReLU mask of the saved activation applied to the patch.
 #include <stdlib.h>
 #include <type_traits>
-#include "common.h"
+#include "bf16_pipe.h"
 
 #ifndef WINO_ABL
 #define WINO_ABL 0      // timing diagnostics (tools/variants.sh): 1 no input transform, 2 no global loads in the loop, 4 no MFMAs, 8 no V / filter LDS traffic of the next group
 #endif
 
 namespace {
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int KB = 32;             // output channels per workgroup
 constexpr int CC = 8;              // input channels per step (= the layout's channel block)
@@ -51,13 +49,6 @@ constexpr int YS = 68;             // output staging stride per output channel (
 constexpr int NP4 = 4;             // float4 patch slots per lane: 6 x 18 px x 2 halves = 216 of 256
 constexpr int NUBUF = 3;           // filter ring
 constexpr size_t WINO_SMEM = (size_t)(NUBUF * UF + 8 * WAVE_LDS + KB) * sizeof(float);   // 152 KB: one workgroup per CU
-
-__device__ __forceinline__ void wave_sync() {
-    // LDS operations of one wave execute in order; only the compiler must not move accesses across phase boundaries
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // Epilogue: y = conv(x) [+ bias] [ReLU]  (forward)   or   y = mask > 0 ? conv(x) + addend : 0  (backward data: `mask` is
 // the saved post-ReLU activation at the OUTPUT positions, i.e. the ReLU of the layer below, `addend` the gradient that
@@ -166,7 +157,7 @@ __global__ __launch_bounds__(512) void winograd_conv3x3_kernel(const float* __re
     };
 
     // ---- input transform of the lane's (channel pair g, tile i16), both channels packed: d rows -> B^T d -> (B^T d) B
-    f32x2 d[4][4];                                       // patch values, then B^T d, then the 16 V values (in place)
+    dhz_f32x2 d[4][4];                                       // patch values, then B^T d, then the 16 V values (in place)
     const float* pread = pw + g * PPL + (2 * (i16 >> 3)) * RS + (i16 & 7) * 4;
     // Q8: window row 0 / 3 (column 0 / 3) of a tile that starts / ends an 8-pixel image belongs to the neighbouring image
     float fr0 = 1.f, fr3 = 1.f, fc0 = 1.f, fc3 = 1.f;
@@ -178,8 +169,8 @@ __global__ __launch_bounds__(512) void winograd_conv3x3_kernel(const float* __re
     auto read_row = [&](int a) {
         const float4 q0 = *reinterpret_cast<const float4*>(pread + a * RS);       // px 0,1 x (c0,c1)
         const float4 q1 = *reinterpret_cast<const float4*>(pread + a * RS + 4);   // px 2,3
-        d[a][0] = f32x2{q0.x, q0.y}; d[a][1] = f32x2{q0.z, q0.w};
-        d[a][2] = f32x2{q1.x, q1.y}; d[a][3] = f32x2{q1.z, q1.w};
+        d[a][0] = dhz_f32x2{q0.x, q0.y}; d[a][1] = dhz_f32x2{q0.z, q0.w};
+        d[a][2] = dhz_f32x2{q1.x, q1.y}; d[a][3] = dhz_f32x2{q1.z, q1.w};
         if (Q8) {
             const float fr = a == 0 ? fr0 : a == 3 ? fr3 : 1.f;
             d[a][0] *= fr * fc0; d[a][3] *= fr * fc3;
@@ -187,11 +178,11 @@ __global__ __launch_bounds__(512) void winograd_conv3x3_kernel(const float* __re
         }
     };
     auto col_transform = [&](int b) {                    // B^T d, column b
-        const f32x2 d0 = d[0][b], d1 = d[1][b], d2 = d[2][b], d3 = d[3][b];
+        const dhz_f32x2 d0 = d[0][b], d1 = d[1][b], d2 = d[2][b], d3 = d[3][b];
         d[0][b] = d0 - d2; d[1][b] = d1 + d2; d[2][b] = d2 - d1; d[3][b] = d1 - d3;
     };
     auto row_transform = [&](int a) {                    // (B^T d) B, row a
-        const f32x2 t0 = d[a][0], t1 = d[a][1], t2 = d[a][2], t3 = d[a][3];
+        const dhz_f32x2 t0 = d[a][0], t1 = d[a][1], t2 = d[a][2], t3 = d[a][3];
         d[a][0] = t0 - t2; d[a][1] = t1 + t2; d[a][2] = t2 - t1; d[a][3] = t1 - t3;
     };
     float* vdst = vw + g * 32 + i16 * 2;
@@ -211,12 +202,12 @@ __global__ __launch_bounds__(512) void winograd_conv3x3_kernel(const float* __re
     // ---- prologue: group 0 transformed and in V, filters 0 in ring slot 0, loads of group 1 in flight
     gload_patch(0);
     gload_u(0);
-    wave_sync();                                         // zero fill before the patch stores
+    dhz_wave_sync();                                         // zero fill before the patch stores
 #pragma unroll
     for (int i = 0; i < NP4; ++i) write_patch_slot(i);
     write_u(0);
     { const int c1 = NG > 1 ? 1 : 0; gload_patch(c1); gload_u(c1); }
-    wave_sync();
+    dhz_wave_sync();
 #pragma unroll
     for (int a = 0; a < 4; ++a) read_row(a);
 #pragma unroll
@@ -237,7 +228,7 @@ __global__ __launch_bounds__(512) void winograd_conv3x3_kernel(const float* __re
         auto slot = [&](int sidx) {
             if (!WITH_NEXT) return;
             if ((WINO_ABL & 1) && sidx >= 13 && sidx <= 21) return;
-            if ((WINO_ABL & 2) && (sidx == 1 || sidx == 6)) { if (sidx == 6) wave_sync(); return; }
+            if ((WINO_ABL & 2) && (sidx == 1 || sidx == 6)) { if (sidx == 6) dhz_wave_sync(); return; }
             if ((WINO_ABL & 8) && (sidx == 0 || (sidx >= 2 && sidx <= 5) || (sidx >= 8 && sidx <= 11) || sidx >= 22)) return;
             switch (sidx) {
                 case 0: write_u(nbuf); break;                                  // loaded during the previous group
@@ -246,7 +237,7 @@ __global__ __launch_bounds__(512) void winograd_conv3x3_kernel(const float* __re
                 case 3: write_patch_slot(1); break;
                 case 4: write_patch_slot(2); break;
                 case 5: write_patch_slot(3); break;
-                case 6: wave_sync(); gload_patch(cb2); break;
+                case 6: dhz_wave_sync(); gload_patch(cb2); break;
                 case 8: read_row(0); break;
                 case 9: read_row(1); break;
                 case 10: read_row(2); break;
@@ -314,9 +305,9 @@ __global__ __launch_bounds__(512) void winograd_conv3x3_kernel(const float* __re
             __builtin_amdgcn_sched_barrier(0);
             a0 = a0n; a1 = a1n; b0 = b0n; b1 = b1n;
         }
-        wave_sync();                                     // every MFMA of this group has read V
+        dhz_wave_sync();                                     // every MFMA of this group has read V
         if (WITH_NEXT && !(WINO_ABL & 8)) { write_v2(12); write_v2(14); }
-        wave_sync();
+        dhz_wave_sync();
     };
     for (int cb = 0; cb + 1 < NG; ++cb) group(cb, std::true_type{});
     group(NG - 1, std::false_type{});
@@ -353,7 +344,7 @@ __global__ __launch_bounds__(512) void winograd_conv3x3_kernel(const float* __re
                 *reinterpret_cast<float2*>(o + 16) = make_float2(y10, y11);
             }
     }
-    wave_sync();
+    dhz_wave_sync();
     if (live) {
         const int KG = K / 8;
         if (RAW) y += (size_t)sl * nimg * K * H * W;     // part sl of the workspace
