@@ -335,6 +335,18 @@ int dhz_bf16_transpose_batched(const float* src, void* dst, const int* desc, int
  *     dw / db HOST arrays of nmat device pointers; ACCUMULATED; db exact fp32 column sums).  T % 64 == 0, nper % 64 == 0, K % 64 == 0. */
 int dhz_linear_wgrad_split(const float* dy, int ldy, const float* x, int ldx, int T, int nmat, int nper, int K, float* const* dw,
                            float* const* db, const float* row_scale, int rows_per_scale, int terms, void* stream);
+/*     The whole backward of such a Linear from ONE pass over dy (csrc/linear_bwd_pair.hip; fp32 storage, six-term products): replaces
+ *         dhz_linear_fwd_split6(dy, ldy, planes of W^T, NULL, dx, K, T, K, N)          dx [T, K] = dy . W       (written in full)
+ *         dhz_linear_wgrad_split(dy, ldy, x, ldx, T, nmat, nper, K, dw, db, NULL, 0, 6)  dw[m] += ..., db[m] += ...  (fp32 atomics)
+ *     where dy [T, N = nmat * nper] is the wide tensor: dy and x are read and cut into bf16 pieces once.  wt_hi / mid / lo: the three
+ *     planes of W^T ([K][N] row-major, W = the nmat matrices stacked; what dhz_split3_planes_t maintains).  dw / db: HOST arrays of nmat
+ *     device pointers, db or any db[m] may be NULL.  Instances N x K = 128 x 32, 256 x 64, 192 x 64; T % 32 == 0; ldy, ldx multiples
+ *     of 4; dy, x, the planes and dx 16-byte aligned; dx contiguous.  DHZ_EINVAL in deterministic mode (callers run the pair above).
+ *     dhz_linear_bwd_pair_grid: the persistent grid of that launch under the current dhz_set_reserved_cus (each workgroup walks a
+ *     contiguous slab of the T / 32 stages); 0 for a shape the entry refuses.  Host-side only. */
+int dhz_linear_bwd_pair(const float* dy, int ldy, const float* x, int ldx, const void* wt_hi, const void* wt_mid, const void* wt_lo,
+                        float* dx, int T, int nmat, int nper, int K, float* const* dw, float* const* db, void* stream);
+int dhz_linear_bwd_pair_grid(int T, int N, int K);
 
 /* bf16 forms of the three token-Linear GEMMs (BASELINE config 4: bf16 activations and bf16 weight copies, fp32 accumulation on
  *     v_mfma_f32_16x16x32_bf16; biases and all parameter gradients stay fp32).  Same contracts as dhz_linear_fwd / _dgrad /

@@ -97,6 +97,8 @@ SIGNATURES = {
     "dhz_linear_fwd_split": [c_f, c_i, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_p],
     "dhz_linear_dgrad_split": [c_f, c_i, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_p],
     "dhz_linear_wgrad_split": [c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_i, c_i, c_p],
+    "dhz_linear_bwd_pair": [c_f, c_i, c_f, c_i, c_p, c_p, c_p, c_f, c_i, c_i, c_i, c_i, c_f, c_f, c_p],
+    "dhz_linear_bwd_pair_grid": [c_i, c_i, c_i],
     "dhz_linear_fwd_split6": [c_f, c_i, c_p, c_p, c_p, c_f, c_f, c_i, c_i, c_i, c_i, c_p],
     "dhz_linear_dgrad_split6": [c_f, c_i, c_p, c_p, c_p, c_f, c_i, c_i, c_i, c_i, c_p],
     "dhz_linear_fwd_split6_res": [c_f, c_i, c_p, c_p, c_p, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p],

@@ -3,7 +3,8 @@
 attention branch : out = x + drop_scale * OutProj(ProbAttn(QKV(partition(roll(LN(x))))))           (M1:839-872)
     forward  : ONE kernel (dhz_fused_window_attn_fwd) where it wins, else dhz_ln_partition_fwd -> QKV GEMM -> dhz_ps_attn_fwd ->
                out-projection GEMM whose EPILOGUE is window reverse + un-roll + DropPath factor + residual (ops.gemm_fwd_res)
-    backward : out-proj dgrad + wgrad -> dhz_ps_attn_bwd (+ bias table gradient) -> QKV dgrad + wgrad -> dhz_ln_partition_bwd with
+    backward : out-proj dgrad + wgrad -> dhz_ps_attn_bwd (+ bias table gradient) -> QKV dgrad + wgrad (ONE kernel over d(qkv) at C = 64,
+               ops.linear_bwd_pair; so is linear1's backward of the LeFF / Mlp branch at C = 32 / 64) -> dhz_ln_partition_bwd with
                the shortcut gradient folded in (dx = dout + dLN) - no autograd-side accumulation kernels at all
 LeFF / Mlp branch: out = x + drop_scale * linear2(gelu(dwconv(gelu(linear1(LN(x))))))                (M1:873)
 whole block      : block() runs both branches as ONE node, so that the gradient between them can live in the layout its consumer
@@ -402,8 +403,8 @@ def _attn_bwd(rec, dout, windowed=False, daw_pre=None):
     ops.ps_attn_bwd_launch(qkv, dqkv, bias, mask, rank, dctx, dpart, B_, H, d)
     dtable = _table_backward(dpart, parts, table_p, H, dev) if bias is not None else None
     # (4) QKV projection
-    dxn = ops.gemm_dgrad(dqkv, ops.cat_rows([wq_.detach(), wk_.detach(), wv_.detach()]))
-    g_wq, g_bq, g_wk, g_bk, g_wv, g_bv = ops.linear_wgrad(dqkv, 0, xn, [(wq, bq), (wk, bk), (wv, bv)])      # one launch, x read once
+    dxn, (g_wq, g_bq, g_wk, g_bk, g_wv, g_bv) = ops.linear_bwd_pair(dqkv, xn, ops.cat_rows([wq_.detach(), wk_.detach(), wv_.detach()]),
+                                                                    [(wq, bq), (wk, bk), (wv, bv)])          # x read once
     # (5) LayerNorm backward + shortcut gradient in one pass
     dx, dgamma, dbeta = _ln_backward(dxn, x, gamma_p, beta_p, gamma, stats, dout, B, Hres, Wres, C, shift, 1, dres_windowed=windowed)
     return (dx, dgamma, dbeta, g_wq, g_bq, g_wk, g_bk, g_wv, g_bv, g_wo, g_bo, dtable)
@@ -568,8 +569,7 @@ def _leff_bwd(rec, dout, dx_window=None, dx2=None):
         dwb = torch.zeros((Ch * 10,), **f32)
         dwconv_bwd(dwb.data_ptr(), dwb.data_ptr() + 4 * Ch * 9)
         g_wd, g_bd = dwb[:Ch * 9].view(Ch, 1, 3, 3), dwb[Ch * 9:]
-    dxn = ops.gemm_dgrad(du, w1_)
-    g_w1, g_b1 = _wgrad(du, 0, xn, w1, b1)
+    dxn, (g_w1, g_b1) = ops.linear_bwd_pair(du, xn, w1_, [(w1, b1)])
     if dx2 is not None:       # dx in token order AND a scaled window-ordered copy (block(), bf16 storage): dx = (dx, copy)
         dx, dgamma, dbeta = _ln_backward(dxn, x, gamma_p, beta_p, gamma, stats, dout, B, Hres, Wres, C, 0, 0, dx2=dx2)
     elif dx_window is None:
@@ -646,8 +646,7 @@ class _FfnBranch(Function):
         du = torch.empty_like(u)
         _lib.call("dhz_gelu_bwd_dt", _p(dz), _p(u), _p(du), u.numel(), _p(dscale) if fold else None, L * Ch if fold else 0, ops._dt(u),
                   _stream())
-        dxn = ops.gemm_dgrad(du, w1_)
-        g_w1, g_b1 = _wgrad(du, 0, xn, w1, b1)
+        dxn, (g_w1, g_b1) = ops.linear_bwd_pair(du, xn, w1_, [(w1, b1)])
         dx, dgamma, dbeta = _ln_backward(dxn, x, gamma_p, beta_p, gamma, stats, dout, B, L, 1, C, 0, 0)
         return (dx, dgamma, dbeta, g_w1, g_b1, g_w2, g_b2, None, None)
 

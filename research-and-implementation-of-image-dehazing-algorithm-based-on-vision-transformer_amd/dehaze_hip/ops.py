@@ -852,6 +852,54 @@ def linear_wgrad(dy, off, x, params, row_scale=None):
     return tuple(slots)
 
 
+# dx, dW and db of a Linear from ONE pass over dy (csrc/linear_bwd_pair.hip) where dy is the wide tensor of its block: LeFF linear1 and the
+# packed Q / K / V projection at C = 32 / 64.  DHZ_LINEAR_BWD_PAIR=0: the two launches everywhere.  A shape (N, K) is listed only when the
+# kernel beats gemm_dgrad + linear_wgrad by more than the spread between rounds on every map size it occurs at; a built shape that does
+# not stays tested and undispatched.  Measured (tools/bench_linear_bwd_pair.py, bs 32, us, two launches -> one kernel; spreads 0.4 - 9.6;
+# profiles/r09_linear_bwd_pair.txt): (128, 32) at 128 x 128 139 -> 104; (256, 64) at 64 x 64 82.3 -> 77.8, at 128 x 128 296 -> 216;
+# (192, 64) at 64 x 64 67.6 -> 60.6, at 128 x 128 253 -> 169.  The config-2 step: -0.29 ms slowest on against fastest off, -0.46 ms by the means.
+LINEAR_BWD_PAIR = os.environ.get("DHZ_LINEAR_BWD_PAIR", "1") != "0"
+LINEAR_BWD_PAIR_BUILT = ((128, 32), (256, 64), (192, 64))
+LINEAR_BWD_PAIR_SHAPES = ((128, 32), (256, 64), (192, 64))
+
+
+def _bwd_pair_operands(dy, x, W, params):
+    """(planes of W^T, [(dW, db or None)]) when dhz_linear_bwd_pair takes this backward, else None"""
+    T, K = x.shape
+    N = W.shape[0]
+    if not LINEAR_BWD_PAIR or (N, K) not in LINEAR_BWD_PAIR_SHAPES or DETERMINISTIC or SPLIT_BF16 != 6 or T % 32:
+        return None
+    if dy.dtype != torch.float32 or x.dtype != torch.float32 or dy.stride(1) != 1 or x.stride(1) != 1 or dy.stride(0) % 4 or x.stride(0) % 4:
+        return None
+    if _p(dy) % 16 or _p(x) % 16 or len({w.shape[0] for w, _ in params}) != 1 or sum(w.shape[0] for w, _ in params) != N:
+        return None
+    if any(not w.requires_grad or (b is not None and not b.requires_grad) for w, b in params):
+        return None
+    planes = split_planes_t(W)
+    if planes is None or any(_p(pl) % 16 for pl in planes):
+        return None
+    pairs = [_grad_pair(w, b) for w, b in params]
+    return (planes, pairs) if all(pr is not None for pr in pairs) else None
+
+
+def linear_bwd_pair(dy, x, W, params):
+    """Backward of the Linears [(W_i, b_i or None)] of equal width whose outputs are the column blocks of dy [T, N] and whose common input
+    is x [T, K]; W [N, K] = their weights stacked (cat_rows).  Returns (dx [T, K], the autograd slots of linear_wgrad): one kernel when
+    everything it needs holds - fp32 storage, six-term arithmetic, not deterministic, W^T planes registered and aligned, every gradient
+    accumulated in place, the shape listed and the switch on - else exactly gemm_dgrad + linear_wgrad."""
+    W = W if W.is_contiguous() else W.contiguous()
+    took = _bwd_pair_operands(dy, x, W, params)
+    if took is None:
+        return gemm_dgrad(dy, W), linear_wgrad(dy, 0, x, params)
+    planes, pairs = took
+    T, K = x.shape
+    dx = torch.empty((T, K), device=dy.device, dtype=dy.dtype)
+    _lib.call("dhz_linear_bwd_pair", _p(dy), dy.stride(0), _p(x), x.stride(0), *[_p(pl) for pl in planes], _p(dx), T, len(params),
+              params[0][0].shape[0], K, _ptr_array([_p(gw) for gw, _ in pairs]), _ptr_array([_p(gb) for _, gb in pairs]), _stream())
+    _ready(*[p for wb in params for p in wb])
+    return dx, (None,) * (2 * len(params))
+
+
 def cat_rows(ts):
     """torch.cat(ts, 0) for detached row blocks - WITHOUT a copy when they already sit back to back in memory, which is how
     FlatAdamW lays out the Q / K / V weights (and biases) of an attention layer in its flat parameter buffer.  Only for use
