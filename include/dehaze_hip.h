@@ -456,7 +456,7 @@ int dhz_linear_wgrad_multi(const float* dy, int ldy, const float* x, int ldx, in
  *        at the OUTPUT positions - the ReLU of the layer below, fused into the store - and out_addend (shape of y, may
  *        be NULL) the gradient reaching that activation from a loss tap.
  *        H % 16 == 0 and W % 16 == 0, or H == W == 8 (the conv5_1 geometry of 128 x 128 patches: four images share one
- *        16 x 16 block of the kernel); C % 8 == 0, K % 32 == 0.
+ *        16 x 16 block of the kernel); C % 8 == 0, K % 32 == 0.  Every other map size: dhz_winograd_conv3x3_any (K11d).
  *      dhz_maxpool2x2_blocked_fwd / _bwd: the 2x2/stride-2 max pooling between VGG stages in the same layout
  *        (N = B*C/8 planes of [H][W][8]); the backward routes gy to the first maximum of each window of the saved
  *        post-ReLU map `act` and applies that map's ReLU (act > 0) in the same pass. */
@@ -498,6 +498,26 @@ int dhz_winograd43_conv3x3_slices(const float* x, const float* upack, const floa
                                   const float* out_addend, float* y, float* workspace, int slices, int B, int H, int W, int C, int K,
                                   void* stream);
 int dhz_winograd_slices(int B, int H, int W, int C, int K);
+/* K11d The F(2x2,3x3) convolution on maps of ANY size (H, W >= 1; C % 8 == 0, K % 32 == 0): what lets the feature stack run patches whose
+ *      maps are no multiples of 16 (64, 192, 240, 384 pixels ...).  Same filters (dhz_winograd_prepack), same epilogues, same error codes as
+ *      dhz_winograd_conv3x3.  How the kernel's 16 x 16 blocks lie on the maps:
+ *        4 x 4                      sixteen images per block (4 x 4 arrangement; a partly filled last block stores only its own images)
+ *        8 x 8                      four images per block   - the launch of dhz_winograd_conv3x3, bit for bit
+ *        H % 16 == 0, W % 16 == 0   whole blocks            - the launch of dhz_winograd_conv3x3, bit for bit
+ *        everything else            ceil(H / 16) x ceil(W / 16) ragged blocks per image: pixels outside the map are zero padding on the way in
+ *                                   and are neither stored nor read (out_mask / out_addend) on the way out.
+ *      dhz_winograd_conv3x3_any_slices: dhz_winograd_conv3x3_slices on the same shapes (slices == 1 is dhz_winograd_conv3x3_any bit for bit).
+ *      dhz_winograd_slices_any: the rule of dhz_winograd_slices (same constants) on the block count of the launch above; 1 for a shape the
+ *        entry refuses.  dhz_winograd_any_blocks: that block count - ceil(B / 16) at 4 x 4, ceil(B / 4) at 8 x 8, B ceil(H / 16) ceil(W / 16)
+ *        otherwise; <= 0 on bad arguments.  Both host-side only.
+ *      The LeakyReLU entry (K11a) and the F(4x4,3x3) kernel (K11b) keep their contracts. */
+int dhz_winograd_conv3x3_any(const float* x, const float* upack, const float* bias, int relu, const float* out_mask,
+                             const float* out_addend, float* y, int B, int H, int W, int C, int K, void* stream);
+int dhz_winograd_conv3x3_any_slices(const float* x, const float* upack, const float* bias, int relu, const float* out_mask,
+                                    const float* out_addend, float* y, float* workspace, int slices, int B, int H, int W, int C, int K,
+                                    void* stream);
+int dhz_winograd_slices_any(int B, int H, int W, int C, int K);
+int dhz_winograd_any_blocks(int B, int H, int W);
 int dhz_maxpool2x2_blocked_fwd(const float* x, float* y, int N, int H, int W, void* stream);
 int dhz_maxpool2x2_blocked_bwd(const float* gy, const float* act, float* gx, int N, int H, int W, void* stream);
 int dhz_layout_blocked8(const float* src, float* dst, int B, int C, int HW, int to_blocked, const float* bias, int relu,

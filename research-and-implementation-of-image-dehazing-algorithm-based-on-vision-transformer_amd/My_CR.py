@@ -81,14 +81,22 @@ class Vgg19(nn.Module):
         self.feature_dtype = torch.float32
 
     def engine_for(self, X):
-        """The MFMA feature engine (dehaze_hip/vgg.py) when it applies: frozen filters, an fp32 image on the GPU, maps that stay
-        multiples of 16 down to relu4_4 (H, W multiples of 128); None -> library convolutions.  `feature_dtype` selects the
-        Winograd fp32 engine (default) or, for BASELINE config 4, the implicit-GEMM engine with bf16 feature maps - what
-        torch.autocast makes of these convolutions in the reference."""
+        """The MFMA feature engine (dehaze_hip/vgg.py) when it applies: frozen filters, an fp32 image on the GPU whose sides are
+        multiples of 16 and at least 64 (vgg.engine_shape_ok: the Winograd kernels take maps of any size; smaller images stay
+        on the library); None -> library convolutions.  `feature_dtype` selects the Winograd fp32 engine (default) or, for
+        BASELINE config 4, the implicit-GEMM engine with bf16 feature maps - what torch.autocast makes of these convolutions
+        in the reference -, which keeps its own gate: H, W multiples of 128."""
         if not (self._frozen and X.is_cuda and X.dtype == torch.float32 and X.dim() == 4 and X.shape[1] == 3
-                and X.shape[2] % 128 == 0 and X.shape[3] % 128 == 0 and self.slice1[0].weight.device == X.device):
+                and self.slice1[0].weight.device == X.device):
             return None                      # (filters on another device: let the library path raise torch's own error)
         bf16 = self.feature_dtype == torch.bfloat16
+        if bf16:
+            if X.shape[2] % 128 or X.shape[3] % 128:
+                return None
+        else:
+            from dehaze_hip.vgg import engine_shape_ok
+            if not engine_shape_ok(X.shape[2], X.shape[3]):
+                return None
         if self._engine is None or self._engine[0] != bf16:
             from dehaze_hip.vgg import VggEngine, VggEngineBF16
             self._engine = (bf16, (VggEngineBF16 if bf16 else VggEngine)([m for m in self.modules() if isinstance(m, nn.Conv2d)]))

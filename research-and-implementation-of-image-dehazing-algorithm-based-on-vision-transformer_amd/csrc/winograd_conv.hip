@@ -54,9 +54,18 @@ constexpr size_t WINO_SMEM = (size_t)(NUBUF * UF + 8 * WAVE_LDS + KB) * sizeof(f
 // the saved post-ReLU activation at the OUTPUT positions, i.e. the ReLU of the layer below, `addend` the gradient that
 // reaches that activation from a loss tap) - so the hot loop is the same for both passes.
 //
-// Q8: 8 x 8 maps (the last VGG layer of the loss, conv5_1).  FOUR images form one virtual 16 x 16 block (2 x 2 arrangement): the
-// patch offsets carry the image of every pixel, the 4 x 4 input window of a tile is masked where it reaches into the
-// neighbouring image (that is where the tile's own image has its zero padding), and the stores scatter back per image.
+// MODE, how the 16 x 16 blocks lie on the maps:
+//   WM_PLAIN   H, W multiples of 16: whole blocks.
+//   WM_PACK8   8 x 8 maps (conv5_1 of 128-pixel patches).  FOUR images form one virtual 16 x 16 block (2 x 2 arrangement): the
+//              patch offsets carry the image of every pixel, the 4 x 4 input window of a tile is masked where it reaches into the
+//              neighbouring image (that is where the tile's own image has its zero padding), and the stores scatter back per image.
+//   WM_PACK4   4 x 4 maps (conv5_1 of 64-pixel patches): the same scheme with SIXTEEN images per block (4 x 4 arrangement); the image of
+//              pixel (iy, ix) of block blk is 16 blk + 4 (iy >> 2) + (ix >> 2).  Loads of images past the last one read the last one,
+//              their stores are skipped.
+//   WM_RAGGED  any H, W >= 1: ceil(H / 16) x ceil(W / 16) blocks per image.  The patch load zero-fills outside the map - which is the
+//              convolution's own padding, so a 2 x 2 output tile may lie half or wholly outside -, and the store skips pixels outside the
+//              map together with their out_mask / out_addend reads (behind the last image's plane there is no memory to read).
+// The MFMA loop is the same in all four.
 //
 // LEAKY (dhz_winograd_conv3x3_act, the UNet baseline's ConvBlock M1:28-40): LeakyReLU(0.01) instead of ReLU.  Forward
 // y = leaky(conv(x) + bias) [+ addend] (the block's conv11 branch joins in the store); backward y = (conv(x) + addend) * (mask > 0 ? 1 : 0.01).
@@ -67,7 +76,8 @@ constexpr size_t WINO_SMEM = (size_t)(NUBUF * UF + 8 * WAVE_LDS + KB) * sizeof(f
 // the plain store uses; winograd_slices_epilogue_kernel adds the parts.  For launches whose plain grid leaves CUs idle: what such a launch
 // costs is the serial walk of one workgroup over the channel groups.  The instances without it see slices = 1 as a constant: same code.
 constexpr float LEAKY_SLOPE = 0.01f;
-template <bool FWD, bool Q8, bool LEAKY = false, bool RAW = false>
+enum { WM_PLAIN = 0, WM_PACK8 = 1, WM_PACK4 = 2, WM_RAGGED = 3 };
+template <bool FWD, int MODE, bool LEAKY = false, bool RAW = false>
 __global__ __launch_bounds__(512) void winograd_conv3x3_kernel(const float* __restrict__ x,
                                                            const float* __restrict__ upack,
                                                            const float* __restrict__ bias, int relu,
@@ -75,6 +85,10 @@ __global__ __launch_bounds__(512) void winograd_conv3x3_kernel(const float* __re
                                                            const float* __restrict__ out_addend,
                                                            float* __restrict__ y, int H, int W, int C, int K, int nblk, int xcd_group,
                                                            int nimg, int slices) {
+    constexpr bool PK = MODE == WM_PACK8 || MODE == WM_PACK4, RG = MODE == WM_RAGGED;
+    constexpr int SH = MODE == WM_PACK4 ? 2 : 3, IS = 1 << SH, IM = IS - 1;      // packed: image side, its mask
+    constexpr int PER = 16 >> SH;                                                // images per block side
+    static_assert(!(LEAKY && (MODE == WM_PACK4 || RG)), "the LeakyReLU instances keep the plain / packed-8 contract");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, half = w >> 2, wl = w & 3;
     const int i16 = lane & 15, g = lane >> 4;
@@ -96,8 +110,8 @@ __global__ __launch_bounds__(512) void winograd_conv3x3_kernel(const float* __re
     int blk = (lid / KBn) * 2 + half;
     const bool live = blk < nblk;                       // odd block count: the last workgroup's second half recomputes, stores nothing
     if (!live) blk = nblk - 1;
-    const int bx_n = Q8 ? 1 : W / 16, by_n = Q8 ? 1 : H / 16;
-    const int bimg = Q8 ? 0 : blk / (bx_n * by_n);              // Q8: the image is a property of the pixel (below)
+    const int bx_n = PK ? 1 : RG ? (W + 15) / 16 : W / 16, by_n = PK ? 1 : RG ? (H + 15) / 16 : H / 16;
+    const int bimg = PK ? 0 : blk / (bx_n * by_n);              // packed: the image is a property of the pixel (below)
     const int by = (blk / bx_n) % by_n, bx = blk % bx_n;
     const int wy0 = by * 16 + 4 * wl, ox0 = bx * 16;        // the wave's output rows wy0..wy0+3; patch origin (wy0-1, ox0-1)
     const size_t plane = (size_t)H * W * 8;                 // floats per (image, channel-group) plane
@@ -119,10 +133,10 @@ __global__ __launch_bounds__(512) void winograd_conv3x3_kernel(const float* __re
         const int hf = e & 1, p = e >> 1;
         const int py = p / 18, px = p % 18;
         const int iy = wy0 - 1 + py, ix = ox0 - 1 + px;
-        const bool in = e < 6 * 18 * 2 && iy >= 0 && iy < (Q8 ? 16 : H) && ix >= 0 && ix < (Q8 ? 16 : W);
-        if (Q8) {
-            const int img = min(4 * blk + 2 * (iy >> 3) + (ix >> 3), nimg - 1);
-            poff[i] = in ? (unsigned)(img * (C / CC) * 512 + ((iy & 7) * 8 + (ix & 7)) * 8 + hf * 4) : 0u;
+        const bool in = e < 6 * 18 * 2 && iy >= 0 && iy < (PK ? 16 : H) && ix >= 0 && ix < (PK ? 16 : W);
+        if (PK) {
+            const int img = min(PER * PER * blk + PER * (iy >> SH) + (ix >> SH), nimg - 1);
+            poff[i] = in ? (unsigned)(img * (C / CC) * (IS * IS * 8) + ((iy & IM) * IS + (ix & IM)) * 8 + hf * 4) : 0u;
         } else
             poff[i] = in ? (unsigned)((iy * W + ix) * 8 + hf * 4) : 0u;
         pdst[i] = (2 * hf) * PPL + (in ? py * RS + px * 2 : 6 * RS + (lane & 15) * 2);
@@ -159,22 +173,34 @@ __global__ __launch_bounds__(512) void winograd_conv3x3_kernel(const float* __re
     // ---- input transform of the lane's (channel pair g, tile i16), both channels packed: d rows -> B^T d -> (B^T d) B
     dhz_f32x2 d[4][4];                                       // patch values, then B^T d, then the 16 V values (in place)
     const float* pread = pw + g * PPL + (2 * (i16 >> 3)) * RS + (i16 & 7) * 4;
-    // Q8: window row 0 / 3 (column 0 / 3) of a tile that starts / ends an 8-pixel image belongs to the neighbouring image
+    // packed: window row 0 / 3 (column 0 / 3) of a tile that starts / ends an 8- (4-) pixel image belongs to the neighbouring image
+    // (4-pixel images: every tile lies against its image's border above or below and left or right - two lane predicates instead of
+    // four factors, which this instance has no registers for)
+    const bool rlo = (i16 & 8) == 0, clo = (i16 & 1) == 0;       // WM_PACK4: window row 0 (else 3) / column 0 (else 3) is the neighbour's
     float fr0 = 1.f, fr3 = 1.f, fc0 = 1.f, fc3 = 1.f;
-    if (Q8) {
+    if (MODE == WM_PACK8) {
         const int r0 = 4 * wl + 2 * (i16 >> 3), c0 = 2 * (i16 & 7);
-        fr0 = (r0 & 7) == 0 ? 0.f : 1.f; fr3 = ((r0 + 2) & 7) == 0 ? 0.f : 1.f;
-        fc0 = (c0 & 7) == 0 ? 0.f : 1.f; fc3 = ((c0 + 2) & 7) == 0 ? 0.f : 1.f;
+        fr0 = (r0 & IM) == 0 ? 0.f : 1.f; fr3 = ((r0 + 2) & IM) == 0 ? 0.f : 1.f;
+        fc0 = (c0 & IM) == 0 ? 0.f : 1.f; fc3 = ((c0 + 2) & IM) == 0 ? 0.f : 1.f;
     }
     auto read_row = [&](int a) {
         const float4 q0 = *reinterpret_cast<const float4*>(pread + a * RS);       // px 0,1 x (c0,c1)
         const float4 q1 = *reinterpret_cast<const float4*>(pread + a * RS + 4);   // px 2,3
         d[a][0] = dhz_f32x2{q0.x, q0.y}; d[a][1] = dhz_f32x2{q0.z, q0.w};
         d[a][2] = dhz_f32x2{q1.x, q1.y}; d[a][3] = dhz_f32x2{q1.z, q1.w};
-        if (Q8) {
+        if (MODE == WM_PACK8) {
             const float fr = a == 0 ? fr0 : a == 3 ? fr3 : 1.f;
             d[a][0] *= fr * fc0; d[a][3] *= fr * fc3;
             if (a == 0 || a == 3) { d[a][1] *= fr; d[a][2] *= fr; }
+        }
+        if (MODE == WM_PACK4) {
+            const dhz_f32x2 z{0.f, 0.f};
+            if (a == 0 || a == 3) {
+                const bool out = a == 0 ? rlo : !rlo;
+#pragma unroll
+                for (int b = 0; b < 4; ++b) d[a][b] = out ? z : d[a][b];
+            }
+            d[a][0] = clo ? z : d[a][0]; d[a][3] = clo ? d[a][3] : z;
         }
     };
     auto col_transform = [&](int b) {                    // B^T d, column b
@@ -355,10 +381,12 @@ __global__ __launch_bounds__(512) void winograd_conv3x3_kernel(const float* __re
             const float* s0 = ys + (kg * 8 + hf * 4) * YS + py * 16 + px;
             float4 v4 = make_float4(s0[0], s0[YS], s0[2 * YS], s0[3 * YS]);
             size_t o;
-            if (Q8) {
-                const int vy = wy0 + py, img = 4 * blk + 2 * (vy >> 3) + (px >> 3);
+            if (PK) {
+                const int vy = wy0 + py, img = PER * PER * blk + PER * (vy >> SH) + (px >> SH);
                 if (img >= nimg) continue;
-                o = ((((size_t)img * KG + kb * 4 + kg) * 8 + (vy & 7)) * 8 + (px & 7)) * 8 + hf * 4;
+                o = ((((size_t)img * KG + kb * 4 + kg) * IS + (vy & IM)) * IS + (px & IM)) * 8 + hf * 4;
+            } else if (RG && (wy0 + py >= H || ox0 + px >= W)) {
+                continue;                                // outside the map: no store, no out_mask / out_addend read
             } else
                 o = (((size_t)bimg * KG + kb * 4 + kg) * H + wy0 + py) * W * 8 + (size_t)(ox0 + px) * 8 + hf * 4;
             if (!FWD || LEAKY) {
@@ -610,17 +638,34 @@ int dhz_wino_slices_epilogue(const char* who, const float* ws, int slices, const
 // eight-group slices are expected to gain little - the constant stays at what the table shows.
 constexpr int SLICE_MIN_GROUPS = 16;
 
-static int winograd_launch(const char* who, const float* x, const float* upack, const float* bias, int relu, const float* out_mask,
+// 16 x 16 blocks a launch walks: ceil(B / 16) at 4 x 4 (`any` only), ceil(B / 4) at 8 x 8, B ceil(H / 16) ceil(W / 16) otherwise
+static long long winograd_blocks(bool any, int B, int H, int W) {
+    if (any && H == 4 && W == 4) return ((long long)B + 15) / 16;
+    if (H == 8 && W == 8) return ((long long)B + 3) / 4;
+    return (long long)B * ((H + 15) / 16) * ((W + 15) / 16);
+}
+
+// any == false: the map-size contract of dhz_winograd_conv3x3 (multiples of 16, or 8 x 8).  any == true (the _any entries): every H, W >= 1 -
+// 4 x 4 packed sixteen to a block, 8 x 8 four to a block, multiples of 16 in whole blocks (those two are the launches of any == false, same
+// instances, same arguments), everything else in ragged blocks.
+static int winograd_launch(const char* who, bool any, const float* x, const float* upack, const float* bias, int relu, const float* out_mask,
                            const float* out_addend, float* y, float* ws, int slices, int B, int H, int W, int C, int K, void* stream) {
     DHZ_REQUIRE(x && upack && y, "%s: null pointer", who);
     const bool q8 = H == 8 && W == 8;                             // four 8 x 8 images per 16 x 16 block
-    DHZ_REQUIRE(B > 0 && ((H % 16 == 0 && W % 16 == 0) || q8) && C % CC == 0 && K % KB == 0,
+    const bool q4 = any && H == 4 && W == 4;                      // sixteen 4 x 4 images
+    const bool rg = any && !q8 && !q4 && (H % 16 != 0 || W % 16 != 0);
+    DHZ_REQUIRE(B > 0 && (any ? (H >= 1 && W >= 1 && C > 0 && K > 0) : ((H % 16 == 0 && W % 16 == 0) || q8)) && C % CC == 0 && K % KB == 0,
                 "%s: unsupported shape B=%d H=%d W=%d C=%d K=%d", who, B, H, W, C, K);
     const bool fwd = !(out_mask || out_addend);
     DHZ_REQUIRE(fwd || !(bias || relu), "%s: bias/relu and out_mask/out_addend are exclusive", who);
     DHZ_REQUIRE(slices >= 1 && slices <= C / CC && (slices == 1 || ws), "%s: slices=%d of %d channel groups, workspace %s", who, slices,
                 C / CC, ws ? "given" : "null");
-    const int nblk = q8 ? (B + 3) / 4 : B * (H / 16) * (W / 16);  // 16x16-pixel output blocks, two per workgroup
+    const long long nblk_ll = winograd_blocks(any, B, H, W);
+    // the kernel's patch offsets are 32-bit: inside one (image, channel group) plane, in the packed modes over the whole input
+    DHZ_REQUIRE(!any || (nblk_ll < (1ll << 30) && (nblk_ll + 1) / 2 * (K / KB) < (1ll << 31) && (long long)H * W * 8 < (1ll << 31) &&
+                         (!(q4 || q8) || (long long)B * C * H * W < (1ll << 31))),
+                "%s: unsupported shape B=%d H=%d W=%d C=%d K=%d", who, B, H, W, C, K);
+    const int nblk = (int)nblk_ll;                                // 16x16-pixel output blocks, two per workgroup
     const int grid = ((nblk + 1) / 2) * (K / KB);
     hipStream_t s = (hipStream_t)stream;
 #ifdef DHZ_DIAG
@@ -632,28 +677,30 @@ static int winograd_launch(const char* who, const float* x, const float* upack, 
     // measured (FETCH_SIZE, batch 64): 2-4x fewer HBM reads on the K <= 256 layers (reads ~= the input once), no change
     // at K = 512, never slower
     const int xcd_group = (grid % 8 == 0) && (xcd_env >= 0 ? xcd_env : 1);
-#define GO(F, Q)                                                                                                   \
+#define GO(F, M)                                                                                                   \
     do {                                                                                                           \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&winograd_conv3x3_kernel<F, Q>),                   \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&winograd_conv3x3_kernel<F, M>),                   \
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)WINO_SMEM);                     \
-        hipLaunchKernelGGL((winograd_conv3x3_kernel<F, Q>), dim3(grid), dim3(512), WINO_SMEM, s, x, upack, bias, relu, \
+        hipLaunchKernelGGL((winograd_conv3x3_kernel<F, M>), dim3(grid), dim3(512), WINO_SMEM, s, x, upack, bias, relu, \
                            out_mask, out_addend, y, H, W, C, K, nblk, xcd_group, B, 1);                            \
     } while (0)
-#define GO_RAW(Q)                                                                                                  \
+#define GO_RAW(M)                                                                                                  \
     do {                                                                                                           \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&winograd_conv3x3_kernel<false, Q, false, true>),  \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&winograd_conv3x3_kernel<false, M, false, true>),  \
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)WINO_SMEM);                     \
-        hipLaunchKernelGGL((winograd_conv3x3_kernel<false, Q, false, true>), dim3(grid * slices), dim3(512), WINO_SMEM, s, x, upack, \
+        hipLaunchKernelGGL((winograd_conv3x3_kernel<false, M, false, true>), dim3(grid * slices), dim3(512), WINO_SMEM, s, x, upack, \
                            nullptr, 0, nullptr, nullptr, ws, H, W, C, K, nblk, xcd_group, B, slices);              \
     } while (0)
     if (slices > 1) {
         DHZ_REQUIRE((long long)grid * slices < (1ll << 31), "%s: grid too large", who);
-        if (q8) GO_RAW(true); else GO_RAW(false);
+        if (q4) GO_RAW(WM_PACK4); else if (q8) GO_RAW(WM_PACK8); else if (rg) GO_RAW(WM_RAGGED); else GO_RAW(WM_PLAIN);
         DHZ_CHECK_LAUNCH(who);
         return dhz_wino_slices_epilogue(who, ws, slices, bias, relu, out_mask, out_addend, y, B, H, W, K, s);
     }
-    if (q8) { if (fwd) GO(true, true); else GO(false, true); }
-    else { if (fwd) GO(true, false); else GO(false, false); }
+    if (q4) { if (fwd) GO(true, WM_PACK4); else GO(false, WM_PACK4); }
+    else if (q8) { if (fwd) GO(true, WM_PACK8); else GO(false, WM_PACK8); }
+    else if (rg) { if (fwd) GO(true, WM_RAGGED); else GO(false, WM_RAGGED); }
+    else { if (fwd) GO(true, WM_PLAIN); else GO(false, WM_PLAIN); }
 #undef GO
 #undef GO_RAW
     DHZ_CHECK_LAUNCH(who);
@@ -662,7 +709,7 @@ static int winograd_launch(const char* who, const float* x, const float* upack, 
 
 extern "C" int dhz_winograd_conv3x3(const float* x, const float* upack, const float* bias, int relu, const float* out_mask,
                                     const float* out_addend, float* y, int B, int H, int W, int C, int K, void* stream) {
-    return winograd_launch("dhz_winograd_conv3x3", x, upack, bias, relu, out_mask, out_addend, y, nullptr, 1, B, H, W, C, K, stream);
+    return winograd_launch("dhz_winograd_conv3x3", false, x, upack, bias, relu, out_mask, out_addend, y, nullptr, 1, B, H, W, C, K, stream);
 }
 
 // The same convolution with the input-channel contraction cut into `slices` ranges of channel groups that run side by side (slices x the
@@ -670,19 +717,46 @@ extern "C" int dhz_winograd_conv3x3(const float* x, const float* upack, const fl
 extern "C" int dhz_winograd_conv3x3_slices(const float* x, const float* upack, const float* bias, int relu, const float* out_mask,
                                            const float* out_addend, float* y, float* workspace, int slices, int B, int H, int W, int C,
                                            int K, void* stream) {
-    return winograd_launch("dhz_winograd_conv3x3_slices", x, upack, bias, relu, out_mask, out_addend, y, workspace, slices, B, H, W, C, K,
-                           stream);
+    return winograd_launch("dhz_winograd_conv3x3_slices", false, x, upack, bias, relu, out_mask, out_addend, y, workspace, slices, B, H, W,
+                           C, K, stream);
 }
 
-extern "C" int dhz_winograd_slices(int B, int H, int W, int C, int K) {
-    const bool q8 = H == 8 && W == 8;
-    if (B <= 0 || !((H % 16 == 0 && W % 16 == 0 && H > 0 && W > 0) || q8) || C <= 0 || K <= 0 || C % CC || K % KB) return 1;
-    const long long nblk = q8 ? (B + 3) / 4 : (long long)B * (H / 16) * (W / 16);
+// The two entries above on maps of any size (see winograd_launch)
+extern "C" int dhz_winograd_conv3x3_any(const float* x, const float* upack, const float* bias, int relu, const float* out_mask,
+                                        const float* out_addend, float* y, int B, int H, int W, int C, int K, void* stream) {
+    return winograd_launch("dhz_winograd_conv3x3_any", true, x, upack, bias, relu, out_mask, out_addend, y, nullptr, 1, B, H, W, C, K, stream);
+}
+
+extern "C" int dhz_winograd_conv3x3_any_slices(const float* x, const float* upack, const float* bias, int relu, const float* out_mask,
+                                               const float* out_addend, float* y, float* workspace, int slices, int B, int H, int W, int C,
+                                               int K, void* stream) {
+    return winograd_launch("dhz_winograd_conv3x3_any_slices", true, x, upack, bias, relu, out_mask, out_addend, y, workspace, slices, B, H,
+                           W, C, K, stream);
+}
+
+extern "C" int dhz_winograd_any_blocks(int B, int H, int W) {
+    if (B <= 0 || H < 1 || W < 1) return 0;
+    const long long nblk = winograd_blocks(true, B, H, W);
+    return nblk < (1ll << 30) ? (int)nblk : 0;
+}
+
+static int winograd_slices_rule(long long nblk, int C, int K) {
     const long long grid = ((nblk + 1) / 2) * (K / KB);
     const int cus = dhz_grid_cus() + dhz_get_reserved_cus();
     for (int S = 4; S > 1; S >>= 1)
         if (S * grid <= cus && (C / CC) / S >= SLICE_MIN_GROUPS) return S;
     return 1;
+}
+
+extern "C" int dhz_winograd_slices(int B, int H, int W, int C, int K) {
+    const bool q8 = H == 8 && W == 8;
+    if (B <= 0 || !((H % 16 == 0 && W % 16 == 0 && H > 0 && W > 0) || q8) || C <= 0 || K <= 0 || C % CC || K % KB) return 1;
+    return winograd_slices_rule(winograd_blocks(false, B, H, W), C, K);
+}
+
+extern "C" int dhz_winograd_slices_any(int B, int H, int W, int C, int K) {
+    if (B <= 0 || H < 1 || W < 1 || C <= 0 || K <= 0 || C % CC || K % KB) return 1;
+    return winograd_slices_rule(winograd_blocks(true, B, H, W), C, K);
 }
 
 // LeakyReLU(0.01) in the store.  backward != 0: y = (conv(x, W') + out_addend) * (out_mask > 0 ? 1 : 0.01) with out_mask the saved
@@ -699,15 +773,15 @@ extern "C" int dhz_winograd_conv3x3_act(const float* x, const float* upack, cons
     const int grid = ((nblk + 1) / 2) * (K / KB);
     hipStream_t s = (hipStream_t)stream;
     const int xcd_group = grid % 8 == 0;
-#define GO(F, Q)                                                                                                         \
+#define GO(F, M)                                                                                                         \
     do {                                                                                                                 \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&winograd_conv3x3_kernel<F, Q, true>),                   \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&winograd_conv3x3_kernel<F, M, true>),                   \
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)WINO_SMEM);                           \
-        hipLaunchKernelGGL((winograd_conv3x3_kernel<F, Q, true>), dim3(grid), dim3(512), WINO_SMEM, s, x, upack, bias, 0, \
+        hipLaunchKernelGGL((winograd_conv3x3_kernel<F, M, true>), dim3(grid), dim3(512), WINO_SMEM, s, x, upack, bias, 0, \
                            out_mask, out_addend, y, H, W, C, K, nblk, xcd_group, B, 1);                                  \
     } while (0)
-    if (q8) { if (!backward) GO(true, true); else GO(false, true); }
-    else { if (!backward) GO(true, false); else GO(false, false); }
+    if (q8) { if (!backward) GO(true, WM_PACK8); else GO(false, WM_PACK8); }
+    else { if (!backward) GO(true, WM_PLAIN); else GO(false, WM_PLAIN); }
 #undef GO
     DHZ_CHECK_LAUNCH("dhz_winograd_conv3x3_act");
     return DHZ_OK;

@@ -68,6 +68,11 @@ SIGNATURES = {
     "dhz_winograd_conv3x3_slices": [c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_p],
     "dhz_winograd43_conv3x3_slices": [c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_p],
     "dhz_winograd_slices": [c_i, c_i, c_i, c_i, c_i],
+    # the F(2x2) convolution on maps of any size (ragged blocks; sixteen 4 x 4 images per block)
+    "dhz_winograd_conv3x3_any": [c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_p],
+    "dhz_winograd_conv3x3_any_slices": [c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_p],
+    "dhz_winograd_slices_any": [c_i, c_i, c_i, c_i, c_i],
+    "dhz_winograd_any_blocks": [c_i, c_i, c_i],
     "dhz_maxpool2x2_blocked_fwd": [c_f, c_f, c_i, c_i, c_i, c_p],
     "dhz_maxpool2x2_blocked_bwd": [c_f, c_f, c_f, c_i, c_i, c_i, c_p],
     "dhz_layout_blocked8": [c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_i, c_p],

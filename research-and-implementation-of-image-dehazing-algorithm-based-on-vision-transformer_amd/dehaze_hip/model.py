@@ -516,11 +516,20 @@ class Downsample(nn.Module):
         if s_ * s_ == x.shape[1] and ops.conv4s2_supported(x, s_, s_, need_grad) and self.out_channel % 32 == 0:
             # implicit GEMM on the fp32 matrix pipe straight from / to the token layout (csrc/conv_gemm.hip)
             return ops.conv4s2_tokens(x, conv.weight, conv.bias, s_, s_)
+        ho = s_ // 2
+        if (need_grad and s_ * s_ == x.shape[1] and self.out_channel % 32 == 0 and ops.conv4s2_supported(x, s_, s_, False)
+                and ho > 0 and (ho & (ho - 1)) == 0):
+            # only the batch is in the way: the weight-gradient kernel takes output pixels in 32s (an odd batch onto the 4 x 4 map of 64-pixel
+            # patches).  Zero images up to the next batch that fits - they add nothing to dW and db, autograd drops their rows - instead of the
+            # library convolution, whose algorithm for this shape is not reproducible from run to run (MIOpen's tuning records decide it,
+            # torch.backends.cudnn.deterministic or not), so that a deterministic step stays one at any batch
+            m = 32 // math.gcd(32, ho * ho)
+            pad = -x.shape[0] % m
+            return ops.conv4s2_tokens(F.pad(x, (0, 0, 0, 0, 0, pad)), conv.weight, conv.bias, s_, s_)[:x.shape[0]]
         if (s_ * s_ == x.shape[1] and x.dtype == torch.bfloat16 and ops.conv4s2_bf16_supported(x, s_, s_)
                 and self.out_channel % 64 == 0):
             # config 4: patch matrix + the bf16-MFMA token-Linear GEMMs (csrc/conv_bf16.hip), fp32 master weights
             return ops.conv4s2_tokens(x, conv.weight, conv.bias, s_, s_)
-        ho = s_ // 2
         if (s_ * s_ == x.shape[1] and x.is_cuda and x.dtype == torch.float32 and self.in_channel % 32 == 16 and self.out_channel % 32 == 0
                 and s_ % 2 == 0 and (not need_grad or ((ho & (ho - 1)) == 0 and (x.shape[0] * ho * ho) % 32 == 0))):
             # 16 (mod 32) input channels (the embed_dim = 16 model's first down-sampling): the implicit-GEMM kernels tile the contraction in

@@ -3,9 +3,10 @@
 PyTorch is plumbing here: it owns device memory (caching allocator), the current HIP stream and the
 autograd tape; the ops below run hand-written gfx950 kernels through ctypes (the token-Linear GEMMs included:
 dhz_linear_fwd / dhz_linear_dgrad / dhz_linear_wgrad).  No vendor compute kernel is left in the fp32 or the bf16 training
-step; the library is reached only for shapes the kernels do not tile (e.g. the last VGG layer on 24 x 24 maps of 384 x 384
-patches, Downsample / projections of unusual channel counts - DESIGN.md section 2).  CPU tensors are rejected - there is no
-fallback path.
+step; the library is reached only for shapes the kernels do not tile (e.g. the VGG19 stack of the contrastive loss on images
+smaller than 64 pixels or with sides that are no multiples of 16 - every larger such patch, 64 / 192 / 240 / 384 pixels
+included, runs the Winograd kernels on maps of any size -, Downsample / projections of unusual channel counts - DESIGN.md
+section 2).  CPU tensors are rejected - there is no fallback path.
 """
 import collections
 import ctypes

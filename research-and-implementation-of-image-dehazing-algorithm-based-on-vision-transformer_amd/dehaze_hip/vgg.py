@@ -3,8 +3,10 @@
 conv 0 (3 -> 64) runs thin-input kernels (dhz_conv3x3_in3_blocked forward with bias + ReLU straight into the blocked layout,
 dhz_thin_conv3x3_dgrad_blocked backward-data straight from it); convs 1..12 run dhz_winograd_conv3x3 with bias + ReLU fused,
 in the channel-blocked NCHW8c layout end to end (conv 12 works on 8x8 maps for 128x128 patches: the kernel then packs four
-images into one of its 16x16 blocks; for patch sizes whose conv-12 maps it does not tile, e.g. 24x24 at 384x384, that one layer
-falls back to the library).  The filters are frozen
+images into one of its 16x16 blocks).  Maps that are neither multiples of 16 nor 8x8 - the 8x8 / 4x4 maps of 64-pixel patches, 24x24 and
+12x12 at 192, 30x30 and 15x15 at 240, 24x24 at 384 - run dhz_winograd_conv3x3_any: the same kernel with ragged blocks at the right and
+bottom edges, and sixteen 4x4 images per block.  Every patch whose sides are multiples of 16 and at least 64 pixels (engine_shape_ok)
+therefore runs the whole stack on these kernels; no layer goes to the library.  The filters are frozen
 (My_CR.py:75-77), so their transform-domain forms (forward and backward-data) are prepacked once per device.
 
 Launches whose grid leaves CUs idle (the 8 x 8 maps; the 16 x 16 maps of the 32 differentiated images) run with their input-channel
@@ -18,7 +20,6 @@ load) - weight gradients are never formed (the reference freezes the VGG, My_CR.
 import os
 
 import torch
-import torch.nn.functional as F
 from torch.autograd import Function
 
 from . import _lib
@@ -31,9 +32,27 @@ POOL_AFTER = (1, 3, 7, 11)
 TAPS = (0, 2, 4, 8, 12)          # relu1_1, relu2_1, relu3_1, relu4_1, relu5_1
 
 
-def wino_supported(H, W):
-    """map sizes dhz_winograd_conv3x3 tiles: multiples of 16, or 8x8 (four images per block)"""
+def engine_shape_ok(H, W):
+    """Image sizes the fp32 engine takes: both sides multiples of 16 (four even poolings, then conv5_1 on H / 16 x W / 16 maps of any size)
+    and at least 64.  Below 64 the last maps are 2 x 2 and 1 x 1, and the 32-pixel model test holds the contrastive loss's gradient to a
+    bound that the library's arithmetic meets and the Winograd transform's does not: those sizes stay on the library."""
+    return H % 16 == 0 and W % 16 == 0 and H >= 64 and W >= 64
+
+
+def _fixed_tiling(H, W):
+    """map sizes dhz_winograd_conv3x3 takes (multiples of 16, or 8x8: four images per block); every other size runs dhz_winograd_conv3x3_any"""
     return (H % 16 == 0 and W % 16 == 0) or (H == 8 and W == 8)
+
+
+def any_blocks(B, H, W):
+    """dhz_winograd_any_blocks, restated for the host tests: the 16 x 16 blocks a dhz_winograd_conv3x3_any launch walks (0: bad arguments)"""
+    if B <= 0 or H < 1 or W < 1:
+        return 0
+    if H == 4 and W == 4:
+        return (B + 15) // 16
+    if H == 8 and W == 8:
+        return (B + 3) // 4
+    return B * ((H + 15) // 16) * ((W + 15) // 16)
 
 
 def to_blocked(x, bias=None, relu=False):
@@ -149,6 +168,17 @@ def wino_slices_rule(B, H, W, C, K, cus):
     return 1
 
 
+def wino_slices_any_rule(B, H, W, C, K, cus):
+    """The rule of dhz_winograd_slices_any, restated for the host tests: wino_slices_rule on the block count of the any-size launch."""
+    if B <= 0 or H < 1 or W < 1 or C <= 0 or K <= 0 or C % 8 or K % 32:
+        return 1
+    grid = (any_blocks(B, H, W) + 1) // 2 * (K // 32)
+    for S in (4, 2):
+        if S * grid <= cus and (C // 8) // S >= SLICE_MIN_GROUPS:
+            return S
+    return 1
+
+
 class VggEngine:
     def __init__(self, convs):
         """convs: the 13 nn.Conv2d modules of vgg19.features[0:30]."""
@@ -193,7 +223,8 @@ class VggEngine:
         C, K = CONVS[i]
         f43 = allow43 and use_f43(B, H, W, C, K)
         s43 = use_f43_slices(B, H, W, C, K) if (allow43 and not f43) else 0
-        s22 = _lib.load().dhz_winograd_slices(B, H, W, C, K) if (SLICES_ON and not f43 and not s43) else 1
+        sfx = "" if _fixed_tiling(H, W) else "_any"             # (F(4x4) never applies to the `_any` shapes: use_f43 wants multiples of 16)
+        s22 = getattr(_lib.load(), "dhz_winograd_slices" + sfx)(B, H, W, C, K) if (SLICES_ON and not f43 and not s43) else 1
         uf, _ = self.packed43(i, xb.device) if (f43 or s43) else self.packed(i, xb.device)
         if pool and f43:
             yp = torch.empty((B, K // 8, H // 2, W // 2, 8), device=xb.device, dtype=torch.float32)
@@ -207,10 +238,10 @@ class VggEngine:
         ev = ops._timed("dhz_winograd_conv3x3")
         if s43 or s22 > 1:
             ws = torch.empty((s43 or s22, B, K // 8, H, W, 8), device=xb.device, dtype=torch.float32)
-            _lib.call("dhz_winograd43_conv3x3_slices" if s43 else "dhz_winograd_conv3x3_slices", _p(xb), _p(uf), _p(self.convs[i].bias), 1,
+            _lib.call("dhz_winograd43_conv3x3_slices" if s43 else f"dhz_winograd_conv3x3{sfx}_slices", _p(xb), _p(uf), _p(self.convs[i].bias), 1,
                       None, None, _p(yb), _p(ws), s43 or s22, B, H, W, C, K, _stream())
         else:
-            _lib.call("dhz_winograd43_conv3x3" if f43 else "dhz_winograd_conv3x3", _p(xb), _p(uf), _p(self.convs[i].bias), 1, None, None,
+            _lib.call("dhz_winograd43_conv3x3" if f43 else "dhz_winograd_conv3x3" + sfx, _p(xb), _p(uf), _p(self.convs[i].bias), 1, None, None,
                       _p(yb), B, H, W, C, K, _stream())
         _timing_end(ev, B, H, W, C, K, f43 or bool(s43))
         return pool_fwd(yb) if pool else yb
@@ -223,7 +254,8 @@ class VggEngine:
         C, K = CONVS[i]
         f43 = use_f43(B, H, W, K, C)                       # the backward-data form: K input channels, C outputs
         s43 = 0 if f43 else use_f43_slices(B, H, W, K, C)
-        s22 = _lib.load().dhz_winograd_slices(B, H, W, K, C) if (SLICES_ON and not f43 and not s43) else 1
+        sfx = "" if _fixed_tiling(H, W) else "_any"
+        s22 = getattr(_lib.load(), "dhz_winograd_slices" + sfx)(B, H, W, K, C) if (SLICES_ON and not f43 and not s43) else 1
         _, ub = self.packed43(i, gb.device) if (f43 or s43) else self.packed(i, gb.device)
         dxb = torch.empty((B, C // 8, H, W, 8), device=gb.device, dtype=torch.float32)
         mask = _p(below_act) if below_act is not None else None
@@ -231,18 +263,17 @@ class VggEngine:
         ev = ops._timed("dhz_winograd_conv3x3")
         if s43 or s22 > 1:
             ws = torch.empty((s43 or s22, B, C // 8, H, W, 8), device=gb.device, dtype=torch.float32)
-            _lib.call("dhz_winograd43_conv3x3_slices" if s43 else "dhz_winograd_conv3x3_slices", _p(gb), _p(ub), None, 0, mask,
+            _lib.call("dhz_winograd43_conv3x3_slices" if s43 else f"dhz_winograd_conv3x3{sfx}_slices", _p(gb), _p(ub), None, 0, mask,
                       _p(add) if add is not None else None, _p(dxb), _p(ws), s43 or s22, B, H, W, K, C, _stream())
         else:
-            _lib.call("dhz_winograd43_conv3x3" if f43 else "dhz_winograd_conv3x3", _p(gb), _p(ub), None, 0, mask,
+            _lib.call("dhz_winograd43_conv3x3" if f43 else "dhz_winograd_conv3x3" + sfx, _p(gb), _p(ub), None, 0, mask,
                       _p(add) if add is not None else None, _p(dxb), B, H, W, K, C, _stream())
         _timing_end(ev, B, H, W, K, C, f43 or bool(s43))
         return dxb
 
     # ---- full stack, forward only
     def forward_taps(self, x, save=None):
-        """x: [B,3,H,W] NCHW.  Returns the 5 tap features, blocked [B,C/8,H,W,8] (tap 5 NCHW when conv 12 ran on the library).
-        `save` (dict) receives what the backward needs."""
+        """x: [B,3,H,W] NCHW.  Returns the 5 tap features, blocked [B,C/8,H,W,8].  `save` (dict) receives what the backward needs."""
         c0 = self.convs[0]
         # first layer (3 -> 64): thin on the input side - convolution + bias + ReLU straight into the blocked layout
         xc = x.contiguous()
@@ -251,28 +282,20 @@ class VggEngine:
                   xc.shape[3], 64, 1, _stream())
         acts = {0: cur}
         taps = [cur]
-        x12 = None
         for i in range(1, 13):
-            if i == 12 and not wino_supported(cur.shape[2], cur.shape[3]):
-                # conv 12 on maps the kernel does not tile (e.g. 24x24 for 384x384 patches): library convolution, NCHW tap
-                c12 = self.convs[12]
-                ops.warn_library_fallback("VGG19 conv5_1", tuple(cur.shape))
-                x12 = to_plain(cur)
-                cur = F.relu(F.conv2d(x12, c12.weight, c12.bias, padding=1))
-            else:
-                # F(4x4,3x3) carries ~3 x the rounding error of F(2x2,3x3) (1.1 - 2.1e-6 rms on O(1) features against 3.7 - 6.7e-7): harmless for
-                # feature VALUES and backward-data products; for the differentiated pass see F43_DIFF above (measured, on by default)
-                if POOL_FUSED and save is None and i in POOL_AFTER and i not in TAPS:
-                    cur = self.conv(i, cur, pool=True)          # no-gradient pass, the un-pooled map has no other reader
-                    continue
-                cur = self.conv(i, cur, allow43=(save is None or F43_DIFF))
+            # F(4x4,3x3) carries ~3 x the rounding error of F(2x2,3x3) (1.1 - 2.1e-6 rms on O(1) features against 3.7 - 6.7e-7): harmless for
+            # feature VALUES and backward-data products; for the differentiated pass see F43_DIFF above (measured, on by default)
+            if POOL_FUSED and save is None and i in POOL_AFTER and i not in TAPS:
+                cur = self.conv(i, cur, pool=True)          # no-gradient pass, the un-pooled map has no other reader
+                continue
+            cur = self.conv(i, cur, allow43=(save is None or F43_DIFF))
             acts[i] = cur
             if i in TAPS:
                 taps.append(cur)
             if i in POOL_AFTER:
                 cur = pool_fwd(cur)
         if save is not None:
-            save.update(x=x, acts=acts, x12=x12)
+            save.update(x=x, acts=acts)
         return taps
 
 
@@ -296,14 +319,7 @@ class _VggTaps(Function):
         with torch.no_grad():
             # G = gradient w.r.t. the PRE-activation of conv i (None while nothing has arrived from above)
             G = g5 * (acts[12] > 0) if g5 is not None else None
-            top = 12
-            if sv["x12"] is not None:                                        # conv 12 ran on the library (see forward_taps)
-                top = 11
-                if G is not None:
-                    gx12 = torch.ops.aten.convolution_backward(G, sv["x12"], eng.convs[12].weight, None, [1, 1], [1, 1], [1, 1],
-                                                               False, [0, 0], 1, [True, False, False])[0]
-                    G = pool_bwd_relu(to_blocked(gx12), acts[11])
-            for i in range(top, 0, -1):
+            for i in range(12, 0, -1):
                 below = i - 1                                                # conv i's input is a_{i-1} (pooled if i-1 in POOL_AFTER)
                 tg = tap_grad.get(below)
                 if G is None:
@@ -478,8 +494,8 @@ class _ToPlain(Function):
 
 
 def to_plain_tap(t):
-    """tap feature -> NCHW (differentiable); tap 5 already is."""
-    return _ToPlain.apply(t) if t.dim() == 5 else t
+    """tap feature -> NCHW (differentiable)"""
+    return _ToPlain.apply(t)
 
 
 def _sfx(t):
