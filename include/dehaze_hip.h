@@ -590,6 +590,19 @@ int dhz_thin_conv3x3_dgrad_blocked(const float* gb, const float* w, float* dx, i
 int dhz_l1_pair_fwd(const float* a, const float* p, const float* n, float* sums, int64_t count, void* stream);
 int dhz_l1_pair_bwd(const float* a, const float* p, const float* n, const float* g, float* da, int64_t count, void* stream);
 
+/* K11d the squared error of one feature tap of FFA-Net's perceptual loss (FFA_model/models/PerceptualLoss.py:24-31: F.mse_loss of the
+ *      VGG16 features at relu1_2 / relu2_2 / relu3_3), csrc/perceptual.hip:
+ *      dhz_mse_pair_fwd: sum[0] += sum (a - g)^2 (the caller zeroes, the kernel accumulates; deterministic mode: workspace slots and
+ *        dhz_det_reduce, no atomic).  dhz_mse_pair_bwd: da = gmean[0] (2 / count) (a - g) with gmean the device-resident gradient of the
+ *        MEAN; relu_mask != 0: da = 0 where a <= 0 (a is a post-ReLU map: the gradient below that ReLU).
+ *        count > 0, count % 4 == 0, a / g / da 16-byte aligned (DHZ_EINVAL otherwise); any (common) element order; fp32 only.
+ *      dhz_maxpool2x2_blocked_bwd_add: dhz_maxpool2x2_blocked_bwd for a post-ReLU map `act` that is a loss tap as well:
+ *        gx = act > 0 ? (gy routed to the first maximum of each window) + addend : 0, addend [N][H][W][8] the tap's own gradient. */
+int dhz_mse_pair_fwd(const float* a, const float* g, float* sum, int64_t count, void* stream);
+int dhz_mse_pair_bwd(const float* a, const float* g, const float* gmean, float* da, int64_t count, int relu_mask, void* stream);
+int dhz_maxpool2x2_blocked_bwd_add(const float* gy, const float* act, const float* addend, float* gx, int N, int H, int W,
+                                   void* stream);
+
 /* K10b the same feature stack for BASELINE config 4 (bf16 feature maps in NHWC / token layout [N, H, W, C]; what torch.autocast
  *      makes of My_CR.py:65-72's convolutions), csrc/vgg_bf16.hip:
  *      dhz_vgg_prepack_bf16: filter w[K, C, 3, 3] fp32 -> bf16 [K][9 C] tap-major (transpose = 0) or the backward-data filter

@@ -1,0 +1,193 @@
+"""FFA-Net trained under its OWN recipe (FFA_model/main.py, options of FFA_model/option.py) on the HIP kernels - the recipe the reference
+trains its FFA baseline with, as opposed to My_train.py --arch FFA, which trains the same network under Uformer's
+(Charbonnier + VGG19 contrastive loss + AdamW + epoch-wise warm-up / cosine):
+
+  * loss = L1(out, y) [+ 0.04 * PerLoss(out, y) with --perloss: VGG16 relu1_2 / relu2_2 / relu3_3 MSE, PerceptualLoss.py], out unclamped
+  * Adam, lr 1e-4, betas (0.9, 0.999), eps 1e-8 - FlatAdamW with weight_decay 0 is that update, in one launch
+  * per-step cosine decay lr = 0.5 (1 + cos(t pi / T)) lr0 (--no_lr_sche: constant)
+  * every --eval_step steps: PSNR / SSIM over the validation pairs (utils/metrics.py, on the host), a checkpoint
+    `<model_dir><name>_<step>_psnr: <p>_ssim: <s>.pk` with the reference's keys (step, max_psnr, max_ssim, ssims, psnrs, losses, model),
+    and `<model_dir><name>_best.pk` when both metrics improve.  `model` keys carry DataParallel's `module.` prefix like the reference's;
+    utils.load_checkpoint reads either form, so `test_long_GPU.py --arch FFA --weights x.pk` evaluates such a file.
+  * --resume [file]: continue from `file`, or without a value from `<model_dir><name>_best.pk` (the reference's rule: only if it exists)
+
+Differences from the reference's script: one process, no DataParallel; data in HBM like My_train.py (--synthetic N, --train_dir / --val_dir
+directories of PNG pairs through dataset.PatchStoreHBM and the crop / augment kernel, or `.pt` files); the loss values are fetched every
+--log_every steps instead of every step (no host sync inside the step); --deterministic.  The ITS / OTS loaders are not restated.
+"""
+import argparse
+import math
+import os
+import random
+import sys
+import time
+
+dir_name = os.path.dirname(os.path.abspath(__file__))
+if dir_name not in sys.path:
+    sys.path.insert(0, dir_name)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import utils  # noqa: E402
+from dehaze_hip.ffa import FFA  # noqa: E402
+from dehaze_hip.train import FlatAdamW, ffa_train_step, lr_schedule_cosdecay, synthetic_batch  # noqa: E402
+from PerceptualLoss import PerLoss  # noqa: E402
+from utils.metrics import peak_signal_noise_ratio, structural_similarity  # noqa: E402
+
+
+def parse(argv=None):
+    parser = argparse.ArgumentParser(description="FFA-Net, its own training recipe")
+    # FFA_model/option.py
+    parser.add_argument('--steps', type=int, default=100000)
+    parser.add_argument('--device', type=str, default='Automatic detection')
+    parser.add_argument('--resume', nargs='?', const=True, default=False, help='continue from this .pk (no value: <model_dir><name>_best.pk)')
+    parser.add_argument('--eval_step', type=int, default=5000)
+    parser.add_argument('--lr', default=0.0001, type=float, help='learning rate')
+    parser.add_argument('--model_dir', type=str, default='./FFA_pretrain_weight/')
+    parser.add_argument('--trainset', type=str, default='its_train')
+    parser.add_argument('--testset', type=str, default='its_test')
+    parser.add_argument('--net', type=str, default='ffa')
+    parser.add_argument('--gps', type=int, default=3, help='residual_groups')
+    parser.add_argument('--blocks', type=int, default=20, help='residual_blocks')
+    parser.add_argument('--bs', type=int, default=4, help='batch size')
+    parser.add_argument('--crop', action='store_true')
+    parser.add_argument('--crop_size', type=int, default=240, help='patch side of a training sample')
+    parser.add_argument('--no_lr_sche', action='store_true', help='no lr cos schedule')
+    parser.add_argument('--perloss', action='store_true', help='perceptual loss')
+    # this project's data options (My_train.py)
+    parser.add_argument('--train_dir', type=str, default='../datasets/NH_haze/train', help='<dir>/gt, <dir>/hazy PNG pairs, or a .pt file')
+    parser.add_argument('--val_dir', type=str, default='../datasets/NH_haze/val')
+    parser.add_argument('--synthetic', type=int, default=0, help='train on N synthetic pairs (HBM resident)')
+    parser.add_argument('--val_synthetic', type=int, default=8)
+    parser.add_argument('--deterministic', action='store_true',
+                        help='bit-reproducible steps: fixed-order reductions instead of fp32 atomics (slower)')
+    parser.add_argument('--log_every', type=int, default=10, help='host sync cadence for the progress line')
+    opt = parser.parse_args(argv)
+    opt.model_name = 'My_NH' + '_' + opt.net.split('.')[0] + '_' + str(opt.gps) + '_' + str(opt.blocks)
+    opt.model_path = opt.model_dir + opt.model_name          # option.py:38: a prefix, not a directory join
+    return opt
+
+
+def load_pairs(path, device):
+    blob = torch.load(path, map_location="cpu")
+    return blob["target"].float().to(device), blob["input"].float().to(device)
+
+
+def evaluate(net, vt, vi):
+    """mean (SSIM, PSNR) over the validation pairs, one image at a time (they may differ in size), metrics on the host"""
+    net.eval()
+    ssims, psnrs = [], []
+    with torch.no_grad():
+        for t, x in zip(vt, vi):
+            pred = torch.clamp(net(x.unsqueeze(0)), 0, 1)[0]
+            a = t.permute(1, 2, 0).cpu().numpy()
+            b = pred.permute(1, 2, 0).cpu().numpy()
+            psnrs.append(float(peak_signal_noise_ratio(a, b)))
+            ssims.append(float(structural_similarity(a, b, multichannel=True)))
+    net.train()
+    return float(np.mean(ssims)), float(np.mean(psnrs))
+
+
+def main(argv=None):
+    opt = parse(argv)
+    torch.backends.cudnn.benchmark = True
+    dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
+    torch.cuda.set_device(dev)
+    opt.device = str(dev)
+    if opt.deterministic:
+        from dehaze_hip import ops
+        ops.set_deterministic(True)
+    print(opt)
+    print('model_dir:', opt.model_path)
+    os.makedirs(os.path.dirname(os.path.abspath(opt.model_path)), exist_ok=True)
+
+    random.seed(1234)
+    np.random.seed(1234)
+    torch.manual_seed(1234)
+    torch.cuda.manual_seed_all(1234)
+
+    net = FFA(gps=opt.gps, blocks=opt.blocks)
+    optimizer = FlatAdamW(net, lr=opt.lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0)
+    net.to(dev)
+    perloss = None
+    if opt.perloss:
+        if not os.environ.get("DEHAZE_VGG16_WEIGHTS") and not opt.synthetic and not os.environ.get("DEHAZE_ALLOW_RANDOM_VGG"):
+            raise SystemExit("FFA_main: --perloss needs the ImageNet VGG16 checkpoint the reference downloads (main.py:187): set "
+                             "DEHAZE_VGG16_WEIGHTS=/path/to/vgg16-397923af.pth, or DEHAZE_ALLOW_RANDOM_VGG=1 to train against SEEDED "
+                             "RANDOM VGG features (not the reference's loss)")
+        perloss = PerLoss().to(dev)
+
+    losses, ssims, psnrs = [], [], []
+    start_step, max_ssim, max_psnr = 0, 0.0, 0.0
+    resume = opt.model_path + '_best.pk' if opt.resume is True else opt.resume
+    if resume and os.path.exists(resume):
+        print(f'resume from {resume}')
+        ckp = torch.load(resume, map_location="cpu")
+        utils.load_checkpoint(net, resume, map_location=dev)
+        losses, ssims, psnrs = list(ckp['losses']), list(ckp['ssims']), list(ckp['psnrs'])
+        start_step, max_ssim, max_psnr = int(ckp['step']), float(ckp['max_ssim']), float(ckp['max_psnr'])
+        print(f'start_step:{start_step} start training ---')
+    else:
+        print('train from scratch *** ')
+
+    # ---- data (HBM resident)
+    store = tgt_all = inp_all = None
+    if opt.synthetic > 0:
+        tgt_all, inp_all = synthetic_batch(opt.synthetic, opt.crop_size, seed=1234, device=dev)
+        vt, vi = synthetic_batch(opt.val_synthetic, opt.crop_size, seed=4321, device=dev)
+    elif os.path.isdir(opt.train_dir):
+        from dataset import DataLoaderVal, PatchStoreHBM
+        store = PatchStoreHBM.from_dir(opt.train_dir, dev)
+        val_set = DataLoaderVal(opt.val_dir)
+        items = [val_set[i] for i in range(len(val_set))]
+        vt, vi = [v[0].to(dev) for v in items], [v[1].to(dev) for v in items]
+    else:
+        tgt_all, inp_all = load_pairs(opt.train_dir, dev)
+        vt, vi = load_pairs(opt.val_dir, dev)
+    n_train = len(store) if store is not None else tgt_all.shape[0]
+
+    def state(step):
+        return {'step': step, 'max_psnr': max_psnr, 'max_ssim': max_ssim, 'ssims': ssims, 'psnrs': psnrs, 'losses': losses,
+                'model': {'module.' + k: v for k, v in net.state_dict().items()}}
+
+    net.train()
+    t0 = time.time()
+    pending = []                                   # device scalars of the steps since the last host sync
+    for step in range(start_step + 1, opt.steps + 1):
+        lr = opt.lr
+        if not opt.no_lr_sche:
+            lr = lr_schedule_cosdecay(step, opt.steps, opt.lr)
+            for g in optimizer.param_groups:
+                g["lr"] = lr
+        sel = torch.randint(n_train, (opt.bs,))          # main.py:84: a fresh shuffled batch every step
+        if store is not None:
+            y, x = store.batch(sel.tolist(), opt.crop_size)
+        else:
+            y, x = tgt_all[sel.to(dev)], inp_all[sel.to(dev)]
+        loss, _, _ = ffa_train_step(net, perloss, optimizer, None, x, y)
+        pending.append(loss)
+        if step % opt.log_every == 0 or step % opt.eval_step == 0 or step == opt.steps:
+            losses += torch.stack(pending).tolist()
+            pending = []
+            print(f'\rtrain loss : {losses[-1]:.5f}| step :{step}/{opt.steps}|lr :{lr :.7f} |time_used :{(time.time() - t0) / 60 :.1f}',
+                  end='', flush=True)
+        if step % opt.eval_step == 0:
+            ssim_eval, psnr_eval = evaluate(net, vt, vi)
+            print(f'\nstep :{step} |ssim:{ssim_eval:.4f}| psnr:{psnr_eval:.4f}')
+            ssims.append(ssim_eval)
+            psnrs.append(psnr_eval)
+            torch.save(state(step), opt.model_path + '_' + str(step) + '_psnr: ' + str(psnr_eval) + '_ssim: ' + str(ssim_eval) + '.pk')
+            if ssim_eval > max_ssim and psnr_eval > max_psnr:
+                max_ssim, max_psnr = max(max_ssim, ssim_eval), max(max_psnr, psnr_eval)
+                torch.save(state(step), opt.model_path + '_best' + '.pk')
+                print(f'   model saved at step :{step}| max_psnr:{max_psnr:.4f}|max_ssim:{max_ssim:.4f}')
+    if losses and not math.isfinite(losses[-1]):
+        raise SystemExit("FFA_main: the loss is not finite")
+    for name, vals in (('losses', losses), ('ssims', ssims), ('psnrs', psnrs)):
+        np.save(f'{opt.model_path}_{opt.steps}_{name}.npy', np.asarray(vals, dtype=np.float64))
+    print()
+
+
+if __name__ == "__main__":
+    main()

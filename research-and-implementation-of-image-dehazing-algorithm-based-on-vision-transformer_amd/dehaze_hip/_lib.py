@@ -184,6 +184,10 @@ SIGNATURES = {
     "dhz_ffa_gate_pa_bwd_b": [c_f] * 6 + [c_i, c_i, c_i, c_i, c_p],
     "dhz_ffa_add": [c_f, c_f, c_f, c_l, c_p],
     "dhz_ffa_relu_bwd_add": [c_f, c_f, c_f, c_f, c_f, c_l, c_p],
+    # squared-error taps of FFA-Net's perceptual loss, pooling backward of a map that is a tap too (csrc/perceptual.hip)
+    "dhz_mse_pair_fwd": [c_f, c_f, c_f, c_l, c_p],
+    "dhz_mse_pair_bwd": [c_f, c_f, c_f, c_f, c_l, c_i, c_p],
+    "dhz_maxpool2x2_blocked_bwd_add": [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_p],
 }
 _RESTYPE = {"dhz_last_error": ctypes.c_char_p, "dhz_build_id": ctypes.c_char_p, "dhz_conv3x3_wgrad_workspace_bytes": ctypes.c_size_t,
             "dhz_ffa_workspace_bytes": ctypes.c_size_t}

@@ -533,6 +533,43 @@ def train_step(model, char_loss, cr_loss, optimizer, reducer, input_, target, w_
     return loss.detach(), loss_rec.detach(), (loss_cr.detach() if loss_cr is not None else None)
 
 
+def lr_schedule_cosdecay(t, T, init_lr):
+    """FFA_model/main.py:52-54: the per-step cosine decay of FFA-Net's recipe"""
+    return 0.5 * (1 + math.cos(t * math.pi / T)) * init_lr
+
+
+def ffa_train_step(model, perloss, optimizer, reducer, input_, target, w_per=0.04):
+    """One step of FFA-Net's own recipe (FFA_model/main.py:84-96): out = model(x); loss = L1(out, y), unclamped, + w_per * perloss(out, y)
+    when `perloss` (PerceptualLoss.LossNetwork) is given; backward; Adam (FlatAdamW with weight_decay 0).  The L1 mean runs on
+    dhz_l1_pair_fwd / _bwd with n = NULL (vgg.l1_pair).  Returns (loss, loss_l1, loss_per) as device scalars - no host sync here."""
+    if getattr(model, "act_dtype", None) == torch.bfloat16 or input_.dtype != torch.float32 \
+            or any(p.dtype != torch.float32 for p in model.parameters()):
+        raise NotImplementedError("ffa_train_step: fp32 only (the squared-error taps and the VGG16 engine have no bf16 form)")
+    from .vgg import l1_pair
+    standalone = reducer is not None and reducer.opt is None
+    if standalone:
+        reducer.zero_grad()
+    else:
+        optimizer.zero_grad()
+    out = model(input_)
+    if out.numel() % 4 == 0 and out.is_cuda:
+        loss_l1 = l1_pair(out, target)[0]
+    else:
+        loss_l1 = torch.nn.functional.l1_loss(out, target)
+    loss = loss_l1
+    loss_per = None
+    if perloss is not None:
+        loss_per = perloss(out, target)
+        loss = loss + w_per * loss_per
+    loss.backward()
+    if reducer is not None:
+        reducer.wait()
+        if standalone:
+            reducer.average_()
+    optimizer.step()
+    return loss.detach(), loss_l1.detach(), (loss_per.detach() if loss_per is not None else None)
+
+
 def psnr(a, b):
     mse = torch.mean((a.double() - b.double()) ** 2).item()
     return 10.0 * math.log10(1.0 / max(mse, 1e-20))

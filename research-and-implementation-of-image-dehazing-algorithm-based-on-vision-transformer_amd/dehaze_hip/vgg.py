@@ -16,6 +16,11 @@ the parts and applies the store epilogue - see SLICES_ON below (DHZ_WINO_SLICES=
 Forward-only passes (target / hazy input, My_CR.py:102) save nothing; the pass on the restored image is one autograd
 node whose backward walks the stack with the same kernel (rotated/transposed filters, ReLU mask fused into the patch
 load) - weight gradients are never formed (the reference freezes the VGG, My_CR.py:75-77).
+
+The stack is a parameter of the engine: VggEngine(convs, pool_after, taps).  The defaults are VGG19[:30] with the five taps above; the
+perceptual loss of FFA-Net's recipe (dehaze_hip/perceptual.py) builds the 7 convolutions of VGG16[:16] with pool_after (1, 3) and taps
+(1, 3, 6).  There two taps are pooled as well: their un-pooled maps are always written, and in the backward the tap's gradient joins
+the pooled one on the un-pooled map in one launch (dhz_maxpool2x2_blocked_bwd_add, csrc/perceptual.hip).
 """
 import os
 
@@ -37,6 +42,12 @@ def engine_shape_ok(H, W):
     and at least 64.  Below 64 the last maps are 2 x 2 and 1 x 1, and the 32-pixel model test holds the contrastive loss's gradient to a
     bound that the library's arithmetic meets and the Winograd transform's does not: those sizes stay on the library."""
     return H % 16 == 0 and W % 16 == 0 and H >= 64 and W >= 64
+
+
+def engine16_shape_ok(H, W):
+    """Image sizes the VGG16[:16] stack of the perceptual loss takes (dehaze_hip/perceptual.py): two poolings only, so sides that are multiples
+    of 16 and at least 32 - the last maps are then 8 x 8 and larger (FFA's own blocked path asks for multiples of 16 too)."""
+    return H % 16 == 0 and W % 16 == 0 and H >= 32 and W >= 32
 
 
 def _fixed_tiling(H, W):
@@ -82,6 +93,14 @@ def pool_bwd_relu(gb, actb):
     B, CG, H, W, _ = actb.shape
     gx = torch.empty_like(actb)
     _lib.call("dhz_maxpool2x2_blocked_bwd", _p(gb.contiguous()), _p(actb), _p(gx), B * CG, H, W, _stream())
+    return gx
+
+
+def pool_bwd_relu_add(gb, actb, addb):
+    """pool_bwd_relu for a map that is a loss tap as well: + the tap's own gradient addb, both through the ReLU (actb > 0), in one launch."""
+    B, CG, H, W, _ = actb.shape
+    gx = torch.empty_like(actb)
+    _lib.call("dhz_maxpool2x2_blocked_bwd_add", _p(gb.contiguous()), _p(actb), _p(addb.contiguous()), _p(gx), B * CG, H, W, _stream())
     return gx
 
 
@@ -180,9 +199,18 @@ def wino_slices_any_rule(B, H, W, C, K, cus):
 
 
 class VggEngine:
-    def __init__(self, convs):
-        """convs: the 13 nn.Conv2d modules of vgg19.features[0:30]."""
-        self.convs = convs
+    def __init__(self, convs, pool_after=POOL_AFTER, taps=TAPS):
+        """convs: the nn.Conv2d modules of the stack - by default the 13 of vgg19.features[0:30]; pool_after: the convolutions a 2 x 2 max
+        pooling follows; taps: the convolutions whose post-ReLU maps are returned, the last tap being the last convolution.  The 7
+        convolutions of vgg16.features[0:16] with pool_after (1, 3) and taps (1, 3, 6) are the perceptual loss's stack (perceptual.py)."""
+        self.convs = list(convs)
+        self.conv_shapes = tuple((int(c.weight.shape[1]), int(c.weight.shape[0])) for c in self.convs)
+        self.pool_after = tuple(pool_after)
+        self.taps = tuple(taps)
+        if not self.taps or self.taps[-1] != len(self.convs) - 1 or list(self.taps) != sorted(set(self.taps)):
+            raise ValueError(f"VggEngine: taps {self.taps} must ascend and end at the last of the {len(self.convs)} convolutions")
+        if self.conv_shapes[0] != (3, 64) or any(c % 8 or k % 32 for c, k in self.conv_shapes[1:]):
+            raise ValueError(f"VggEngine: unsupported convolution shapes {self.conv_shapes}")
         self._packed = {}
         self._packed43 = {}
 
@@ -220,7 +248,7 @@ class VggEngine:
         """conv i + bias + ReLU; pool=True: + the 2 x 2 max pooling behind it, in the same launch when the layer runs the F(4x4) kernel (the
         un-pooled map is then never written: only for layers whose output is no tap and is not saved)."""
         B, CG, H, W, _ = xb.shape
-        C, K = CONVS[i]
+        C, K = self.conv_shapes[i]
         f43 = allow43 and use_f43(B, H, W, C, K)
         s43 = use_f43_slices(B, H, W, C, K) if (allow43 and not f43) else 0
         sfx = "" if _fixed_tiling(H, W) else "_any"             # (F(4x4) never applies to the `_any` shapes: use_f43 wants multiples of 16)
@@ -251,7 +279,7 @@ class VggEngine:
         `below_act` (the saved post-ReLU map that IS that input) the tap gradient `addend` is added and the ReLU below
         applied in the kernel's store, i.e. the result is the gradient w.r.t. the pre-activation of conv i-1."""
         B, KG, H, W, _ = gb.shape
-        C, K = CONVS[i]
+        C, K = self.conv_shapes[i]
         f43 = use_f43(B, H, W, K, C)                       # the backward-data form: K input channels, C outputs
         s43 = 0 if f43 else use_f43_slices(B, H, W, K, C)
         sfx = "" if _fixed_tiling(H, W) else "_any"
@@ -273,7 +301,7 @@ class VggEngine:
 
     # ---- full stack, forward only
     def forward_taps(self, x, save=None):
-        """x: [B,3,H,W] NCHW.  Returns the 5 tap features, blocked [B,C/8,H,W,8].  `save` (dict) receives what the backward needs."""
+        """x: [B,3,H,W] NCHW.  Returns the tap features, blocked [B,C/8,H,W,8].  `save` (dict) receives what the backward needs."""
         c0 = self.convs[0]
         # first layer (3 -> 64): thin on the input side - convolution + bias + ReLU straight into the blocked layout
         xc = x.contiguous()
@@ -281,22 +309,57 @@ class VggEngine:
         _lib.call("dhz_conv3x3_in3_blocked", _p(xc), _p(c0.weight.contiguous()), _p(c0.bias), _p(cur), xc.shape[0], xc.shape[2],
                   xc.shape[3], 64, 1, _stream())
         acts = {0: cur}
-        taps = [cur]
-        for i in range(1, 13):
+        taps = [cur] if 0 in self.taps else []
+        for i in range(1, len(self.convs)):
             # F(4x4,3x3) carries ~3 x the rounding error of F(2x2,3x3) (1.1 - 2.1e-6 rms on O(1) features against 3.7 - 6.7e-7): harmless for
             # feature VALUES and backward-data products; for the differentiated pass see F43_DIFF above (measured, on by default)
-            if POOL_FUSED and save is None and i in POOL_AFTER and i not in TAPS:
-                cur = self.conv(i, cur, pool=True)          # no-gradient pass, the un-pooled map has no other reader
+            if POOL_FUSED and save is None and i in self.pool_after and i not in self.taps:
+                cur = self.conv(i, cur, pool=True)          # no-gradient pass, the un-pooled map has no other reader (a tap has one: the loss)
                 continue
             cur = self.conv(i, cur, allow43=(save is None or F43_DIFF))
             acts[i] = cur
-            if i in TAPS:
+            if i in self.taps:
                 taps.append(cur)
-            if i in POOL_AFTER:
+            if i in self.pool_after:
                 cur = pool_fwd(cur)
         if save is not None:
             save.update(x=x, acts=acts)
         return taps
+
+    def backward_taps(self, saved, grads, last_masked=False):
+        """gradient w.r.t. the image from the gradients of the taps (None where a tap received none).  last_masked: the last tap's gradient
+        has passed that map's ReLU already (dhz_mse_pair_bwd with relu_mask)."""
+        acts = saved["acts"]
+        last = len(self.convs) - 1
+        tap_grad = dict(zip(self.taps[:-1], grads[:-1]))
+        g_last = grads[-1]
+        c0 = self.convs[0]
+        # G = gradient w.r.t. the PRE-activation of conv i (None while nothing has arrived from above)
+        G = None
+        if g_last is not None:
+            G = g_last if last_masked else g_last * (acts[last] > 0)
+        for i in range(last, 0, -1):
+            below = i - 1                                                # conv i's input is a_{i-1} (pooled if i-1 in pool_after)
+            tg = tap_grad.get(below)
+            if G is None:
+                if tg is not None:                                       # the first gradient enters at this tap
+                    G = tg * (acts[below] > 0)
+                continue
+            if below in self.pool_after:
+                if tg is not None:                                       # a tap that is pooled too: its gradient joins on the un-pooled map
+                    G = pool_bwd_relu_add(self.conv_dgrad(i, G), acts[below], tg)
+                else:
+                    G = pool_bwd_relu(self.conv_dgrad(i, G), acts[below])
+            else:
+                G = self.conv_dgrad(i, G, below_act=acts[below], addend=tg)
+        if G is None:
+            return None
+        # first layer (3 -> 64): its backward-data is a thin 64 -> 3 convolution - straight from the blocked gradient
+        x0 = saved["x"]
+        gx = torch.empty_like(x0, memory_format=torch.contiguous_format)
+        _lib.call("dhz_thin_conv3x3_dgrad_blocked", _p(G.contiguous()), _p(c0.weight.contiguous()), _p(gx), x0.shape[0],
+                  x0.shape[2], x0.shape[3], 64, _stream())
+        return gx
 
 
 class _VggTaps(Function):
@@ -311,32 +374,9 @@ class _VggTaps(Function):
         return tuple(taps)
 
     @staticmethod
-    def backward(ctx, g1, g2, g3, g4, g5):
-        eng, sv = ctx.engine, ctx.saved
-        acts = sv["acts"]
-        tap_grad = {0: g1, 2: g2, 4: g3, 8: g4}
-        c0 = eng.convs[0]
+    def backward(ctx, *grads):
         with torch.no_grad():
-            # G = gradient w.r.t. the PRE-activation of conv i (None while nothing has arrived from above)
-            G = g5 * (acts[12] > 0) if g5 is not None else None
-            for i in range(12, 0, -1):
-                below = i - 1                                                # conv i's input is a_{i-1} (pooled if i-1 in POOL_AFTER)
-                tg = tap_grad.get(below)
-                if G is None:
-                    if tg is not None:                                       # the first gradient enters at this tap
-                        G = tg * (acts[below] > 0)
-                    continue
-                if below in POOL_AFTER:
-                    G = pool_bwd_relu(eng.conv_dgrad(i, G), acts[below])
-                else:
-                    G = eng.conv_dgrad(i, G, below_act=acts[below], addend=tg)
-            if G is None:
-                return None, None
-            # first layer (3 -> 64): its backward-data is a thin 64 -> 3 convolution - straight from the blocked gradient
-            x0 = sv["x"]
-            gx = torch.empty_like(x0, memory_format=torch.contiguous_format)
-            _lib.call("dhz_thin_conv3x3_dgrad_blocked", _p(G.contiguous()), _p(c0.weight.contiguous()), _p(gx), x0.shape[0],
-                      x0.shape[2], x0.shape[3], 64, _stream())
+            gx = ctx.engine.backward_taps(ctx.saved, grads)
         ctx.saved = None
         return None, gx
 

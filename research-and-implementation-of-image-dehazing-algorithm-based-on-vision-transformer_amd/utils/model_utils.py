@@ -38,7 +38,9 @@ def _target(model):
 def load_checkpoint(model, weights, map_location=None):
     checkpoint = torch.load(weights, map_location=map_location)
     print('load weight path:' + weights)
-    _target(model).load_state_dict(_strip_module(checkpoint["state_dict"]))
+    # 'state_dict': My_train.py's checkpoints (TR:296); 'model': the .pk files of FFA-Net's own loop (FFA_model/main.py:122-130, FFA_main.py)
+    sd = checkpoint["state_dict"] if "state_dict" in checkpoint else checkpoint["model"]
+    _target(model).load_state_dict(_strip_module(sd))
 
 
 def load_checkpoint_CPU(model, weights):
