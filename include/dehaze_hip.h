@@ -563,6 +563,20 @@ size_t dhz_conv3x3_wgrad_workspace_bytes(int B, int H, int W, int Cin, int Kout)
 int dhz_conv3x3_wgrad_parts(int B, int H, int W, int Cin, int Kout);
 int dhz_conv3x3_wgrad(const float* x, const float* dy, float* dw, float* db, float* ws, size_t ws_bytes, int B, int H, int W, int Cin,
                       int Kout, void* stream);
+/*      The same on maps of ANY size (H, W >= 1; the channel constraints, the tensors, the workspace rules and the error codes are those
+ *      above): what lets FFA-Net's 64 -> 64 layers train and be scored on whole images.  How the 64-position chunks lie on the maps:
+ *        8 x 8                      one image per chunk        - the launch of dhz_conv3x3_wgrad, bit for bit
+ *        H % 16 == 0, W % 16 == 0   whole 4 x 16 chunks        - the launch of dhz_conv3x3_wgrad, bit for bit
+ *        everything else            ceil(H / 4) x ceil(W / 16) chunks per image, B ceil(H / 4) ceil(W / 16) in all (times 64 must fit an
+ *                                   int): dy positions outside the map are zeros in LDS and never loaded, like the x halo, so they add
+ *                                   zero to dw and db.
+ *      The slab rule is the one above - min(ceil(512 / tiles), chunks / 4), at least 1 - on that chunk count.
+ *      dhz_conv3x3_wgrad_workspace_bytes_any / dhz_conv3x3_wgrad_parts_any: the two queries for these shapes (equal to the queries above
+ *      wherever those answer; 0 for a shape this entry refuses). */
+size_t dhz_conv3x3_wgrad_workspace_bytes_any(int B, int H, int W, int Cin, int Kout);
+int dhz_conv3x3_wgrad_parts_any(int B, int H, int W, int Cin, int Kout);
+int dhz_conv3x3_wgrad_any(const float* x, const float* dy, float* dw, float* db, float* ws, size_t ws_bytes, int B, int H, int W, int Cin,
+                          int Kout, void* stream);
 
 /* K9b  output projection (My_model_1.py:696-723): Conv2d(C -> 3, 3x3, pad 1) from tokens x[B, H*W, C] to an NCHW image
  *      y[B, 3, H, W] (+ bias[3], may be NULL); backward-data dx[B, H*W, C] from dy[B, 3, H, W]; weight / bias gradient
@@ -787,7 +801,7 @@ int dhz_comm_destroy(void* comm);
  *      PALayer (FFA:9-21: 1x1 convolution 64 -> 8 -> relu_ -> 1x1 convolution 8 -> 1 -> sigmoid -> mul) and the `res += x` of a Block
  *      (FFA:54-56) with G = 1 map; the fusion head (FFA:105-108: aten::cat of the three group outputs -> mean -> the gate MLP -> three
  *      slices, three mul, two add -> PALayer) with G = 3 maps m0, m1, m2 (m1, m2 are ignored for G = 1; no concatenated tensor exists).
- *      Maps are [B][8][H][W][8]; H and W multiples of 16; 16-byte aligned pointers.
+ *      Maps are [B][8][H][W][8]; H and W multiples of 16 (any H, W: the `_any` entries below); 16-byte aligned pointers.
  *        mean[b][g 64 + c] = (1 / HW) sum_p m_g[b][c][p]
  *        hid = relu(Wa mean + ba)     Wa [hc][64 G], hc = 8 (G = 1, FFA:29) or 4 (G = 3, FFA:86)
  *        ca  = sigmoid(Wb hid + bb)   Wb [64 G][hc]
@@ -831,11 +845,40 @@ int dhz_ffa_ca_bwd(float* ws, size_t ws_bytes, const float* Wa, const float* Wb,
                    int H, int W, int G, void* stream);
 int dhz_ffa_gate_pa_bwd_b(const float* dt, const float* ca, const float* dmean, float* dm0, float* dm1, float* dm2, int B, int H, int W,
                           int G, void* stream);
+/*      The six entries on maps of ANY size (H, W >= 1; 64 H W < 2^31): FFA-Net on whole images, as FFA_model/test.py feeds it.  Formulas,
+ *      tensors, G, alignment and workspace rules, error codes: those above.  The kernels index a flat pixel p < HW; what the ragged
+ *      sizes change is the tails, each a function of the shapes alone:
+ *        pooling       chunks of 1024 pixels; the last chunk holds HW - 1024 (chunks - 1) pixels, of any count
+ *        gate forward  ceil(HW / 256) workgroups per image; threads whose pixel is >= HW do nothing
+ *        backward a    chunks = ceil(HW / 128) workgroups per image; in a partly filled last one the pixels >= HW are neither loaded
+ *                      nor stored and enter the slot's sums as zeros.  The workspace layout is the one above with this `chunks`: the
+ *                      level-1 sums at float offset B chunks (64 G + 532), as [B][ceil(chunks / 16)][64 G + 532]
+ *        backward b    one thread per float4 of dt, bounded by 16 B HW
+ *      On a shape the entries above take (H, W multiples of 16) each `_any` entry issues the same launches and writes the same bits, and
+ *      dhz_ffa_workspace_bytes_any equals dhz_ffa_workspace_bytes.  No atomics: the same bits from run to run, under any
+ *      dhz_set_reserved_cus, with the deterministic mode on or off. */
+size_t dhz_ffa_workspace_bytes_any(int B, int H, int W, int G);
+int dhz_ffa_ca_fwd_any(const float* m0, const float* m1, const float* m2, const float* Wa, const float* ba, const float* Wb,
+                       const float* bb, float* mean, float* hid, float* ca, float* ws, size_t ws_bytes, int B, int H, int W, int G,
+                       void* stream);
+int dhz_ffa_gate_pa_fwd_any(const float* m0, const float* m1, const float* m2, const float* ca, const float* Wp1, const float* bp1,
+                            const float* wp2, const float* bp2, const float* res, float* out, int B, int H, int W, int G, void* stream);
+int dhz_ffa_gate_pa_bwd_a_any(const float* m0, const float* m1, const float* m2, const float* ca, const float* Wp1, const float* bp1,
+                              const float* wp2, const float* bp2, const float* dout, float* dt, float* ws, size_t ws_bytes, int B, int H,
+                              int W, int G, void* stream);
+int dhz_ffa_ca_bwd_any(float* ws, size_t ws_bytes, const float* Wa, const float* Wb, const float* mean, const float* hid, const float* ca,
+                       float* dWa, float* dba, float* dWb, float* dbb, float* dmean, float* dWp1, float* dbp1, float* dwp2, float* dbp2,
+                       int B, int H, int W, int G, void* stream);
+int dhz_ffa_gate_pa_bwd_b_any(const float* dt, const float* ca, const float* dmean, float* dm0, float* dm1, float* dm2, int B, int H,
+                              int W, int G, void* stream);
 /*      The two elementwise passes of a Block (FFA:51-56) over n floats (n % 4 == 0, any common element order):
  *      dhz_ffa_add: y = a + x  (`res = res + x`, FFA:52: aten::add; also the group residual FFA:69 and the `+ x1` of FFA:110).
  *      dhz_ffa_relu_bwd_add: dpre1 = a1 > 0 ? dr : 0 (aten::threshold_backward of act1 by the sign of the saved activation a1) and
  *        s = dout + dr (the two gradients that reach the block input besides conv1's) in one pass. */
 int dhz_ffa_add(const float* a, const float* x, float* y, int64_t n, void* stream);
+/*      dhz_ffa_add_any: dhz_ffa_add for any n > 0 (the last n % 4 floats are added one by one; where n % 4 == 0, the same bits): the `+ x1` of
+ *        FFA:110 on an image whose 3 B H W is no multiple of 4. */
+int dhz_ffa_add_any(const float* a, const float* x, float* y, int64_t n, void* stream);
 int dhz_ffa_relu_bwd_add(const float* a1, const float* dr, const float* dout, float* dpre1, float* s, int64_t n, void* stream);
 
 #ifdef __cplusplus

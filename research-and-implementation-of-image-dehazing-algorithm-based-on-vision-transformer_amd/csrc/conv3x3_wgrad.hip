@@ -6,7 +6,9 @@
 //
 // Nine implicit GEMMs (one per tap) with a tiny result (Kout x Cin) and a contraction over every position B*H*W, so the contraction is
 // what gets split.  The cut:
-//   chunk  = 64 output positions: 4 rows x 16 columns of one image (H, W multiples of 16), or one whole 8 x 8 image;
+//   chunk  = 64 output positions: 4 rows x 16 columns of one image (H, W multiples of 16), or one whole 8 x 8 image; the `_any` entries
+//            take every other map too, as ceil(H / 4) x ceil(W / 16) chunks per image whose positions outside the map are zeros in LDS
+//            (never loaded), so that they add zero to dW and db;
 //   slab   = a run of consecutive chunks; `slabs` of them, min(ceil(512 / tiles), chunks / 4) - a function of the shapes alone;
 //   tile   = 32 output channels x 32 input channels (all nine taps);
 //   item   = (slab, tile): one workgroup accumulates the tile over the slab's chunks in fp32 on v_mfma_f32_16x16x4_f32 and STORES it to
@@ -32,19 +34,23 @@ constexpr int TARGET_ITEMS = 512;  // items aimed at: two workgroups per CU of a
 constexpr int WG_PER_CU = 4;
 constexpr int NTHR = 256;
 
+enum { MODE_M16 = 0, MODE_Q8 = 1, MODE_RAGGED = 2 };   // kernel instances: whole 4 x 16 chunks; one 8 x 8 image per chunk; 4 x 16 chunks cut by the map's edge
+
 struct Cut {
-    bool ok, q8;
+    bool ok;
+    int mode;
     int nchunks, tiles, slabs;
     long wlen, slot;               // floats of dW; floats of one workspace slot (dW + db)
 };
 
-Cut make_cut(int B, int H, int W, int Cin, int Kout) {
+// any: the `_any` entries (every H, W >= 1); otherwise multiples of 16, or 8 x 8
+Cut make_cut(int B, int H, int W, int Cin, int Kout, bool any) {
     Cut c{};
-    c.q8 = H == 8 && W == 8;
+    c.mode = H == 8 && W == 8 ? MODE_Q8 : (H >= 16 && W >= 16 && H % 16 == 0 && W % 16 == 0 ? MODE_M16 : MODE_RAGGED);
     c.ok = B >= 1 && Cin >= TKC && Kout >= TKC && Cin <= 512 && Kout <= 512 && Cin % TKC == 0 && Kout % TKC == 0 &&
-           (c.q8 || (H >= 16 && W >= 16 && H % 16 == 0 && W % 16 == 0));
+           (c.mode != MODE_RAGGED || (any && H >= 1 && W >= 1));
     if (!c.ok) return c;
-    const long nch = c.q8 ? (long)B : (long)B * (H / 4) * (W / 16);
+    const long nch = c.mode == MODE_Q8 ? (long)B : (long)B * ((H + 3) / 4) * ((W + 15) / 16);
     if (nch > INT_MAX / NPOS) { c.ok = false; return c; }         // B*H*W fits an int
     c.nchunks = (int)nch;
     c.tiles = (Kout / TKC) * (Cin / TKC);
@@ -56,10 +62,11 @@ Cut make_cut(int B, int H, int W, int Cin, int Kout) {
     return c;
 }
 
-template <bool Q8>
+template <int MODE>
 __global__ __launch_bounds__(NTHR) void conv3x3_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                              float* __restrict__ ws, int H, int W, int Cin, int Kout, int nchunks,
                                                              int slabs, long slot, int with_db) {
+    constexpr bool Q8 = MODE == MODE_Q8;
     constexpr int CH = Q8 ? 8 : 4, CW = Q8 ? 8 : 16;            // chunk rows x columns
     constexpr int PW = CW + 2, NPATCH = (CH + 2) * PW;           // patch: 6 x 18 = 108 px, or 10 x 10 = 100 px
     constexpr int NX = (NPATCH * 8 + NTHR - 1) / NTHR;           // float4 patch slots per thread (4)
@@ -73,7 +80,7 @@ __global__ __launch_bounds__(NTHR) void conv3x3_wgrad_kernel(const float* __rest
     const int CT = Cin / TKC, tiles = (Kout / TKC) * CT;
     const int items = slabs * tiles;
     const size_t plane = (size_t)H * W * 8;
-    const int bxn = Q8 ? 1 : W / 16, cpi = Q8 ? 1 : (H / 4) * bxn;     // chunks per image row group / per image
+    const int bxn = Q8 ? 1 : (W + 15) / 16, cpi = Q8 ? 1 : ((H + 3) / 4) * bxn;     // chunks per image row group / per image
 
     // per-thread staging slots, fixed for the whole kernel: float4 e = t + 256 i of the dy chunk -> (pixel, channel group, half),
     // of the patch -> (patch pixel, channel group, half; group >= 4: no such slot).  Recomputed where used: constants of t.
@@ -101,7 +108,12 @@ __global__ __launch_bounds__(NTHR) void conv3x3_wgrad_kernel(const float* __rest
             for (int i = 0; i < 2; ++i) {
                 DY_SLOT(i);
                 const int py = pix / CW, px = pix % CW;
-                rdy[i] = ld4v(dyb + cg * plane + ((size_t)(y0 + py) * W + x0 + px) * 8 + hf * 4);
+                if (MODE == MODE_RAGGED) {                                                       // behind the map's edge: zeros, never read
+                    rdy[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    if (y0 + py < H && x0 + px < W) rdy[i] = ld4v(dyb + cg * plane + ((size_t)(y0 + py) * W + x0 + px) * 8 + hf * 4);
+                } else {
+                    rdy[i] = ld4v(dyb + cg * plane + ((size_t)(y0 + py) * W + x0 + px) * 8 + hf * 4);
+                }
             }
 #pragma unroll
             for (int i = 0; i < NX; ++i) {
@@ -220,49 +232,68 @@ __global__ __launch_bounds__(256) void blocked_to_tokens_kernel(const float* __r
     st4v(tok + row * ld + 4 * q, v);
 }
 
-}  // namespace
-
-extern "C" size_t dhz_conv3x3_wgrad_workspace_bytes(int B, int H, int W, int Cin, int Kout) {
-    const Cut c = make_cut(B, H, W, Cin, Kout);
-    return c.ok ? (size_t)c.slabs * (size_t)c.slot * sizeof(float) : 0;
-}
-
-extern "C" int dhz_conv3x3_wgrad_parts(int B, int H, int W, int Cin, int Kout) {
-    const Cut c = make_cut(B, H, W, Cin, Kout);
-    return c.ok ? c.slabs : 0;
-}
-
-extern "C" int dhz_conv3x3_wgrad(const float* x, const float* dy, float* dw, float* db, float* ws, size_t ws_bytes, int B, int H,
-                                 int W, int Cin, int Kout, void* stream) {
-    DHZ_REQUIRE(x && dy && dw, "dhz_conv3x3_wgrad: null pointer (x=%p dy=%p dw=%p)", (const void*)x, (const void*)dy, (void*)dw);
-    const Cut c = make_cut(B, H, W, Cin, Kout);
-    DHZ_REQUIRE(c.ok,
-                "dhz_conv3x3_wgrad: unsupported shape B=%d H=%d W=%d Cin=%d Kout=%d (channels in 32s up to 512; maps in 16s, or 8 x 8)", B,
-                H, W, Cin, Kout);
+int wgrad(const char* who, bool any, const float* x, const float* dy, float* dw, float* db, float* ws, size_t ws_bytes, int B, int H, int W,
+          int Cin, int Kout, void* stream) {
+    DHZ_REQUIRE(x && dy && dw, "%s: null pointer (x=%p dy=%p dw=%p)", who, (const void*)x, (const void*)dy, (void*)dw);
+    const Cut c = make_cut(B, H, W, Cin, Kout, any);
+    DHZ_REQUIRE(c.ok, "%s: unsupported shape B=%d H=%d W=%d Cin=%d Kout=%d (channels in 32s up to 512; maps %s)", who, B, H, W, Cin, Kout,
+                any ? "of H, W >= 1" : "in 16s, or 8 x 8");
     const size_t need = (size_t)c.slabs * (size_t)c.slot * sizeof(float);
     if (dhz_det()) {                                              // the mode's workspace; the kernels are the same
-        ws = dhz_det_ws("dhz_conv3x3_wgrad", c.slabs, c.slot);
+        ws = dhz_det_ws(who, c.slabs, c.slot);
         if (!ws) return DHZ_EINVAL;
     } else {
-        DHZ_REQUIRE(ws, "dhz_conv3x3_wgrad: null workspace (%zu bytes needed: dhz_conv3x3_wgrad_workspace_bytes)", need);
-        DHZ_REQUIRE(ws_bytes >= need, "dhz_conv3x3_wgrad: workspace of %zu bytes, %zu needed", ws_bytes, need);
+        DHZ_REQUIRE(ws, "%s: null workspace (%zu bytes needed: dhz_conv3x3_wgrad_workspace_bytes%s)", who, need, any ? "_any" : "");
+        DHZ_REQUIRE(ws_bytes >= need, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, need);
     }
     hipStream_t s = (hipStream_t)stream;
     const int items = c.slabs * c.tiles;
     const int cap = WG_PER_CU * dhz_num_cus();
     const int grid = items < cap ? items : cap;
-    if (c.q8)
-        hipLaunchKernelGGL((conv3x3_wgrad_kernel<true>), dim3(grid), dim3(NTHR), 0, s, x, dy, ws, H, W, Cin, Kout, c.nchunks, c.slabs,
+    if (c.mode == MODE_Q8)
+        hipLaunchKernelGGL((conv3x3_wgrad_kernel<MODE_Q8>), dim3(grid), dim3(NTHR), 0, s, x, dy, ws, H, W, Cin, Kout, c.nchunks, c.slabs,
+                           c.slot, db != nullptr);
+    else if (c.mode == MODE_M16)
+        hipLaunchKernelGGL((conv3x3_wgrad_kernel<MODE_M16>), dim3(grid), dim3(NTHR), 0, s, x, dy, ws, H, W, Cin, Kout, c.nchunks, c.slabs,
                            c.slot, db != nullptr);
     else
-        hipLaunchKernelGGL((conv3x3_wgrad_kernel<false>), dim3(grid), dim3(NTHR), 0, s, x, dy, ws, H, W, Cin, Kout, c.nchunks, c.slabs,
-                           c.slot, db != nullptr);
-    DHZ_CHECK_LAUNCH("dhz_conv3x3_wgrad");
+        hipLaunchKernelGGL((conv3x3_wgrad_kernel<MODE_RAGGED>), dim3(grid), dim3(NTHR), 0, s, x, dy, ws, H, W, Cin, Kout, c.nchunks,
+                           c.slabs, c.slot, db != nullptr);
+    DHZ_CHECK_LAUNCH(who);
     const long total = c.wlen + (db ? Kout : 0);
     hipLaunchKernelGGL(conv3x3_wgrad_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, ws, c.slabs, c.slot, c.wlen,
                        total, dw, db);
-    DHZ_CHECK_LAUNCH("dhz_conv3x3_wgrad (reduction)");
+    DHZ_CHECK_LAUNCH(any ? "dhz_conv3x3_wgrad_any (reduction)" : "dhz_conv3x3_wgrad (reduction)");
     return DHZ_OK;
+}
+
+}  // namespace
+
+extern "C" size_t dhz_conv3x3_wgrad_workspace_bytes(int B, int H, int W, int Cin, int Kout) {
+    const Cut c = make_cut(B, H, W, Cin, Kout, false);
+    return c.ok ? (size_t)c.slabs * (size_t)c.slot * sizeof(float) : 0;
+}
+extern "C" size_t dhz_conv3x3_wgrad_workspace_bytes_any(int B, int H, int W, int Cin, int Kout) {
+    const Cut c = make_cut(B, H, W, Cin, Kout, true);
+    return c.ok ? (size_t)c.slabs * (size_t)c.slot * sizeof(float) : 0;
+}
+
+extern "C" int dhz_conv3x3_wgrad_parts(int B, int H, int W, int Cin, int Kout) {
+    const Cut c = make_cut(B, H, W, Cin, Kout, false);
+    return c.ok ? c.slabs : 0;
+}
+extern "C" int dhz_conv3x3_wgrad_parts_any(int B, int H, int W, int Cin, int Kout) {
+    const Cut c = make_cut(B, H, W, Cin, Kout, true);
+    return c.ok ? c.slabs : 0;
+}
+
+extern "C" int dhz_conv3x3_wgrad(const float* x, const float* dy, float* dw, float* db, float* ws, size_t ws_bytes, int B, int H,
+                                 int W, int Cin, int Kout, void* stream) {
+    return wgrad("dhz_conv3x3_wgrad", false, x, dy, dw, db, ws, ws_bytes, B, H, W, Cin, Kout, stream);
+}
+extern "C" int dhz_conv3x3_wgrad_any(const float* x, const float* dy, float* dw, float* db, float* ws, size_t ws_bytes, int B, int H,
+                                     int W, int Cin, int Kout, void* stream) {
+    return wgrad("dhz_conv3x3_wgrad_any", true, x, dy, dw, db, ws, ws_bytes, B, H, W, Cin, Kout, stream);
 }
 
 extern "C" int dhz_tokens_to_blocked8(const float* tok, int ld, const float* leaky_mask, float* blk, int B, int HW, int C, void* stream) {

@@ -3,10 +3,13 @@
 // FFA.py:9-21), their composition with the block residual (FFA.py:54-56, G = 1) and the fusion head over the three group outputs
 // (FFA.py:105-108, G = 3: the concatenated tensor is never built).  include/dehaze_hip.h, K13, has the formulas and the contracts.
 //
-// Cuts (functions of the shapes alone; H and W are multiples of 16, so H*W is a multiple of 256):
-//   pooling      chunks of PCH = 1024 pixels (the last one may be shorter), one 64-vector per (image, group, chunk)
-//   gate forward / backward-b   one thread per pixel / per float4, nothing reduced
-//   backward-a   chunks of BCH = 128 pixels, one slot of slot_len(G) floats per (image, chunk): [dca 64 G | dWp1 512 | dbp1 8 | dwp2 8 | dbp2 1]
+// Cuts (functions of the shapes alone).  The entries without `_any` take H and W in multiples of 16, so H*W is a multiple of 256 and every
+// workgroup below is full; the `_any` entries take any H, W >= 1 on the same launch code (on a multiple-of-16 shape: the same launch):
+//   pooling      chunks of PCH = 1024 pixels (the last one may be shorter, of any length), one 64-vector per (image, group, chunk)
+//   gate forward / backward-b   one thread per pixel / per float4, nothing reduced; ceil(HW / 256) workgroups per image, pixels >= HW idle
+//   backward-a   chunks of BCH = 128 pixels, ceil(HW / 128) per image, one slot of slot_len(G) floats per (image, chunk):
+//                [dca 64 G | dWp1 512 | dbp1 8 | dwp2 8 | dbp2 1].  In a partly filled last chunk the pixels >= HW are neither loaded nor
+//                stored and enter the slot's sums as zeros
 //   ca_bwd       level 1 sums SEG = 16 consecutive slots per (image, segment), level 2 (one workgroup per image) the segments, level 3 the
 //                images, all in ascending order
 // No atomics anywhere: the same bits from run to run, under any dhz_set_reserved_cus, with the deterministic mode on or off.
@@ -27,19 +30,22 @@ struct Maps { const float* m[3]; };
 struct MapsOut { float* m[3]; };
 
 struct Cut {
-    bool ok;
+    bool ok, ragged;
     long HW;
     int npch, nbch, nseg, slot;
     size_t fwd_floats, bwd_a_floats, seg_floats, bwd_floats;
 };
 
-Cut make_cut(int B, int H, int W, int G) {
+// any: the `_any` entries (H, W >= 1); otherwise multiples of 16.  ragged: HW is no multiple of 256 - the bounded kernel instances
+Cut make_cut(int B, int H, int W, int G, bool any) {
     Cut c{};
-    c.ok = B >= 1 && H >= 16 && W >= 16 && H % 16 == 0 && W % 16 == 0 && (G == 1 || G == 3) && (long)H * W * 64 < (1l << 31);
+    c.ok = B >= 1 && (any ? H >= 1 && W >= 1 : H >= 16 && W >= 16 && H % 16 == 0 && W % 16 == 0) && (G == 1 || G == 3) &&
+           (long)H * W * 64 < (1l << 31);
     if (!c.ok) return c;
     c.HW = (long)H * W;
+    c.ragged = c.HW % 256 != 0;
     c.npch = (int)((c.HW + PCH - 1) / PCH);
-    c.nbch = (int)(c.HW / BCH);
+    c.nbch = (int)((c.HW + BCH - 1) / BCH);
     c.nseg = (c.nbch + SEG - 1) / SEG;
     c.slot = slot_len(G);
     c.fwd_floats = (size_t)B * G * c.npch * 64;
@@ -59,7 +65,7 @@ __global__ __launch_bounds__(256) void ffa_pool_kernel(Maps maps, float* __restr
     const int ch = blockIdx.x, g = blockIdx.y, b = blockIdx.z;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int p0 = ch * PCH;
-    const int np = min(PCH, HW - p0);                      // pixels of this chunk (a multiple of 256)
+    const int np = min(PCH, HW - p0);                      // pixels of this chunk (any number: thread t sums float4s t, t + 256, ... < 2 np)
     const float* __restrict__ m = maps.m[g] + (size_t)b * 64 * HW;
 #pragma unroll 1
     for (int o = 0; o < 8; ++o) {
@@ -167,7 +173,8 @@ __device__ __forceinline__ float pixel_gate(const float (&t)[64], float (&h)[8],
     return sigmoidf_(z);
 }
 
-// ---- (b) out = t * pg (+ res): one pixel per thread, 256 pixels of one image per workgroup
+// ---- (b) out = t * pg (+ res): one pixel per thread, 256 pixels of one image per workgroup (RAGGED: the last one may hold fewer)
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void ffa_gate_pa_fwd_kernel(Maps maps, const float* __restrict__ ca, const float* __restrict__ Wp1,
                                                               const float* __restrict__ bp1, const float* __restrict__ wp2,
                                                               const float* __restrict__ bp2, const float* __restrict__ res,
@@ -176,6 +183,7 @@ __global__ __launch_bounds__(256) void ffa_gate_pa_fwd_kernel(Maps maps, const f
     const int b = blockIdx.y;
     stage_pa(S, ca, Wp1, bp1, wp2, bp2, b, G, 256);
     const int p = blockIdx.x * 256 + threadIdx.x;
+    if (RAGGED && p >= HW) return;                          // behind the parameters' barrier; no other follows
     const size_t img = (size_t)b * 64 * HW;
     float t[64], h[8];
     load_t(t, maps, S, img, HW, p, G);
@@ -193,7 +201,8 @@ __global__ __launch_bounds__(256) void ffa_gate_pa_fwd_kernel(Maps maps, const f
 
 // ---- (c) backward a: recompute t, h, pg; dt to memory; the workgroup's partial sums to its slot.  128 pixels per workgroup; a reduction
 // round puts one 64-vector per pixel into LDS ([pixel][65]: conflict-free both ways), thread (c = tid & 63, q = tid >> 6) sums the 64
-// pixels of wave q for channel c in ascending order, and the two halves are added.
+// pixels of wave q for channel c in ascending order, and the two halves are added.  RAGGED: the image's last workgroup may hold fewer than
+// 128 pixels; a thread whose pixel is >= HW loads and stores nothing and puts zeros into every LDS row it owns, so the sums keep their order.
 struct BwdSmem {
     PaSmem pa;
     float v[BCH][65];
@@ -201,6 +210,7 @@ struct BwdSmem {
     float r[2][64 * 9];
 };
 
+template <bool RAGGED>
 __global__ __launch_bounds__(BCH) void ffa_gate_pa_bwd_a_kernel(Maps maps, const float* __restrict__ ca, const float* __restrict__ Wp1,
                                                                 const float* __restrict__ bp1, const float* __restrict__ wp2,
                                                                 const float* __restrict__ bp2, const float* __restrict__ dout,
@@ -211,24 +221,32 @@ __global__ __launch_bounds__(BCH) void ffa_gate_pa_bwd_a_kernel(Maps maps, const
     const int p = blockIdx.x * BCH + tid;
     const size_t img = (size_t)b * 64 * HW;
     float* __restrict__ slot = ws + ((size_t)b * gridDim.x + blockIdx.x) * slot_len(G);
-    float t[64], h[8], dh[8];
-    load_t(t, maps, S.pa, img, HW, p, G);
-    const float pg = pixel_gate(t, h, S.pa);
-    // dpg = sum_c dout_c t_c, with dout read once: it is turned into dt in place below
-    float g[64];
-    float dpg = 0.f;
+    const bool live = !RAGGED || p < HW;
+    float t[64], h[8], dh[8], g[64];
+    float pg = 0.f, dz = 0.f;
+    if (live) {
+        load_t(t, maps, S.pa, img, HW, p, G);
+        pg = pixel_gate(t, h, S.pa);
+        // dpg = sum_c dout_c t_c, with dout read once: it is turned into dt in place below
+        float dpg = 0.f;
 #pragma unroll
-    for (int o = 0; o < 8; ++o) {
-        const size_t e = img + ((size_t)o * HW + p) * 8;
-        const f32x4 lo = ld4v(dout + e), hi = ld4v(dout + e + 4);
+        for (int o = 0; o < 8; ++o) {
+            const size_t e = img + ((size_t)o * HW + p) * 8;
+            const f32x4 lo = ld4v(dout + e), hi = ld4v(dout + e + 4);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            g[o * 8 + j] = lo[j]; g[o * 8 + 4 + j] = hi[j];
-            dpg = fmaf(lo[j], t[o * 8 + j], dpg);
-            dpg = fmaf(hi[j], t[o * 8 + 4 + j], dpg);
+            for (int j = 0; j < 4; ++j) {
+                g[o * 8 + j] = lo[j]; g[o * 8 + 4 + j] = hi[j];
+                dpg = fmaf(lo[j], t[o * 8 + j], dpg);
+                dpg = fmaf(hi[j], t[o * 8 + 4 + j], dpg);
+            }
         }
+        dz = dpg * pg * (1.0f - pg);
+    } else {                                                                   // a pixel behind the map: zeros all the way down
+#pragma unroll
+        for (int cc = 0; cc < 64; ++cc) { t[cc] = 0.f; g[cc] = 0.f; }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) h[i] = 0.f;
     }
-    const float dz = dpg * pg * (1.0f - pg);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         dh[i] = h[i] > 0.f ? dz * S.pa.w2[i] : 0.f;
@@ -244,11 +262,13 @@ __global__ __launch_bounds__(BCH) void ffa_gate_pa_bwd_a_kernel(Maps maps, const
         g[cc] = s;                                                            // dt
         S.v[tid][cc] = t[cc];
     }
+    if (live) {
 #pragma unroll
-    for (int o = 0; o < 8; ++o) {
-        const size_t e = img + ((size_t)o * HW + p) * 8;
-        st4v(dt + e, f32x4{g[o * 8], g[o * 8 + 1], g[o * 8 + 2], g[o * 8 + 3]});
-        st4v(dt + e + 4, f32x4{g[o * 8 + 4], g[o * 8 + 5], g[o * 8 + 6], g[o * 8 + 7]});
+        for (int o = 0; o < 8; ++o) {
+            const size_t e = img + ((size_t)o * HW + p) * 8;
+            st4v(dt + e, f32x4{g[o * 8], g[o * 8 + 1], g[o * 8 + 2], g[o * 8 + 3]});
+            st4v(dt + e + 4, f32x4{g[o * 8 + 4], g[o * 8 + 5], g[o * 8 + 6], g[o * 8 + 7]});
+        }
     }
     __syncthreads();
     // round 0: dWp1[i][c] = sum_p dh_i[p] t_c[p]
@@ -275,7 +295,8 @@ __global__ __launch_bounds__(BCH) void ffa_gate_pa_bwd_a_kernel(Maps maps, const
         const float* __restrict__ m = maps.m[gi] + img;
 #pragma unroll
         for (int o = 0; o < 8; ++o) {
-            const f32x4 lo = ld4v(m + ((size_t)o * HW + p) * 8), hi = ld4v(m + ((size_t)o * HW + p) * 8 + 4);
+            f32x4 lo = {0.f, 0.f, 0.f, 0.f}, hi = {0.f, 0.f, 0.f, 0.f};      // g is zero there too
+            if (live) { lo = ld4v(m + ((size_t)o * HW + p) * 8); hi = ld4v(m + ((size_t)o * HW + p) * 8 + 4); }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 S.v[tid][o * 8 + j] = g[o * 8 + j] * lo[j];
@@ -407,6 +428,15 @@ __global__ __launch_bounds__(256) void ffa_add_kernel(const float* __restrict__ 
     if (i < n4) st4v(y + 4 * i, ld4v(a + 4 * i) + ld4v(x + 4 * i));
 }
 
+// the same for any n: thread i owns floats 4 i .. 4 i + 3; the one that meets the end adds the last n % 4 floats one by one
+__global__ __launch_bounds__(256) void ffa_add_any_kernel(const float* __restrict__ a, const float* __restrict__ x, float* __restrict__ y,
+                                                          size_t n) {
+    const size_t e = 4 * ((size_t)blockIdx.x * 256 + threadIdx.x);
+    if (e + 4 <= n) st4v(y + e, ld4v(a + e) + ld4v(x + e));
+    else
+        for (size_t k = e; k < n; ++k) y[k] = a[k] + x[k];
+}
+
 __global__ __launch_bounds__(256) void ffa_relu_bwd_add_kernel(const float* __restrict__ a1, const float* __restrict__ dr,
                                                                const float* __restrict__ dout, float* __restrict__ dpre1,
                                                                float* __restrict__ s, size_t n4) {
@@ -424,9 +454,10 @@ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 #define FFA_SHAPE(who)                                                                                                                 \
     DHZ_REQUIRE(B >= 1, "%s: B=%d (at least 1)", who, B);                                                                              \
-    DHZ_REQUIRE(H >= 16 && W >= 16 && H % 16 == 0 && W % 16 == 0, "%s: H=%d W=%d (multiples of 16)", who, H, W);                       \
+    if (any) DHZ_REQUIRE(H >= 1 && W >= 1, "%s: H=%d W=%d (at least 1)", who, H, W);                                                   \
+    else DHZ_REQUIRE(H >= 16 && W >= 16 && H % 16 == 0 && W % 16 == 0, "%s: H=%d W=%d (multiples of 16)", who, H, W);                  \
     DHZ_REQUIRE(G == 1 || G == 3, "%s: G=%d (1 or 3)", who, G);                                                                        \
-    const Cut c = make_cut(B, H, W, G);                                                                                                \
+    const Cut c = make_cut(B, H, W, G, any);                                                                                           \
     DHZ_REQUIRE(c.ok, "%s: map of H=%d W=%d too large (64 H W must stay below 2^31)", who, H, W)
 
 #define FFA_MAPS(who, a0, a1, a2)                                                                                                      \
@@ -443,24 +474,21 @@ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
             ws = dhz_det_ws(who, 1, (long)(floats));                                                                                   \
             if (!ws) return DHZ_EINVAL;                                                                                                \
         } else {                                                                                                                       \
-            DHZ_REQUIRE(ws, "%s: null workspace (%zu bytes needed: dhz_ffa_workspace_bytes)", who, need_);                             \
+            DHZ_REQUIRE(ws, "%s: null workspace (%zu bytes needed: dhz_ffa_workspace_bytes%s)", who, need_, any ? "_any" : "");        \
             DHZ_REQUIRE(aligned16(ws), "%s: workspace %p must be 16-byte aligned", who, (void*)ws);                                    \
             DHZ_REQUIRE(ws_bytes >= need_, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, need_);                            \
         }                                                                                                                              \
     } while (0)
 
-}  // namespace
-
-extern "C" size_t dhz_ffa_workspace_bytes(int B, int H, int W, int G) {
-    const Cut c = make_cut(B, H, W, G);
+size_t workspace_bytes(int B, int H, int W, int G, bool any) {
+    const Cut c = make_cut(B, H, W, G, any);
     if (!c.ok) return 0;
     return (c.bwd_floats > c.fwd_floats ? c.bwd_floats : c.fwd_floats) * sizeof(float);
 }
 
-extern "C" int dhz_ffa_ca_fwd(const float* m0, const float* m1, const float* m2, const float* Wa, const float* ba, const float* Wb,
+int ca_fwd(const char* who, bool any, const float* m0, const float* m1, const float* m2, const float* Wa, const float* ba, const float* Wb,
                               const float* bb, float* mean, float* hid, float* ca, float* ws, size_t ws_bytes, int B, int H, int W, int G,
                               void* stream) {
-    const char* who = "dhz_ffa_ca_fwd";
     FFA_SHAPE(who);
     FFA_MAPS(who, m0, m1, m2);
     DHZ_REQUIRE(Wa && ba && Wb && bb && mean && hid && ca, "%s: null pointer (Wa=%p ba=%p Wb=%p bb=%p mean=%p hid=%p ca=%p)", who,
@@ -469,32 +497,35 @@ extern "C" int dhz_ffa_ca_fwd(const float* m0, const float* m1, const float* m2,
     hipStream_t s = (hipStream_t)stream;
     const Maps maps{{m0, m1, m2}};
     hipLaunchKernelGGL(ffa_pool_kernel, dim3(c.npch, G, B), dim3(256), 0, s, maps, ws, (int)c.HW, c.npch, G);
-    DHZ_CHECK_LAUNCH("dhz_ffa_ca_fwd (pooling)");
+    DHZ_CHECK_LAUNCH(any ? "dhz_ffa_ca_fwd_any (pooling)" : "dhz_ffa_ca_fwd (pooling)");
     hipLaunchKernelGGL(ffa_ca_mlp_kernel, dim3(B), dim3(256), 0, s, ws, Wa, ba, Wb, bb, mean, hid, ca, (int)c.HW, c.npch, G);
-    DHZ_CHECK_LAUNCH("dhz_ffa_ca_fwd (gate)");
+    DHZ_CHECK_LAUNCH(any ? "dhz_ffa_ca_fwd_any (gate)" : "dhz_ffa_ca_fwd (gate)");
     return DHZ_OK;
 }
 
-extern "C" int dhz_ffa_gate_pa_fwd(const float* m0, const float* m1, const float* m2, const float* ca, const float* Wp1, const float* bp1,
+int gate_pa_fwd(const char* who, bool any, const float* m0, const float* m1, const float* m2, const float* ca, const float* Wp1, const float* bp1,
                                    const float* wp2, const float* bp2, const float* res, float* out, int B, int H, int W, int G,
                                    void* stream) {
-    const char* who = "dhz_ffa_gate_pa_fwd";
     FFA_SHAPE(who);
     FFA_MAPS(who, m0, m1, m2);
     DHZ_REQUIRE(ca && Wp1 && bp1 && wp2 && bp2 && out, "%s: null pointer (ca=%p Wp1=%p bp1=%p wp2=%p bp2=%p out=%p)", who, (const void*)ca,
                 (const void*)Wp1, (const void*)bp1, (const void*)wp2, (const void*)bp2, (void*)out);
     DHZ_REQUIRE(aligned16(out) && aligned16(res), "%s: out=%p / res=%p must be 16-byte aligned", who, (void*)out, (const void*)res);
     const Maps maps{{m0, m1, m2}};
-    hipLaunchKernelGGL(ffa_gate_pa_fwd_kernel, dim3((unsigned)(c.HW / 256), B), dim3(256), 0, (hipStream_t)stream, maps, ca, Wp1, bp1, wp2,
-                       bp2, res, out, (int)c.HW, G);
+    const dim3 grid((unsigned)((c.HW + 255) / 256), B);
+    if (c.ragged)
+        hipLaunchKernelGGL(ffa_gate_pa_fwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, maps, ca, Wp1, bp1, wp2, bp2, res, out,
+                           (int)c.HW, G);
+    else
+        hipLaunchKernelGGL(ffa_gate_pa_fwd_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, maps, ca, Wp1, bp1, wp2, bp2, res, out,
+                           (int)c.HW, G);
     DHZ_CHECK_LAUNCH(who);
     return DHZ_OK;
 }
 
-extern "C" int dhz_ffa_gate_pa_bwd_a(const float* m0, const float* m1, const float* m2, const float* ca, const float* Wp1,
+int gate_pa_bwd_a(const char* who, bool any, const float* m0, const float* m1, const float* m2, const float* ca, const float* Wp1,
                                      const float* bp1, const float* wp2, const float* bp2, const float* dout, float* dt, float* ws,
                                      size_t ws_bytes, int B, int H, int W, int G, void* stream) {
-    const char* who = "dhz_ffa_gate_pa_bwd_a";
     FFA_SHAPE(who);
     FFA_MAPS(who, m0, m1, m2);
     DHZ_REQUIRE(ca && Wp1 && bp1 && wp2 && bp2 && dout && dt, "%s: null pointer (ca=%p Wp1=%p bp1=%p wp2=%p bp2=%p dout=%p dt=%p)", who,
@@ -502,16 +533,19 @@ extern "C" int dhz_ffa_gate_pa_bwd_a(const float* m0, const float* m1, const flo
     DHZ_REQUIRE(aligned16(dout) && aligned16(dt), "%s: dout=%p / dt=%p must be 16-byte aligned", who, (const void*)dout, (void*)dt);
     FFA_WS(who, c.bwd_floats);
     const Maps maps{{m0, m1, m2}};
-    hipLaunchKernelGGL(ffa_gate_pa_bwd_a_kernel, dim3(c.nbch, B), dim3(BCH), 0, (hipStream_t)stream, maps, ca, Wp1, bp1, wp2, bp2, dout, dt,
-                       ws, (int)c.HW, G);
+    if (c.HW % BCH)
+        hipLaunchKernelGGL(ffa_gate_pa_bwd_a_kernel<true>, dim3(c.nbch, B), dim3(BCH), 0, (hipStream_t)stream, maps, ca, Wp1, bp1, wp2, bp2,
+                           dout, dt, ws, (int)c.HW, G);
+    else
+        hipLaunchKernelGGL(ffa_gate_pa_bwd_a_kernel<false>, dim3(c.nbch, B), dim3(BCH), 0, (hipStream_t)stream, maps, ca, Wp1, bp1, wp2, bp2,
+                           dout, dt, ws, (int)c.HW, G);
     DHZ_CHECK_LAUNCH(who);
     return DHZ_OK;
 }
 
-extern "C" int dhz_ffa_ca_bwd(float* ws, size_t ws_bytes, const float* Wa, const float* Wb, const float* mean, const float* hid,
+int ca_bwd(const char* who, bool any, float* ws, size_t ws_bytes, const float* Wa, const float* Wb, const float* mean, const float* hid,
                               const float* ca, float* dWa, float* dba, float* dWb, float* dbb, float* dmean, float* dWp1, float* dbp1,
                               float* dwp2, float* dbp2, int B, int H, int W, int G, void* stream) {
-    const char* who = "dhz_ffa_ca_bwd";
     FFA_SHAPE(who);
     DHZ_REQUIRE(Wa && Wb && mean && hid && ca, "%s: null pointer (Wa=%p Wb=%p mean=%p hid=%p ca=%p)", who, (const void*)Wa, (const void*)Wb,
                 (const void*)mean, (const void*)hid, (const void*)ca);
@@ -523,19 +557,18 @@ extern "C" int dhz_ffa_ca_bwd(float* ws, size_t ws_bytes, const float* Wa, const
     float* segs = ws + c.bwd_a_floats;
     hipLaunchKernelGGL(ffa_seg_sum_kernel, dim3((c.slot + 255) / 256, c.nseg, B), dim3(256), 0, s, ws, segs, c.nbch, c.nseg, c.slot,
                        64 * G + NPA);
-    DHZ_CHECK_LAUNCH("dhz_ffa_ca_bwd (segments)");
+    DHZ_CHECK_LAUNCH(any ? "dhz_ffa_ca_bwd_any (segments)" : "dhz_ffa_ca_bwd (segments)");
     float* recs = segs + c.seg_floats;
     hipLaunchKernelGGL(ffa_ca_bwd_image_kernel, dim3(B), dim3(256), 0, s, segs, Wa, Wb, mean, hid, ca, dmean, recs, c.nseg, G);
-    DHZ_CHECK_LAUNCH("dhz_ffa_ca_bwd (images)");
+    DHZ_CHECK_LAUNCH(any ? "dhz_ffa_ca_bwd_any (images)" : "dhz_ffa_ca_bwd (images)");
     hipLaunchKernelGGL(ffa_ca_bwd_sum_kernel, dim3((img_len(G) + 255) / 256), dim3(256), 0, s, recs, dWa, dba, dWb, dbb, dWp1, dbp1, dwp2,
                        dbp2, B, G);
     DHZ_CHECK_LAUNCH(who);
     return DHZ_OK;
 }
 
-extern "C" int dhz_ffa_gate_pa_bwd_b(const float* dt, const float* ca, const float* dmean, float* dm0, float* dm1, float* dm2, int B, int H,
+int gate_pa_bwd_b(const char* who, bool any, const float* dt, const float* ca, const float* dmean, float* dm0, float* dm1, float* dm2, int B, int H,
                                      int W, int G, void* stream) {
-    const char* who = "dhz_ffa_gate_pa_bwd_b";
     FFA_SHAPE(who);
     FFA_MAPS(who, dm0, dm1, dm2);
     DHZ_REQUIRE(dt && ca && dmean, "%s: null pointer (dt=%p ca=%p dmean=%p)", who, (const void*)dt, (const void*)ca, (const void*)dmean);
@@ -549,6 +582,69 @@ extern "C" int dhz_ffa_gate_pa_bwd_b(const float* dt, const float* ca, const flo
     return DHZ_OK;
 }
 
+}  // namespace
+
+// every entry twice: multiples of 16 only, and (`_any`) any H, W >= 1 on the same launch code
+extern "C" size_t dhz_ffa_workspace_bytes(int B, int H, int W, int G) { return workspace_bytes(B, H, W, G, false); }
+extern "C" size_t dhz_ffa_workspace_bytes_any(int B, int H, int W, int G) { return workspace_bytes(B, H, W, G, true); }
+
+#define FFA_CA_FWD_ARGS                                                                                                                \
+    const float *m0, const float *m1, const float *m2, const float *Wa, const float *ba, const float *Wb, const float *bb, float *mean, \
+        float *hid, float *ca, float *ws, size_t ws_bytes, int B, int H, int W, int G, void *stream
+extern "C" int dhz_ffa_ca_fwd(FFA_CA_FWD_ARGS) {
+    return ca_fwd("dhz_ffa_ca_fwd", false, m0, m1, m2, Wa, ba, Wb, bb, mean, hid, ca, ws, ws_bytes, B, H, W, G, stream);
+}
+extern "C" int dhz_ffa_ca_fwd_any(FFA_CA_FWD_ARGS) {
+    return ca_fwd("dhz_ffa_ca_fwd_any", true, m0, m1, m2, Wa, ba, Wb, bb, mean, hid, ca, ws, ws_bytes, B, H, W, G, stream);
+}
+#undef FFA_CA_FWD_ARGS
+
+#define FFA_GATE_FWD_ARGS                                                                                                              \
+    const float *m0, const float *m1, const float *m2, const float *ca, const float *Wp1, const float *bp1, const float *wp2,           \
+        const float *bp2, const float *res, float *out, int B, int H, int W, int G, void *stream
+extern "C" int dhz_ffa_gate_pa_fwd(FFA_GATE_FWD_ARGS) {
+    return gate_pa_fwd("dhz_ffa_gate_pa_fwd", false, m0, m1, m2, ca, Wp1, bp1, wp2, bp2, res, out, B, H, W, G, stream);
+}
+extern "C" int dhz_ffa_gate_pa_fwd_any(FFA_GATE_FWD_ARGS) {
+    return gate_pa_fwd("dhz_ffa_gate_pa_fwd_any", true, m0, m1, m2, ca, Wp1, bp1, wp2, bp2, res, out, B, H, W, G, stream);
+}
+#undef FFA_GATE_FWD_ARGS
+
+#define FFA_BWD_A_ARGS                                                                                                                 \
+    const float *m0, const float *m1, const float *m2, const float *ca, const float *Wp1, const float *bp1, const float *wp2,           \
+        const float *bp2, const float *dout, float *dt, float *ws, size_t ws_bytes, int B, int H, int W, int G, void *stream
+extern "C" int dhz_ffa_gate_pa_bwd_a(FFA_BWD_A_ARGS) {
+    return gate_pa_bwd_a("dhz_ffa_gate_pa_bwd_a", false, m0, m1, m2, ca, Wp1, bp1, wp2, bp2, dout, dt, ws, ws_bytes, B, H, W, G, stream);
+}
+extern "C" int dhz_ffa_gate_pa_bwd_a_any(FFA_BWD_A_ARGS) {
+    return gate_pa_bwd_a("dhz_ffa_gate_pa_bwd_a_any", true, m0, m1, m2, ca, Wp1, bp1, wp2, bp2, dout, dt, ws, ws_bytes, B, H, W, G, stream);
+}
+#undef FFA_BWD_A_ARGS
+
+#define FFA_CA_BWD_ARGS                                                                                                                \
+    float *ws, size_t ws_bytes, const float *Wa, const float *Wb, const float *mean, const float *hid, const float *ca, float *dWa,    \
+        float *dba, float *dWb, float *dbb, float *dmean, float *dWp1, float *dbp1, float *dwp2, float *dbp2, int B, int H, int W,     \
+        int G, void *stream
+extern "C" int dhz_ffa_ca_bwd(FFA_CA_BWD_ARGS) {
+    return ca_bwd("dhz_ffa_ca_bwd", false, ws, ws_bytes, Wa, Wb, mean, hid, ca, dWa, dba, dWb, dbb, dmean, dWp1, dbp1, dwp2, dbp2, B, H, W, G,
+                  stream);
+}
+extern "C" int dhz_ffa_ca_bwd_any(FFA_CA_BWD_ARGS) {
+    return ca_bwd("dhz_ffa_ca_bwd_any", true, ws, ws_bytes, Wa, Wb, mean, hid, ca, dWa, dba, dWb, dbb, dmean, dWp1, dbp1, dwp2, dbp2, B, H, W,
+                  G, stream);
+}
+#undef FFA_CA_BWD_ARGS
+
+#define FFA_BWD_B_ARGS                                                                                                                 \
+    const float *dt, const float *ca, const float *dmean, float *dm0, float *dm1, float *dm2, int B, int H, int W, int G, void *stream
+extern "C" int dhz_ffa_gate_pa_bwd_b(FFA_BWD_B_ARGS) {
+    return gate_pa_bwd_b("dhz_ffa_gate_pa_bwd_b", false, dt, ca, dmean, dm0, dm1, dm2, B, H, W, G, stream);
+}
+extern "C" int dhz_ffa_gate_pa_bwd_b_any(FFA_BWD_B_ARGS) {
+    return gate_pa_bwd_b("dhz_ffa_gate_pa_bwd_b_any", true, dt, ca, dmean, dm0, dm1, dm2, B, H, W, G, stream);
+}
+#undef FFA_BWD_B_ARGS
+
 extern "C" int dhz_ffa_add(const float* a, const float* x, float* y, int64_t n, void* stream) {
     DHZ_REQUIRE(a && x && y, "dhz_ffa_add: null pointer (a=%p x=%p y=%p)", (const void*)a, (const void*)x, (void*)y);
     DHZ_REQUIRE(n > 0 && n % 4 == 0, "dhz_ffa_add: n=%lld (a positive multiple of 4)", (long long)n);
@@ -557,6 +653,17 @@ extern "C" int dhz_ffa_add(const float* a, const float* x, float* y, int64_t n, 
     const size_t n4 = (size_t)n / 4;
     hipLaunchKernelGGL(ffa_add_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, x, y, n4);
     DHZ_CHECK_LAUNCH("dhz_ffa_add");
+    return DHZ_OK;
+}
+
+extern "C" int dhz_ffa_add_any(const float* a, const float* x, float* y, int64_t n, void* stream) {
+    DHZ_REQUIRE(a && x && y, "dhz_ffa_add_any: null pointer (a=%p x=%p y=%p)", (const void*)a, (const void*)x, (void*)y);
+    DHZ_REQUIRE(n > 0, "dhz_ffa_add_any: n=%lld (positive)", (long long)n);
+    DHZ_REQUIRE(aligned16(a) && aligned16(x) && aligned16(y), "dhz_ffa_add_any: pointers must be 16-byte aligned (a=%p x=%p y=%p)",
+                (const void*)a, (const void*)x, (void*)y);
+    const size_t n4 = ((size_t)n + 3) / 4;
+    hipLaunchKernelGGL(ffa_add_any_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, x, y, (size_t)n);
+    DHZ_CHECK_LAUNCH("dhz_ffa_add_any");
     return DHZ_OK;
 }
 

@@ -183,6 +183,17 @@ SIGNATURES = {
     "dhz_ffa_ca_bwd": [c_f, ctypes.c_size_t] + [c_f] * 14 + [c_i, c_i, c_i, c_i, c_p],
     "dhz_ffa_gate_pa_bwd_b": [c_f] * 6 + [c_i, c_i, c_i, c_i, c_p],
     "dhz_ffa_add": [c_f, c_f, c_f, c_l, c_p],
+    # the same attention entries and the dense weight gradient on maps of any size (ragged tails; FFA-Net on whole images)
+    "dhz_ffa_workspace_bytes_any": [c_i, c_i, c_i, c_i],
+    "dhz_ffa_add_any": [c_f, c_f, c_f, c_l, c_p],
+    "dhz_ffa_ca_fwd_any": [c_f] * 11 + [ctypes.c_size_t, c_i, c_i, c_i, c_i, c_p],
+    "dhz_ffa_gate_pa_fwd_any": [c_f] * 10 + [c_i, c_i, c_i, c_i, c_p],
+    "dhz_ffa_gate_pa_bwd_a_any": [c_f] * 11 + [ctypes.c_size_t, c_i, c_i, c_i, c_i, c_p],
+    "dhz_ffa_ca_bwd_any": [c_f, ctypes.c_size_t] + [c_f] * 14 + [c_i, c_i, c_i, c_i, c_p],
+    "dhz_ffa_gate_pa_bwd_b_any": [c_f] * 6 + [c_i, c_i, c_i, c_i, c_p],
+    "dhz_conv3x3_wgrad_workspace_bytes_any": [c_i, c_i, c_i, c_i, c_i],
+    "dhz_conv3x3_wgrad_parts_any": [c_i, c_i, c_i, c_i, c_i],
+    "dhz_conv3x3_wgrad_any": [c_f, c_f, c_f, c_f, c_f, ctypes.c_size_t, c_i, c_i, c_i, c_i, c_i, c_p],
     "dhz_ffa_relu_bwd_add": [c_f, c_f, c_f, c_f, c_f, c_l, c_p],
     # squared-error taps of FFA-Net's perceptual loss, pooling backward of a map that is a tap too (csrc/perceptual.hip)
     "dhz_mse_pair_fwd": [c_f, c_f, c_f, c_l, c_p],
@@ -190,7 +201,8 @@ SIGNATURES = {
     "dhz_maxpool2x2_blocked_bwd_add": [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_p],
 }
 _RESTYPE = {"dhz_last_error": ctypes.c_char_p, "dhz_build_id": ctypes.c_char_p, "dhz_conv3x3_wgrad_workspace_bytes": ctypes.c_size_t,
-            "dhz_ffa_workspace_bytes": ctypes.c_size_t}
+            "dhz_ffa_workspace_bytes": ctypes.c_size_t, "dhz_conv3x3_wgrad_workspace_bytes_any": ctypes.c_size_t,
+            "dhz_ffa_workspace_bytes_any": ctypes.c_size_t}
 
 _lib = None
 

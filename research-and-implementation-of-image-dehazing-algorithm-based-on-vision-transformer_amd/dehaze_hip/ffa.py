@@ -1,7 +1,7 @@
 """FFA-Net, the second CNN baseline the reference measures against (FFA_model/models/FFA.py:9-110; get_arch 'FFA').  Module tree,
 attribute names, registration order and init stream are the reference's, so seeded construction draws the same parameters and its
-checkpoints load; there are no buffers.  CPU tensors run the plain-torch path.  On a HIP device (fp32, H and W multiples of 16) every
-layer runs the hand-written kernels and the maps stay channel-blocked [B][8][H][W][8] from `pre` to `post[0]`:
+checkpoints load; there are no buffers.  CPU tensors run the plain-torch path.  On a HIP device (fp32, a map size blocked_shape_ok takes)
+every layer runs the hand-written kernels and the maps stay channel-blocked [B][8][H][W][8] from `pre` to `post[0]`:
 
   pre[0] 3 -> 64                        dhz_conv3x3_in3_blocked (relu = 0); weight gradient dhz_input_proj_bwd with slope 1
   Block.conv1 + act1                    Winograd convolution with the ReLU in its store; a1 is saved, its sign is the backward's mask
@@ -10,12 +10,21 @@ layer runs the hand-written kernels and the maps stay channel-blocked [B][8][H][
   calayer, palayer, `res += x`          dhz_ffa_ca_fwd + dhz_ffa_gate_pa_fwd, G = 1          (csrc/ffa_attn.hip)
   self.ca over the three group outputs, the weighted sum, self.palayer     the same two entries, G = 3: nothing is concatenated
   group residual                        dhz_ffa_add
-  post[1] 64 -> 3, + x1                 dhz_blocked8_to_tokens, ops.thin_conv3x3, dhz_ffa_add
+  post[1] 64 -> 3, + x1                 dhz_blocked8_to_tokens, ops.thin_conv3x3, dhz_ffa_add (dhz_ffa_add_any where 3 B H W % 4 != 0)
   every 3x3 weight gradient             dhz_conv3x3_wgrad
 
 A block keeps x, a1, c2 (conv2's output) and the small vectors mean, hid, ca for its backward; res = a1 + x is formed again there (the
 same bits) rather than stored, and the gated map, the pixel gate and the block output are recomputed by the backward kernels.
-Any other input (another dtype, a side that is no multiple of 16) runs the library convolutions through ops.warn_library_fallback."""
+
+Whole images (FFA_model/test.py:49-61, data_utils.py:21-23: `size='whole img'`, 620 x 460 on SOTS-indoor) have sides that are no
+multiples of 16.  On such a ragged map the same layers call the `_any` entries: dhz_winograd_conv3x3_any (ragged 16 x 16 blocks),
+dhz_conv3x3_wgrad_any (ragged 4 x 16 chunks), dhz_ffa_*_any (bounded tails); the other entries in the table take any H, W as they
+are.  dhz_winograd_conv3x3_any is F(2x2) only - the F(4x4) kernel has no ragged mode - so FWD_F43 / BWD_F43 are ignored on ragged
+maps.  On a multiple-of-16 map every helper calls exactly what it called before those entries existed.  DHZ_FFA_ANY=0 (A/B switch)
+keeps ragged maps on the library path.
+Any other input (another dtype, a ragged map with a side below 32) runs the library convolutions through ops.warn_library_fallback."""
+import os
+
 import torch
 import torch.nn as nn
 from torch.autograd import Function
@@ -24,6 +33,22 @@ DIM = 64
 # Winograd variant per direction: F(2x2,3x3) (dhz_winograd_conv3x3) or F(4x4,3x3) (dhz_winograd43_conv3x3, ~2x the rounding error)
 FWD_F43 = False
 BWD_F43 = False
+ANY = os.environ.get("DHZ_FFA_ANY", "1") != "0"      # A/B switch: ragged maps on the `_any` entries (off: on the library path, with the warning)
+ANY_MIN = 32
+
+
+def blocked_shape_ok(H, W):
+    """map sizes the blocked path takes: both sides multiples of 16 (from 16 up), as ever; or, with ANY, any other H x W with both sides
+    at least ANY_MIN = 32.  The floor is deliberate: 32 is LossNetwork's smallest patch too, no dehazing set has smaller images, and
+    ragged maps below it (24 x 40 ...) keep the library path they have always had."""
+    if H % 16 == 0 and W % 16 == 0:
+        return H >= 16 and W >= 16
+    return ANY and H >= ANY_MIN and W >= ANY_MIN
+
+
+def _ragged(H, W):
+    """a map only the `_any` entries take"""
+    return H % 16 != 0 or W % 16 != 0
 
 
 def _lib():
@@ -37,11 +62,13 @@ def _conv64(xb, w, transposed, bias, relu, addend, f43):
     L = _lib()
     B, _, H, W, _ = xb.shape
     st = ops._stream()
+    ragged = _ragged(H, W)
+    f43 = f43 and not ragged                                         # the F(4x4) kernel has no ragged mode
     up = torch.empty((36 if f43 else 16) * DIM * DIM, device=xb.device, dtype=torch.float32)
     L.call("dhz_winograd43_prepack" if f43 else "dhz_winograd_prepack", ops._p(w), ops._p(up), DIM, DIM, int(transposed), st)
     y = torch.empty_like(xb)
-    L.call("dhz_winograd43_conv3x3" if f43 else "dhz_winograd_conv3x3", ops._p(xb), ops._p(up), ops._p(bias), int(relu), None,
-           ops._p(addend), ops._p(y), B, H, W, DIM, DIM, st)
+    entry = "dhz_winograd_conv3x3_any" if ragged else ("dhz_winograd43_conv3x3" if f43 else "dhz_winograd_conv3x3")
+    L.call(entry, ops._p(xb), ops._p(up), ops._p(bias), int(relu), None, ops._p(addend), ops._p(y), B, H, W, DIM, DIM, st)
     return y
 
 
@@ -51,22 +78,26 @@ def _wgrad64(xb, dyb, w):
     B, _, H, W, _ = xb.shape
     dw = torch.empty_like(w)
     db = torch.empty(DIM, device=xb.device, dtype=torch.float32)
-    need = L.load().dhz_conv3x3_wgrad_workspace_bytes(B, H, W, DIM, DIM)
+    sfx = "_any" if _ragged(H, W) else ""
+    need = getattr(L.load(), "dhz_conv3x3_wgrad_workspace_bytes" + sfx)(B, H, W, DIM, DIM)
     ws = None if ops.DETERMINISTIC else torch.empty(need // 4, device=xb.device, dtype=torch.float32)
-    L.call("dhz_conv3x3_wgrad", ops._p(xb), ops._p(dyb), ops._p(dw), ops._p(db), ops._p(ws), need, B, H, W, DIM, DIM, ops._stream())
+    L.call("dhz_conv3x3_wgrad" + sfx, ops._p(xb), ops._p(dyb), ops._p(dw), ops._p(db), ops._p(ws), need, B, H, W, DIM, DIM, ops._stream())
     return dw, db
 
 
 def _add(a, x):
     from . import ops
+    # a batch slice of an image whose 3 H W is no multiple of 4 starts off the 16 bytes the kernels load by: a copy of it does not
+    a, x = (t if t.data_ptr() % 16 == 0 else t.clone() for t in (a, x))
     y = torch.empty_like(a)
-    _lib().call("dhz_ffa_add", ops._p(a), ops._p(x), ops._p(y), a.numel(), ops._stream())
+    # an image's 3 B H W floats need not come in fours (413 x 550); a blocked map's 64 B H W always do
+    _lib().call("dhz_ffa_add" if a.numel() % 4 == 0 else "dhz_ffa_add_any", ops._p(a), ops._p(x), ops._p(y), a.numel(), ops._stream())
     return y
 
 
 def _workspace(B, H, W, G, device):
     from . import ops
-    need = _lib().load().dhz_ffa_workspace_bytes(B, H, W, G)
+    need = getattr(_lib().load(), "dhz_ffa_workspace_bytes" + ("_any" if _ragged(H, W) else ""))(B, H, W, G)
     return (None if ops.DETERMINISTIC else torch.empty(need // 4, device=device, dtype=torch.float32)), need
 
 
@@ -85,10 +116,11 @@ def _attn_fwd(maps, attn, res):
     hid = torch.empty((B, hc), device=dev, dtype=torch.float32)
     ca = torch.empty((B, DIM * G), device=dev, dtype=torch.float32)
     ws, need = _workspace(B, H, W, G, dev)
-    L.call("dhz_ffa_ca_fwd", *m, ops._p(Wa), ops._p(ba), ops._p(Wb), ops._p(bb), ops._p(mean), ops._p(hid), ops._p(ca), ops._p(ws), need,
+    sfx = "_any" if _ragged(H, W) else ""
+    L.call("dhz_ffa_ca_fwd" + sfx, *m, ops._p(Wa), ops._p(ba), ops._p(Wb), ops._p(bb), ops._p(mean), ops._p(hid), ops._p(ca), ops._p(ws), need,
            B, H, W, G, st)
     out = torch.empty_like(maps[0])
-    L.call("dhz_ffa_gate_pa_fwd", *m, ops._p(ca), ops._p(Wp1), ops._p(bp1), ops._p(wp2), ops._p(bp2), ops._p(res), ops._p(out), B, H, W, G,
+    L.call("dhz_ffa_gate_pa_fwd" + sfx, *m, ops._p(ca), ops._p(Wp1), ops._p(bp1), ops._p(wp2), ops._p(bp2), ops._p(res), ops._p(out), B, H, W, G,
            st)
     return out, (mean, hid, ca)
 
@@ -105,16 +137,17 @@ def _attn_bwd(maps, attn, vecs, dout):
     st = ops._stream()
     m = [ops._p(t) for t in maps] + [None] * (3 - G)
     ws, need = _workspace(B, H, W, G, dev)
+    sfx = "_any" if _ragged(H, W) else ""
     dt = torch.empty_like(maps[0])
-    L.call("dhz_ffa_gate_pa_bwd_a", *m, ops._p(ca), ops._p(Wp1), ops._p(bp1), ops._p(wp2), ops._p(bp2), ops._p(dout), ops._p(dt), ops._p(ws),
+    L.call("dhz_ffa_gate_pa_bwd_a" + sfx, *m, ops._p(ca), ops._p(Wp1), ops._p(bp1), ops._p(wp2), ops._p(bp2), ops._p(dout), ops._p(dt), ops._p(ws),
            need, B, H, W, G, st)
     grads = [torch.empty_like(p) for p in attn]
     dmean = torch.empty_like(mean)
     dWa, dba, dWb, dbb, dWp1, dbp1, dwp2, dbp2 = grads
-    L.call("dhz_ffa_ca_bwd", ops._p(ws), need, ops._p(Wa), ops._p(Wb), ops._p(mean), ops._p(hid), ops._p(ca), ops._p(dWa), ops._p(dba),
+    L.call("dhz_ffa_ca_bwd" + sfx, ops._p(ws), need, ops._p(Wa), ops._p(Wb), ops._p(mean), ops._p(hid), ops._p(ca), ops._p(dWa), ops._p(dba),
            ops._p(dWb), ops._p(dbb), ops._p(dmean), ops._p(dWp1), ops._p(dbp1), ops._p(dwp2), ops._p(dbp2), B, H, W, G, st)
     dm = [torch.empty_like(maps[0]) for _ in range(G)]
-    L.call("dhz_ffa_gate_pa_bwd_b", ops._p(dt), ops._p(ca), ops._p(dmean), *([ops._p(t) for t in dm] + [None] * (3 - G)), B, H, W, G, st)
+    L.call("dhz_ffa_gate_pa_bwd_b" + sfx, ops._p(dt), ops._p(ca), ops._p(dmean), *([ops._p(t) for t in dm] + [None] * (3 - G)), B, H, W, G, st)
     return dm, grads
 
 
@@ -344,7 +377,7 @@ class FFA(nn.Module):
         if not x1.is_cuda:
             return self._forward_torch(x1)
         B, C, H, W = x1.shape
-        if x1.dtype != torch.float32 or C != 3 or H % 16 != 0 or W % 16 != 0 or H < 16 or W < 16:
+        if x1.dtype != torch.float32 or C != 3 or not blocked_shape_ok(H, W):
             from . import ops
             ops.warn_library_fallback("FFA", (C, H, W, str(x1.dtype)))
             return self._forward_torch(x1)
