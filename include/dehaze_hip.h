@@ -617,6 +617,25 @@ int dhz_mse_pair_bwd(const float* a, const float* g, const float* gmean, float* 
 int dhz_maxpool2x2_blocked_bwd_add(const float* gy, const float* act, const float* addend, float* gx, int N, int H, int W,
                                    void* stream);
 
+/* K11e whole images (the reference's default, FFA_model/data_utils.py:21: crop_size = 'whole_img'): the three poolings of the blocked layout
+ *      and the L1 mean on ANY size.  fp32 only.
+ *      dhz_maxpool2x2_blocked_fwd_any / _bwd_any / _bwd_add_any: the entries of the same name without `_any` for any H, W >= 2 (DHZ_EINVAL
+ *        below, before a launch), floor mode as nn.MaxPool2d(2, 2): x / act / addend / gx [N][H][W][8], y / gy [N][H / 2][W / 2][8]; an odd
+ *        last row or column feeds no window.  The two backward entries write EVERY element of gx: inside the windows the routing above
+ *        (first maximum, through the ReLU act > 0); on the dropped row / column gx = 0 (_bwd_any) or gx = act > 0 ? addend : 0
+ *        (_bwd_add_any: the tap's own gradient alone).  Maps 16-byte aligned.  On even H, W the bits of the entries above.  No atomics.
+ *      dhz_l1_pair_fwd_any / _bwd_any: K11b for any count >= 1 and 4-byte aligned pointers: a float4 body from the first element at which
+ *        all pointers are 16-byte aligned (none when they never are together), the elements before and behind it one by one.  Same
+ *        accumulation as K11b (one partial per workgroup, fp32 atomics or, in deterministic mode, workspace slots and dhz_det_reduce;
+ *        the cut into workgroups is a function of count and of the pointers' alignment); where K11b applies (count % 4 == 0, 16-byte
+ *        aligned pointers), the same launch geometry and the same bits per workgroup. */
+int dhz_maxpool2x2_blocked_fwd_any(const float* x, float* y, int N, int H, int W, void* stream);
+int dhz_maxpool2x2_blocked_bwd_any(const float* gy, const float* act, float* gx, int N, int H, int W, void* stream);
+int dhz_maxpool2x2_blocked_bwd_add_any(const float* gy, const float* act, const float* addend, float* gx, int N, int H, int W,
+                                       void* stream);
+int dhz_l1_pair_fwd_any(const float* a, const float* p, const float* n, float* sums, int64_t count, void* stream);
+int dhz_l1_pair_bwd_any(const float* a, const float* p, const float* n, const float* g, float* da, int64_t count, void* stream);
+
 /* K10b the same feature stack for BASELINE config 4 (bf16 feature maps in NHWC / token layout [N, H, W, C]; what torch.autocast
  *      makes of My_CR.py:65-72's convolutions), csrc/vgg_bf16.hip:
  *      dhz_vgg_prepack_bf16: filter w[K, C, 3, 3] fp32 -> bf16 [K][9 C] tap-major (transpose = 0) or the backward-data filter
@@ -650,6 +669,11 @@ int dhz_contrast_combine_bwd(const float* d, const float* w, int k, int ablation
  *     dims=[-1,-2], 4-7 the same followed by flip(-2)), float32 [n,3,ps,ps] = value / 255. */
 int dhz_crop_augment_pair(const uint8_t* gt, const uint8_t* hazy, const int* table, float* out_gt, float* out_hazy,
                           int n, int Hs, int Ws, int ps, void* stream);
+/*     dhz_crop_augment_pair_rect: the same for an h x w crop (h <= Hs, w <= Ws; h = Hs, w = Ws: whole images), float32 [n,3,h,w].  For
+ *     h != w only the four shape-preserving maps exist and the kernel reads k & 6 (0 id, 2 rot180, 4 flip(-2), 6 flip(-1)); for h == w all
+ *     eight, bit for bit dhz_crop_augment_pair.  The caller keeps r + h <= Hs and c + w <= Ws. */
+int dhz_crop_augment_pair_rect(const uint8_t* gt, const uint8_t* hazy, const int* table, float* out_gt, float* out_hazy,
+                               int n, int Hs, int Ws, int h, int w, void* stream);
 
 /* K6  shift mask builder: mask[nW,64,64] in {0,-100}  (M1:803-836), Hres x Wres map, win 8. */
 int dhz_shift_mask(float* mask, int Hres, int Wres, int shift, void* stream);

@@ -9,6 +9,13 @@ trains its FFA baseline with, as opposed to My_train.py --arch FFA, which trains
     `<model_dir><name>_<step>_psnr: <p>_ssim: <s>.pk` with the reference's keys (step, max_psnr, max_ssim, ssims, psnrs, losses, model),
     and `<model_dir><name>_best.pk` when both metrics improve.  `model` keys carry DataParallel's `module.` prefix like the reference's;
     utils.load_checkpoint reads either form, so `test_long_GPU.py --arch FFA --weights x.pk` evaluates such a file.
+  * --whole_img: batches are whole stored images, no crop - the REFERENCE'S DEFAULT setting (FFA_model/data_utils.py:21-23: crop_size =
+    'whole_img' unless --crop is given; SOTS / ITS frames are 620 x 460, NH-HAZE frames 1600 x 1200).  Here it is an explicit option:
+    without it the script cuts --crop_size squares as before (and still ignores --crop).  The images of a store share one size
+    (PatchStoreHBM.from_dir asserts it); they pass the feed kernel's h x w form (dhz_crop_augment_pair_rect: identity, rot180 and the two
+    flips on non-square frames - see PatchStoreHBM.batch), the network's `_any` kernels, the any-size L1 mean and, with --perloss, the
+    VGG16 engine's ragged convolutions and floor-mode poolings: no library compute op in the step for sides from 32 up.  With
+    --synthetic N the pairs are --height x --width (validation pairs too).
   * --resume [file]: continue from `file`, or without a value from `<model_dir><name>_best.pk` (the reference's rule: only if it exists)
 
 Differences from the reference's script: one process, no DataParallel; data in HBM like My_train.py (--synthetic N, --train_dir / --val_dir
@@ -63,6 +70,10 @@ def parse(argv=None):
     parser.add_argument('--deterministic', action='store_true',
                         help='bit-reproducible steps: fixed-order reductions instead of fp32 atomics (slower)')
     parser.add_argument('--log_every', type=int, default=10, help='host sync cadence for the progress line')
+    parser.add_argument('--whole_img', action='store_true',
+                        help="train on whole stored images, no crop: the reference's default setting (data_utils.py:21, crop_size = 'whole_img')")
+    parser.add_argument('--height', type=int, default=460, help='--whole_img --synthetic: image height (SOTS / ITS frames: 460)')
+    parser.add_argument('--width', type=int, default=620, help='--whole_img --synthetic: image width (SOTS / ITS frames: 620)')
     opt = parser.parse_args(argv)
     opt.model_name = 'My_NH' + '_' + opt.net.split('.')[0] + '_' + str(opt.gps) + '_' + str(opt.blocks)
     opt.model_path = opt.model_dir + opt.model_name          # option.py:38: a prefix, not a directory join
@@ -134,8 +145,9 @@ def main(argv=None):
     # ---- data (HBM resident)
     store = tgt_all = inp_all = None
     if opt.synthetic > 0:
-        tgt_all, inp_all = synthetic_batch(opt.synthetic, opt.crop_size, seed=1234, device=dev)
-        vt, vi = synthetic_batch(opt.val_synthetic, opt.crop_size, seed=4321, device=dev)
+        size = (opt.height, opt.width) if opt.whole_img else opt.crop_size
+        tgt_all, inp_all = synthetic_batch(opt.synthetic, size, seed=1234, device=dev)
+        vt, vi = synthetic_batch(opt.val_synthetic, size, seed=4321, device=dev)
     elif os.path.isdir(opt.train_dir):
         from dataset import DataLoaderVal, PatchStoreHBM
         store = PatchStoreHBM.from_dir(opt.train_dir, dev)
@@ -162,7 +174,7 @@ def main(argv=None):
                 g["lr"] = lr
         sel = torch.randint(n_train, (opt.bs,))          # main.py:84: a fresh shuffled batch every step
         if store is not None:
-            y, x = store.batch(sel.tolist(), opt.crop_size)
+            y, x = store.batch(sel.tolist(), None if opt.whole_img else opt.crop_size)
         else:
             y, x = tgt_all[sel.to(dev)], inp_all[sel.to(dev)]
         loss, _, _ = ffa_train_step(net, perloss, optimizer, None, x, y)

@@ -37,7 +37,52 @@ __global__ void crop_augment_pair_kernel(const uint8_t* __restrict__ gt, const u
     }
 }
 
+// The same feed for an h x w crop (whole images: h = Hs, w = Ws).  On h != w only the four maps that keep the shape exist - identity,
+// rot180, the two flips: k & 6 -; on h == w all eight, position for position the kernel above.
+__global__ void crop_augment_pair_rect_kernel(const uint8_t* __restrict__ gt, const uint8_t* __restrict__ hazy,
+                                              const int* __restrict__ table, float* __restrict__ out_gt,
+                                              float* __restrict__ out_hazy, int n, int Hs, int Ws, int h, int w) {
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t per = (size_t)h * w;
+    if (e >= (size_t)n * per) return;
+    const int item = (int)(e / per);
+    const int pix = (int)(e % per);
+    const int i = pix / w, j = pix % w, mi = h - 1, mj = w - 1;
+    const int id = table[item * 4 + 0], r = table[item * 4 + 1], c = table[item * 4 + 2];
+    const int k = table[item * 4 + 3] & (h == w ? 7 : 6);
+    int si, sj;                                     // source position inside the crop for output (i, j)
+    switch (k) {
+        case 0: si = i;      sj = j;      break;    // identity
+        case 1: si = mi - j; sj = i;      break;    // rot90(k=1, dims=[-1,-2])        (square crops only, mi == mj)
+        case 2: si = mi - i; sj = mj - j; break;    // rot90(k=2)
+        case 3: si = j;      sj = mj - i; break;    // rot90(k=3)                      (square)
+        case 4: si = mi - i; sj = j;      break;    // flip(-2)
+        case 5: si = mi - j; sj = mj - i; break;    // rot90(k=1).flip(-2)             (square)
+        case 6: si = i;      sj = mj - j; break;    // rot90(k=2).flip(-2)
+        default: si = j;     sj = i;      break;    // rot90(k=3).flip(-2)             (square)
+    }
+    const size_t src = (((size_t)id * Hs + r + si) * Ws + c + sj) * 3;
+    const size_t dst = (size_t)item * 3 * per + pix;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        out_gt[dst + ch * per] = (float)gt[src + ch] / 255.f;
+        out_hazy[dst + ch * per] = (float)hazy[src + ch] / 255.f;
+    }
+}
+
 }  // namespace
+
+extern "C" int dhz_crop_augment_pair_rect(const uint8_t* gt, const uint8_t* hazy, const int* table, float* out_gt, float* out_hazy,
+                                          int n, int Hs, int Ws, int h, int w, void* stream) {
+    DHZ_REQUIRE(gt && hazy && table && out_gt && out_hazy, "dhz_crop_augment_pair_rect: null pointer");
+    DHZ_REQUIRE(n > 0 && h > 0 && w > 0 && h <= Hs && w <= Ws, "dhz_crop_augment_pair_rect: bad sizes n=%d h=%d w=%d H=%d W=%d", n, h, w, Hs, Ws);
+    DHZ_REQUIRE((long long)n * h * w < (1ll << 31), "dhz_crop_augment_pair_rect: batch too large n=%d h=%d w=%d", n, h, w);
+    const size_t total = (size_t)n * h * w;
+    hipLaunchKernelGGL(crop_augment_pair_rect_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, gt,
+                       hazy, table, out_gt, out_hazy, n, Hs, Ws, h, w);
+    DHZ_CHECK_LAUNCH("dhz_crop_augment_pair_rect");
+    return DHZ_OK;
+}
 
 extern "C" int dhz_crop_augment_pair(const uint8_t* gt, const uint8_t* hazy, const int* table, float* out_gt,
                                      float* out_hazy, int n, int Hs, int Ws, int ps, void* stream) {

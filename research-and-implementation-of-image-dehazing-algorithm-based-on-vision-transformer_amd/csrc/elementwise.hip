@@ -578,6 +578,66 @@ __global__ __launch_bounds__(256) void l1_pair_bwd_kernel(const float* __restric
     }
 }
 
+// The two kernels above on ANY element count and 4-byte aligned pointers: a float4 body of n4 vectors that starts `head` elements in (where
+// the pointers reach a 16-byte boundary together), and the head + count - head - 4 n4 elements before and behind it one by one, spread over
+// the first threads of the grid.  With head = 0 and count = 4 n4 a thread adds what the kernel above adds, in its order: the same bits.
+template <bool DET>
+__global__ __launch_bounds__(256) void l1_pair_fwd_any_kernel(const float* __restrict__ a, const float* __restrict__ p,
+                                                              const float* __restrict__ n, float* __restrict__ sums, int64_t head,
+                                                              int64_t n4, int64_t count) {
+    __shared__ float part[2][4];
+    float sp = 0.f, sn = 0.f;
+    const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t e = t0; e < n4; e += step) {
+        const float4 av = reinterpret_cast<const float4*>(a + head)[e];
+        const float4 pv = reinterpret_cast<const float4*>(p + head)[e];
+        sp += fabsf(av.x - pv.x) + fabsf(av.y - pv.y) + fabsf(av.z - pv.z) + fabsf(av.w - pv.w);
+        if (n) {
+            const float4 nv = reinterpret_cast<const float4*>(n + head)[e];
+            sn += fabsf(av.x - nv.x) + fabsf(av.y - nv.y) + fabsf(av.z - nv.z) + fabsf(av.w - nv.w);
+        }
+    }
+    const int64_t singles = count - 4 * n4;                               // [0, head) and [head + 4 n4, count)
+    for (int64_t s = t0; s < singles; s += step) {
+        const int64_t i = s < head ? s : s + 4 * n4;
+        sp += fabsf(a[i] - p[i]);
+        if (n) sn += fabsf(a[i] - n[i]);
+    }
+    sp = wave_sum(sp); sn = wave_sum(sn);
+    if ((threadIdx.x & 63) == 0) { part[0][threadIdx.x >> 6] = sp; part[1][threadIdx.x >> 6] = sn; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float* o = sums + (DET ? 2 * blockIdx.x : 0);
+        dhz_accum<DET>(o, part[0][0] + part[0][1] + part[0][2] + part[0][3]);
+        if (n) dhz_accum<DET>(o + 1, part[1][0] + part[1][1] + part[1][2] + part[1][3]);
+    }
+}
+
+__global__ __launch_bounds__(256) void l1_pair_bwd_any_kernel(const float* __restrict__ a, const float* __restrict__ p,
+                                                              const float* __restrict__ n, const float* __restrict__ g, float inv_n,
+                                                              float* __restrict__ da, int64_t head, int64_t n4, int64_t count) {
+    const float cp = g[0] * inv_n, cn = n ? g[1] * inv_n : 0.f;
+    auto sgn = [](float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); };
+    const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t e = t0; e < n4; e += step) {
+        const float4 av = reinterpret_cast<const float4*>(a + head)[e];
+        const float4 pv = reinterpret_cast<const float4*>(p + head)[e];
+        float4 r = make_float4(cp * sgn(av.x - pv.x), cp * sgn(av.y - pv.y), cp * sgn(av.z - pv.z), cp * sgn(av.w - pv.w));
+        if (n) {
+            const float4 nv = reinterpret_cast<const float4*>(n + head)[e];
+            r.x += cn * sgn(av.x - nv.x); r.y += cn * sgn(av.y - nv.y); r.z += cn * sgn(av.z - nv.z); r.w += cn * sgn(av.w - nv.w);
+        }
+        reinterpret_cast<float4*>(da + head)[e] = r;
+    }
+    const int64_t singles = count - 4 * n4;
+    for (int64_t s = t0; s < singles; s += step) {
+        const int64_t i = s < head ? s : s + 4 * n4;
+        float r = cp * sgn(a[i] - p[i]);
+        if (n) r += cn * sgn(a[i] - n[i]);
+        da[i] = r;
+    }
+}
+
 
 // The scalar side of ContrastLoss.forward (My_CR.py:104-123) over the k taps, one launch each way instead of a dozen [k]-vector
 // torch ops: means d_i = sums_i / count_i;  loss = sum_i w_i ap_i / (an_i + 1e-7)  (ablation: sum_i w_i ap_i), all_ap, all_an;
@@ -1081,5 +1141,56 @@ extern "C" int dhz_l1_pair_bwd(const float* a, const float* p, const float* n, c
     hipLaunchKernelGGL(l1_pair_bwd_kernel, dim3(grid_for(count / 4)), dim3(256), 0, (hipStream_t)stream, a, p, n, g,
                        1.0f / (float)count, da, count / 4);
     DHZ_CHECK_LAUNCH("dhz_l1_pair_bwd");
+    return DHZ_OK;
+}
+
+// The cut of `count` elements into head | float4 body | tail for the `_any` entries: the body starts where `first` reaches a 16-byte boundary,
+// provided every other pointer reaches one at the same element; pointers that do not agree modulo 16 bytes leave no body (all singles).
+static void l1_any_cut(const void* first, const void* const* others, int nothers, int64_t count, int64_t* head, int64_t* n4) {
+    const uintptr_t r = (uintptr_t)first & 15;
+    bool together = true;
+    for (int i = 0; i < nothers; ++i)
+        if (others[i] && ((uintptr_t)others[i] & 15) != r) together = false;
+    int64_t h = together ? (int64_t)(((16 - r) & 15) / 4) : count;
+    if (h > count) h = count;
+    *head = h;
+    *n4 = (count - h) / 4;
+}
+
+static bool l1_aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
+
+extern "C" int dhz_l1_pair_fwd_any(const float* a, const float* p, const float* n, float* sums, int64_t count, void* stream) {
+    DHZ_REQUIRE(a && p && sums, "dhz_l1_pair_fwd_any: null pointer");
+    DHZ_REQUIRE(count > 0, "dhz_l1_pair_fwd_any: bad arguments (count must be positive)");
+    DHZ_REQUIRE(l1_aligned4(a) && l1_aligned4(p) && l1_aligned4(n), "dhz_l1_pair_fwd_any: a, p and n must be 4-byte aligned");
+    int64_t head, n4;
+    const void* others[2] = {p, n};
+    l1_any_cut(a, others, 2, count, &head, &n4);
+    const int grid = grid_for(n4 + (count - 4 * n4 + 3) / 4, 256, 768);       // a function of count and of the pointers' alignment: count / 4 where the entry above applies
+    if (dhz_det()) {                                      // one item per workgroup
+        float* ws = dhz_det_ws("dhz_l1_pair_fwd_any", grid, 2);
+        if (!ws) return DHZ_EINVAL;
+        hipLaunchKernelGGL(l1_pair_fwd_any_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a, p, n, ws, head, n4, count);
+        DHZ_CHECK_LAUNCH("dhz_l1_pair_fwd_any");
+        DetSegs segs{};
+        segs.n = 1; segs.off[0] = 0; segs.len[0] = n ? 2 : 1; segs.dst[0] = sums;
+        return dhz_det_reduce("dhz_l1_pair_fwd_any", ws, grid, 2, segs, (hipStream_t)stream);
+    }
+    hipLaunchKernelGGL(l1_pair_fwd_any_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a, p, n, sums, head, n4, count);
+    DHZ_CHECK_LAUNCH("dhz_l1_pair_fwd_any");
+    return DHZ_OK;
+}
+
+extern "C" int dhz_l1_pair_bwd_any(const float* a, const float* p, const float* n, const float* g, float* da, int64_t count,
+                                   void* stream) {
+    DHZ_REQUIRE(a && p && g && da, "dhz_l1_pair_bwd_any: null pointer");
+    DHZ_REQUIRE(count > 0, "dhz_l1_pair_bwd_any: bad arguments (count must be positive)");
+    DHZ_REQUIRE(l1_aligned4(a) && l1_aligned4(p) && l1_aligned4(n) && l1_aligned4(da), "dhz_l1_pair_bwd_any: a, p, n and da must be 4-byte aligned");
+    int64_t head, n4;
+    const void* others[3] = {p, n, da};
+    l1_any_cut(a, others, 3, count, &head, &n4);
+    hipLaunchKernelGGL(l1_pair_bwd_any_kernel, dim3(grid_for(n4 + (count - 4 * n4 + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a, p, n, g,
+                       1.0f / (float)count, da, head, n4, count);
+    DHZ_CHECK_LAUNCH("dhz_l1_pair_bwd_any");
     return DHZ_OK;
 }

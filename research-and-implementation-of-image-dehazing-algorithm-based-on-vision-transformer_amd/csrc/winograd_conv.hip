@@ -598,6 +598,85 @@ __global__ void maxpool2x2_blocked_bwd_kernel(const float4* __restrict__ gy, con
     gx[o] = ra; gx[o + 2] = rb; gx[o + 2 * W] = rc; gx[o + 2 * W + 2] = rd;
 }
 
+// The same pooling on maps of ANY size, floor mode (nn.MaxPool2d(2, 2)): Ho = H / 2, Wo = W / 2, an odd last row or column feeds no window.
+// Forward: the thread layout of the kernel above, rows of the source W (not 2 Wo) float4 pairs apart.
+__global__ void maxpool2x2_blocked_fwd_any_kernel(const float4* __restrict__ x, float4* __restrict__ y, size_t total, int H, int W) {
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;     // over [n][ho][wo][2 halves]
+    if (e >= total) return;
+    const int Ho = H / 2, Wo = W / 2;
+    const int hf = e & 1;
+    const size_t p = e >> 1;
+    const int wo = p % Wo;
+    const size_t r = p / Wo;
+    const int ho = r % Ho;
+    const size_t n = r / Ho;
+    const float4* src = x + ((n * H + 2 * ho) * W + 2 * wo) * 2 + hf;
+    const float4 a = src[0], b = src[2], c = src[2 * W], d = src[2 * W + 2];
+    float4 m;
+    m.x = fmaxf(fmaxf(a.x, b.x), fmaxf(c.x, d.x)); m.y = fmaxf(fmaxf(a.y, b.y), fmaxf(c.y, d.y));
+    m.z = fmaxf(fmaxf(a.z, b.z), fmaxf(c.z, d.z)); m.w = fmaxf(fmaxf(a.w, b.w), fmaxf(c.w, d.w));
+    y[e] = m;
+}
+
+// Backward on any size: one thread = 4 channels of one CELL of the ceil(H / 2) x ceil(W / 2) grid of 2 x 2 cells that covers the whole
+// un-pooled map, so every element of gx is written by exactly one thread.  A cell inside the pooled map (hc < Ho and wc < Wo) is a window:
+// the routing of the kernels above (ADD: + the tap's own gradient, csrc/perceptual.hip), expression for expression.  A cell on the dropped
+// odd row or column holds one or two positions that no window read: gx = 0 there, or with ADD the tap's gradient through the ReLU alone.
+template <bool ADD>
+__global__ __launch_bounds__(256) void maxpool2x2_blocked_bwd_any_kernel(const float4* __restrict__ gy, const float4* __restrict__ act,
+                                                                         const float4* __restrict__ add, float4* __restrict__ gx,
+                                                                         size_t total, int H, int W) {
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;     // over [n][hc][wc][2 halves]
+    if (e >= total) return;
+    const int Ho = H / 2, Wo = W / 2, Hc = (H + 1) / 2, Wc = (W + 1) / 2;
+    const int hf = e & 1;
+    const size_t p = e >> 1;
+    const int wc = p % Wc;
+    const size_t r = p / Wc;
+    const int hc = r % Hc;
+    const size_t n = r / Hc;
+    const size_t o = ((n * H + 2 * hc) * W + 2 * wc) * 2 + hf;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (hc < Ho && wc < Wo) {
+        const float4 a = act[o], b = act[o + 2], c = act[o + 2 * W], d = act[o + 2 * W + 2];
+        float4 ta = zero, tb = zero, tc = zero, td = zero;
+        if (ADD) { ta = add[o]; tb = add[o + 2]; tc = add[o + 2 * W]; td = add[o + 2 * W + 2]; }
+        const float4 g = gy[((n * Ho + hc) * Wo + wc) * 2 + hf];
+        float4 ra, rb, rc, rd;
+#define ROUTE(f)                                                                              \
+    {                                                                                         \
+        const float m = fmaxf(fmaxf(a.f, b.f), fmaxf(c.f, d.f));                              \
+        const float gv = m > 0.f ? g.f : 0.f;                                                 \
+        const bool ia = a.f == m, ib = !ia && b.f == m, ic = !ia && !ib && c.f == m;          \
+        ra.f = ia ? gv : 0.f; rb.f = ib ? gv : 0.f; rc.f = ic ? gv : 0.f;                     \
+        rd.f = (!ia && !ib && !ic) ? gv : 0.f;                                                \
+        if (ADD) {                                                                            \
+            ra.f = ra.f + (a.f > 0.f ? ta.f : 0.f); rb.f = rb.f + (b.f > 0.f ? tb.f : 0.f);   \
+            rc.f = rc.f + (c.f > 0.f ? tc.f : 0.f); rd.f = rd.f + (d.f > 0.f ? td.f : 0.f);   \
+        }                                                                                     \
+    }
+        ROUTE(x) ROUTE(y) ROUTE(z) ROUTE(w)
+#undef ROUTE
+        gx[o] = ra; gx[o + 2] = rb; gx[o + 2 * W] = rc; gx[o + 2 * W + 2] = rd;
+        return;
+    }
+    // the dropped row (hc == Ho: one map row, H odd) and / or column (wc == Wo: one map column, W odd): the positions of this cell inside the map
+    const bool two_rows = 2 * hc + 1 < H, two_cols = 2 * wc + 1 < W;
+#define EDGE(off)                                                                             \
+    {                                                                                         \
+        float4 rr = zero;                                                                     \
+        if (ADD) {                                                                            \
+            const float4 a = act[off], t = add[off];                                          \
+            rr = make_float4(a.x > 0.f ? t.x : 0.f, a.y > 0.f ? t.y : 0.f, a.z > 0.f ? t.z : 0.f, a.w > 0.f ? t.w : 0.f); \
+        }                                                                                     \
+        gx[off] = rr;                                                                         \
+    }
+    EDGE(o)
+    if (two_cols) EDGE(o + 2)
+    if (two_rows) EDGE(o + 2 * W)
+#undef EDGE
+}
+
 }  // namespace
 
 extern "C" int dhz_winograd_prepack(const float* weight, float* upack, int Kout, int Cin, int transposed_rot,
@@ -820,5 +899,53 @@ extern "C" int dhz_maxpool2x2_blocked_bwd(const float* gy, const float* act, flo
                        reinterpret_cast<const float4*>(gy), reinterpret_cast<const float4*>(act), reinterpret_cast<float4*>(gx),
                        total, H / 2, W / 2);
     DHZ_CHECK_LAUNCH("dhz_maxpool2x2_blocked_bwd");
+    return DHZ_OK;
+}
+
+// The three pooling entries on maps of any size (floor mode; see the kernels).  `who` names the entry in its messages.
+static int maxpool_any_check(const char* who, int N, int H, int W) {
+    DHZ_REQUIRE(N > 0 && H >= 2 && W >= 2, "%s: bad arguments N=%d H=%d W=%d (N > 0 and H, W >= 2)", who, N, H, W);
+    // one thread per float4 pair position of the un-pooled map at the most: the grid stays below 2^31 workgroups
+    DHZ_REQUIRE((long long)N * ((H + 1) / 2) * ((W + 1) / 2) < (1ll << 37), "%s: map too large N=%d H=%d W=%d", who, N, H, W);
+    return DHZ_OK;
+}
+
+static inline bool pool_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+extern "C" int dhz_maxpool2x2_blocked_fwd_any(const float* x, float* y, int N, int H, int W, void* stream) {
+    DHZ_REQUIRE(x && y, "dhz_maxpool2x2_blocked_fwd_any: null pointer");
+    if (int rc = maxpool_any_check("dhz_maxpool2x2_blocked_fwd_any", N, H, W)) return rc;
+    DHZ_REQUIRE(pool_aligned16(x) && pool_aligned16(y), "dhz_maxpool2x2_blocked_fwd_any: the maps must be 16-byte aligned");
+    const size_t total = (size_t)N * (H / 2) * (W / 2) * 2;
+    hipLaunchKernelGGL(maxpool2x2_blocked_fwd_any_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const float4*>(x), reinterpret_cast<float4*>(y), total, H, W);
+    DHZ_CHECK_LAUNCH("dhz_maxpool2x2_blocked_fwd_any");
+    return DHZ_OK;
+}
+
+extern "C" int dhz_maxpool2x2_blocked_bwd_any(const float* gy, const float* act, float* gx, int N, int H, int W, void* stream) {
+    DHZ_REQUIRE(gy && act && gx, "dhz_maxpool2x2_blocked_bwd_any: null pointer");
+    if (int rc = maxpool_any_check("dhz_maxpool2x2_blocked_bwd_any", N, H, W)) return rc;
+    DHZ_REQUIRE(pool_aligned16(gy) && pool_aligned16(act) && pool_aligned16(gx),
+                "dhz_maxpool2x2_blocked_bwd_any: the maps must be 16-byte aligned");
+    const size_t total = (size_t)N * ((H + 1) / 2) * ((W + 1) / 2) * 2;
+    hipLaunchKernelGGL(maxpool2x2_blocked_bwd_any_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const float4*>(gy), reinterpret_cast<const float4*>(act), nullptr,
+                       reinterpret_cast<float4*>(gx), total, H, W);
+    DHZ_CHECK_LAUNCH("dhz_maxpool2x2_blocked_bwd_any");
+    return DHZ_OK;
+}
+
+extern "C" int dhz_maxpool2x2_blocked_bwd_add_any(const float* gy, const float* act, const float* addend, float* gx, int N, int H, int W,
+                                                  void* stream) {
+    DHZ_REQUIRE(gy && act && addend && gx, "dhz_maxpool2x2_blocked_bwd_add_any: null pointer");
+    if (int rc = maxpool_any_check("dhz_maxpool2x2_blocked_bwd_add_any", N, H, W)) return rc;
+    DHZ_REQUIRE(pool_aligned16(gy) && pool_aligned16(act) && pool_aligned16(addend) && pool_aligned16(gx),
+                "dhz_maxpool2x2_blocked_bwd_add_any: the maps must be 16-byte aligned");
+    const size_t total = (size_t)N * ((H + 1) / 2) * ((W + 1) / 2) * 2;
+    hipLaunchKernelGGL(maxpool2x2_blocked_bwd_any_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const float4*>(gy), reinterpret_cast<const float4*>(act), reinterpret_cast<const float4*>(addend),
+                       reinterpret_cast<float4*>(gx), total, H, W);
+    DHZ_CHECK_LAUNCH("dhz_maxpool2x2_blocked_bwd_add_any");
     return DHZ_OK;
 }

@@ -39,6 +39,20 @@ def draw_crop_aug(H, W, ps):
     return r, c, random.getrandbits(3)
 
 
+def draw_rect_aug(H, W, h, w):
+    """(r, c, k) for an h x w crop of an H x W image.  h == w: draw_crop_aug itself.  h != w: the same number of draws - none for the
+    whole image, else one per axis, an axis without room drawing from [0, 1) - and the augmentation masked to the four maps that keep
+    the shape (k & 6: 0 identity, 2 rot180, 4 flip(-2), 6 flip(-1))."""
+    if h == w:
+        return draw_crop_aug(H, W, h)
+    if H == h and W == w:
+        r, c = 0, 0
+    else:
+        r = np.random.randint(0, max(H - h, 1))
+        c = np.random.randint(0, max(W - w, 1))
+    return r, c, random.getrandbits(3) & 6
+
+
 def _chw(path):
     """One PNG as float32 CHW in [0, 1] (the reference's load_img + permute)."""
     return torch.from_numpy(np.float32(load_img(path))).permute(2, 0, 1)
@@ -145,19 +159,37 @@ class PatchStoreHBM:
 
     def batch(self, indices, ps):
         """indices: iterable of patch ids.  Returns (clean, noisy) float32 [n,3,ps,ps] on the device; per item the crop
-        origin and the augmentation are drawn like DataLoaderTrain.__getitem__ does, in item order."""
+        origin and the augmentation are drawn like DataLoaderTrain.__getitem__ does, in item order.
+
+        ps may also be (h, w) - an h x w crop, [n,3,h,w] - or None: the stored size, i.e. whole images (FFA_main.py --whole_img).  These go
+        through dhz_crop_augment_pair_rect; an int keeps the square entry.  The table is drawn by draw_rect_aug: for h == w exactly
+        draw_crop_aug's draws (the batch then equals batch(indices, h) bit for bit), for h != w the same number of draws with the
+        augmentation masked to k & 6 - identity, rot180 and the two flips, the four of the eight maps that keep an h x w shape.  The
+        reference (FFA_model/data_utils.py:69-77, FF.rotate) rotates the PIL images by 90 degrees WITHOUT expanding the canvas, so its non-square
+        frames come out with black corners and cut-off ends; that artefact is deliberately not restated here."""
         from dehaze_hip import _lib
         from dehaze_hip.ops import _p, _stream
+        rect = not isinstance(ps, int)
+        if rect:
+            h, w = (self.H, self.W) if ps is None else (int(ps[0]), int(ps[1]))
+            if not (0 < h <= self.H and 0 < w <= self.W):
+                raise ValueError(f"PatchStoreHBM.batch: a {h} x {w} crop does not fit the stored {self.H} x {self.W} images")
         idx = [int(i) % self.N for i in indices]
         n = len(idx)
         tab = torch.empty((n, 4), dtype=torch.int32)
         if self.device.type == "cuda":
             tab = tab.pin_memory()
         for j, i in enumerate(idx):
-            r, c, k = draw_crop_aug(self.H, self.W, ps)
+            r, c, k = draw_rect_aug(self.H, self.W, h, w) if rect else draw_crop_aug(self.H, self.W, ps)
             tab[j, 0], tab[j, 1], tab[j, 2], tab[j, 3] = i, r, c, k
         self._table = tab                                       # keep the pinned buffer alive until the copy ran
         tab_d = tab.to(self.device, non_blocking=True)
+        if rect:
+            clean = torch.empty((n, 3, h, w), device=self.device, dtype=torch.float32)
+            noisy = torch.empty_like(clean)
+            _lib.call("dhz_crop_augment_pair_rect", self.gt.data_ptr(), self.hazy.data_ptr(), tab_d.data_ptr(), _p(clean), _p(noisy),
+                      n, self.H, self.W, h, w, _stream())
+            return clean, noisy
         clean = torch.empty((n, 3, ps, ps), device=self.device, dtype=torch.float32)
         noisy = torch.empty_like(clean)
         _lib.call("dhz_crop_augment_pair", self.gt.data_ptr(), self.hazy.data_ptr(), tab_d.data_ptr(), _p(clean), _p(noisy),

@@ -199,6 +199,13 @@ SIGNATURES = {
     "dhz_mse_pair_fwd": [c_f, c_f, c_f, c_l, c_p],
     "dhz_mse_pair_bwd": [c_f, c_f, c_f, c_f, c_l, c_i, c_p],
     "dhz_maxpool2x2_blocked_bwd_add": [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_p],
+    # whole images: the poolings and the L1 mean on any size, the feed for h x w crops
+    "dhz_maxpool2x2_blocked_fwd_any": [c_f, c_f, c_i, c_i, c_i, c_p],
+    "dhz_maxpool2x2_blocked_bwd_any": [c_f, c_f, c_f, c_i, c_i, c_i, c_p],
+    "dhz_maxpool2x2_blocked_bwd_add_any": [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_p],
+    "dhz_l1_pair_fwd_any": [c_f, c_f, c_f, c_f, c_l, c_p],
+    "dhz_l1_pair_bwd_any": [c_f, c_f, c_f, c_f, c_f, c_l, c_p],
+    "dhz_crop_augment_pair_rect": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_p],
 }
 _RESTYPE = {"dhz_last_error": ctypes.c_char_p, "dhz_build_id": ctypes.c_char_p, "dhz_conv3x3_wgrad_workspace_bytes": ctypes.c_size_t,
             "dhz_ffa_workspace_bytes": ctypes.c_size_t, "dhz_conv3x3_wgrad_workspace_bytes_any": ctypes.c_size_t,

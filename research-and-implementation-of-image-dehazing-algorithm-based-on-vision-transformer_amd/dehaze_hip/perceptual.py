@@ -2,7 +2,9 @@
 taps of vgg16().features[:16] - relu1_2, relu2_2, relu3_3 - of the MSE between the features of the dehazed image and of the ground
 truth.  No ImageNet normalisation (the reference applies none).
 
-On a HIP device, with frozen filters and an fp32 image whose sides are multiples of 16 and at least 32 (vgg.engine16_shape_ok), the
+On a HIP device, with frozen filters and an fp32 image whose sides are at least 32 - multiples of 16 (vgg.engine16_shape_ok) or, for whole
+images (the reference's default: FFA_model/data_utils.py:21), any other size (vgg.engine16_any_shape_ok; ragged Winograd blocks and
+floor-mode poolings whose backward writes the dropped odd row / column too; DHZ_PERLOSS_ANY=0 / perceptual.ANY = False: off) -, the
 stack runs on the Winograd engine of dehaze_hip/vgg.py built as VggEngine(7 convolutions, pool_after (1, 3), taps (1, 3, 6)): one
 no-gradient pass for the ground truth, one differentiated pass for the dehazed image, features channel-blocked throughout, the three
 squared-error sums into one zeroed 3-float buffer (dhz_mse_pair_fwd) and ONE autograd node whose backward is three dhz_mse_pair_bwd
@@ -26,6 +28,9 @@ POOL_AFTER16 = (1, 3)
 TAPS16 = (1, 3, 6)                               # relu1_2, relu2_2, relu3_3 = features[3], [8], [15]
 TAP_LAYERS = {3: "relu1_2", 8: "relu2_2", 15: "relu3_3"}
 VGG16_SEED = 1606
+# A/B switch: image sizes that are no multiples of 16 (sides from 32 up) on the engine - its `_any` convolutions and floor-mode poolings -, and
+# the image-space L1 of ffa_train_step on any element count (off: such sizes on the library path, with the warning)
+ANY = os.environ.get("DHZ_PERLOSS_ANY", "1") != "0"
 
 
 def vgg16_feature_layers():
@@ -153,8 +158,8 @@ class LossNetwork(nn.Module):
                 or self.vgg_layers[0].weight.device != x.device or self.vgg_layers[0].weight.dtype != torch.float32:
             return None
         from . import ops
-        from .vgg import VggEngine, engine16_shape_ok
-        if not engine16_shape_ok(x.shape[2], x.shape[3]):
+        from .vgg import VggEngine, engine16_any_shape_ok, engine16_shape_ok
+        if not (engine16_shape_ok(x.shape[2], x.shape[3]) or (ANY and engine16_any_shape_ok(x.shape[2], x.shape[3]))):
             ops.warn_library_fallback("PerLoss VGG16", (3, x.shape[2], x.shape[3]))
             return None
         if self._engine is None:

@@ -541,7 +541,7 @@ def lr_schedule_cosdecay(t, T, init_lr):
 def ffa_train_step(model, perloss, optimizer, reducer, input_, target, w_per=0.04):
     """One step of FFA-Net's own recipe (FFA_model/main.py:84-96): out = model(x); loss = L1(out, y), unclamped, + w_per * perloss(out, y)
     when `perloss` (PerceptualLoss.LossNetwork) is given; backward; Adam (FlatAdamW with weight_decay 0).  The L1 mean runs on
-    dhz_l1_pair_fwd / _bwd with n = NULL (vgg.l1_pair).  Returns (loss, loss_l1, loss_per) as device scalars - no host sync here."""
+    dhz_l1_pair_fwd / _bwd with n = NULL (vgg.l1_pair; dhz_l1_pair_fwd_any / _bwd_any where 3 B H W is no multiple of 4).  Returns (loss, loss_l1, loss_per) as device scalars - no host sync here."""
     if getattr(model, "act_dtype", None) == torch.bfloat16 or input_.dtype != torch.float32 \
             or any(p.dtype != torch.float32 for p in model.parameters()):
         raise NotImplementedError("ffa_train_step: fp32 only (the squared-error taps and the VGG16 engine have no bf16 form)")
@@ -552,7 +552,9 @@ def ffa_train_step(model, perloss, optimizer, reducer, input_, target, w_per=0.0
     else:
         optimizer.zero_grad()
     out = model(input_)
-    if out.numel() % 4 == 0 and out.is_cuda:
+    from . import perceptual
+    # any element count with perceptual.ANY (a whole image such as 3 x 413 x 550: dhz_l1_pair_*_any); multiples of 4 as ever
+    if (out.numel() % 4 == 0 or perceptual.ANY) and out.is_cuda:
         loss_l1 = l1_pair(out, target)[0]
     else:
         loss_l1 = torch.nn.functional.l1_loss(out, target)

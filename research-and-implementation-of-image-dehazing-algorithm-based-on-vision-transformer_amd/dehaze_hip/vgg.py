@@ -20,7 +20,9 @@ load) - weight gradients are never formed (the reference freezes the VGG, My_CR.
 The stack is a parameter of the engine: VggEngine(convs, pool_after, taps).  The defaults are VGG19[:30] with the five taps above; the
 perceptual loss of FFA-Net's recipe (dehaze_hip/perceptual.py) builds the 7 convolutions of VGG16[:16] with pool_after (1, 3) and taps
 (1, 3, 6).  There two taps are pooled as well: their un-pooled maps are always written, and in the backward the tap's gradient joins
-the pooled one on the un-pooled map in one launch (dhz_maxpool2x2_blocked_bwd_add, csrc/perceptual.hip).
+the pooled one on the un-pooled map in one launch (dhz_maxpool2x2_blocked_bwd_add, csrc/perceptual.hip).  That stack also takes whole
+images of any size from 32 x 32 up (engine16_any_shape_ok): a map with an odd side is pooled in floor mode by the `_any` pooling entries
+(csrc/winograd_conv.hip), whose backward writes the dropped row / column too; even maps keep the launches they always had.
 """
 import os
 
@@ -48,6 +50,13 @@ def engine16_shape_ok(H, W):
     """Image sizes the VGG16[:16] stack of the perceptual loss takes (dehaze_hip/perceptual.py): two poolings only, so sides that are multiples
     of 16 and at least 32 - the last maps are then 8 x 8 and larger (FFA's own blocked path asks for multiples of 16 too)."""
     return H % 16 == 0 and W % 16 == 0 and H >= 32 and W >= 32
+
+
+def engine16_any_shape_ok(H, W):
+    """Whole images (FFA_model/data_utils.py:21): the VGG16[:16] stack on any H x W with both sides at least 32.  The convolutions take any map
+    (dhz_conv3x3_in3_blocked, dhz_winograd_conv3x3_any, dhz_thin_conv3x3_dgrad_blocked), the two poolings run in floor mode on odd maps
+    (dhz_maxpool2x2_blocked_*_any).  The floor is engine16_shape_ok's: the last maps are 8 x 8 and larger."""
+    return H >= 32 and W >= 32
 
 
 def _fixed_tiling(H, W):
@@ -81,10 +90,15 @@ def to_plain(xb):
     return out
 
 
+def _pool_sfx(H, W):
+    """an odd side: the `_any` pooling entries (floor mode, the dropped row / column written too); even maps keep the entries they always ran"""
+    return "_any" if (H % 2 or W % 2) else ""
+
+
 def pool_fwd(xb):
     B, CG, H, W, _ = xb.shape
     yb = torch.empty((B, CG, H // 2, W // 2, 8), device=xb.device, dtype=torch.float32)
-    _lib.call("dhz_maxpool2x2_blocked_fwd", _p(xb), _p(yb), B * CG, H, W, _stream())
+    _lib.call("dhz_maxpool2x2_blocked_fwd" + _pool_sfx(H, W), _p(xb), _p(yb), B * CG, H, W, _stream())
     return yb
 
 
@@ -92,7 +106,7 @@ def pool_bwd_relu(gb, actb):
     """gradient w.r.t. the pre-activation below the post-ReLU map `actb` whose 2x2 max pooling received gradient gb."""
     B, CG, H, W, _ = actb.shape
     gx = torch.empty_like(actb)
-    _lib.call("dhz_maxpool2x2_blocked_bwd", _p(gb.contiguous()), _p(actb), _p(gx), B * CG, H, W, _stream())
+    _lib.call("dhz_maxpool2x2_blocked_bwd" + _pool_sfx(H, W), _p(gb.contiguous()), _p(actb), _p(gx), B * CG, H, W, _stream())
     return gx
 
 
@@ -100,7 +114,8 @@ def pool_bwd_relu_add(gb, actb, addb):
     """pool_bwd_relu for a map that is a loss tap as well: + the tap's own gradient addb, both through the ReLU (actb > 0), in one launch."""
     B, CG, H, W, _ = actb.shape
     gx = torch.empty_like(actb)
-    _lib.call("dhz_maxpool2x2_blocked_bwd_add", _p(gb.contiguous()), _p(actb), _p(addb.contiguous()), _p(gx), B * CG, H, W, _stream())
+    _lib.call("dhz_maxpool2x2_blocked_bwd_add" + _pool_sfx(H, W), _p(gb.contiguous()), _p(actb), _p(addb.contiguous()), _p(gx), B * CG, H, W,
+              _stream())
     return gx
 
 
@@ -545,6 +560,14 @@ def _sfx(t):
     return ""
 
 
+def _l1_sfx(t):
+    """_sfx for l1_pair: an fp32 tensor whose element count is no multiple of 4 (the image-space L1 of FFA-Net's recipe on whole images, e.g.
+    3 x 413 x 550) takes dhz_l1_pair_*_any; every other tensor the entry it always took"""
+    if t.dtype != torch.bfloat16 and t.numel() % 4:
+        return "_any"
+    return _sfx(t)
+
+
 class _L1Pair(Function):
     """(mean|a - p|, mean|a - n|) of one feature tap in one pass; gradient w.r.t. a only (p, n carry none, My_CR.py:102)."""
 
@@ -555,7 +578,7 @@ class _L1Pair(Function):
         sums = torch.zeros(2, device=a.device, dtype=torch.float32)
         if a.dtype == torch.bfloat16:
             ops._refuse_bf16_deterministic("contrast sums")
-        _lib.call("dhz_l1_pair_fwd" + _sfx(a), _p(a), _p(p), _p(n) if n is not None else None, _p(sums), a.numel(), _stream())
+        _lib.call("dhz_l1_pair_fwd" + _l1_sfx(a), _p(a), _p(p), _p(n) if n is not None else None, _p(sums), a.numel(), _stream())
         ctx.save_for_backward(a, p, n) if n is not None else ctx.save_for_backward(a, p)
         ctx.has_n = n is not None
         return sums / a.numel()
@@ -566,7 +589,7 @@ class _L1Pair(Function):
         a, p = saved[0], saved[1]
         n = saved[2] if ctx.has_n else None
         da = torch.empty_like(a)
-        _lib.call("dhz_l1_pair_bwd" + _sfx(a), _p(a), _p(p), _p(n) if n is not None else None, _p(g.contiguous()), _p(da),
+        _lib.call("dhz_l1_pair_bwd" + _l1_sfx(a), _p(a), _p(p), _p(n) if n is not None else None, _p(g.contiguous()), _p(da),
                   a.numel(), _stream())
         return da, None, None
 
