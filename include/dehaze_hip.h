@@ -905,6 +905,38 @@ int dhz_ffa_add(const float* a, const float* x, float* y, int64_t n, void* strea
 int dhz_ffa_add_any(const float* a, const float* x, float* y, int64_t n, void* stream);
 int dhz_ffa_relu_bwd_add(const float* a1, const float* dr, const float* dout, float* dpre1, float* s, int64_t n, void* stream);
 
+/* K14  SSIM and squared error of image pairs, scored in float64 (csrc/metrics.hip): the validation metrics of FFA-Net's recipe
+ *      (M = FFA_model/metrics.py; FFA_model/main.py:151-173 scores every validation image with them) and of utils/metrics.py (U, the
+ *      scikit-image form test_long_GPU.py:94-98 uses), from one kernel.  a, b: fp32 planes, plane (i, c) of `a` starts at
+ *      a + i a_img_stride + c a_ch_stride (elements, >= 0), its rows are W floats apart; only 4-byte alignment is assumed (image 1 of a
+ *      stacked batch may start anywhere).  With clamp01 != 0 both inputs are clamped to [0, 1] on load (M:51-52, M:62-63).  Per plane, with
+ *      x, y the (clamped) inputs as doubles and w = `window` (K x K fp32 weights, row-major, on the device), all arithmetic in double:
+ *        mx = wscale sum w x,  my = wscale sum w y,  mxx = wscale sum w x x,  myy = wscale sum w y y,  mxy = wscale sum w x y      (M:32-39, U:38-41)
+ *        vx = cov_norm (mxx - mx mx),  vy = cov_norm (myy - my my),  vxy = cov_norm (mxy - mx my)                                    (M:37-39, U:42)
+ *        S  = ((2 mx my + C1)(2 vxy + C2)) / ((mx mx + my my + C1)(vx + vy + C2))                                                    (M:42,    U:44)
+ *      valid == 0, the zero-padded rule: S on all H x W pixels, window centred, taps outside the plane contribute 0 (M:32: padding =
+ *        window_size // 2); any H, W >= 1, planes smaller than the window included.
+ *      valid == 1: S on the (H - K + 1) x (W - K + 1) pixels whose window lies inside the plane (U:45-46: what is left after the border
+ *        crop, which uniform_filter's reflection never reaches); needs H, W >= K.
+ *      ssim_sum[i C + c] = sum of S over that extent (the caller divides by its pixel count: M:45, M:47, U:46);
+ *      sqerr_sum[i C + c] = sum over all H x W pixels of (x - y)^2, the subtraction and the square in fp32 as both host routes form them
+ *        (M:64-65, U:30), added in double.  Both are WRITTEN.
+ *      M is K = 11, window = create_window's fp32 outer product (M:25-26: not separable to the last bit, hence a table), wscale = 1,
+ *        valid = 0, C1 = 0.01^2, C2 = 0.03^2 (M:40-41), cov_norm = 1, clamp01 = 1.
+ *      U is K = 7, window = 49 ones, wscale = 1 / 49 (a double: the fp32 value of 1 / 49 is 4.6e-8 off, which 1 / C2 would amplify),
+ *        valid = 1, C1 = (0.01 R)^2, C2 = (0.03 R)^2 with R = data_range (U:43), cov_norm = 49 / 48 (U:36-37), clamp01 = 0.
+ *      Cuts: bands of 32 columns x 64 rows, one workgroup and one pair of double partial sums in ws each; a second launch adds a plane's
+ *      pairs in ascending band order, one owner thread per result.  No atomics; every cut is a function of the shapes: the same bits from
+ *      run to run, under any dhz_set_reserved_cus, with the deterministic mode on or off (the mode's workspace is not used).
+ *      ws: dhz_ssim_pair_workspace_bytes(B, C, H, W) bytes (0 for an unsupported shape), 8-byte aligned like ssim_sum and sqerr_sum.
+ *      Anything else - a null pointer, K outside {7, 11}, B, C, H or W < 1 (or B C > 65535, H > 4194240, H W >= 2^31), H or W < K under the
+ *      valid rule, a border rule outside {0, 1}, a negative stride, a missing, too small or misaligned workspace - is DHZ_EINVAL before
+ *      any launch. */
+size_t dhz_ssim_pair_workspace_bytes(int B, int C, int H, int W);
+int dhz_ssim_pair(double* ssim_sum, double* sqerr_sum, const float* a, int64_t a_img_stride, int64_t a_ch_stride, const float* b,
+                  int64_t b_img_stride, int64_t b_ch_stride, int B, int C, int H, int W, int K, const float* window, double wscale,
+                  int valid, double C1, double C2, double cov_norm, int clamp01, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

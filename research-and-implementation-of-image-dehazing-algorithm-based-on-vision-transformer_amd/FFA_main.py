@@ -5,7 +5,8 @@ trains its FFA baseline with, as opposed to My_train.py --arch FFA, which trains
   * loss = L1(out, y) [+ 0.04 * PerLoss(out, y) with --perloss: VGG16 relu1_2 / relu2_2 / relu3_3 MSE, PerceptualLoss.py], out unclamped
   * Adam, lr 1e-4, betas (0.9, 0.999), eps 1e-8 - FlatAdamW with weight_decay 0 is that update, in one launch
   * per-step cosine decay lr = 0.5 (1 + cos(t pi / T)) lr0 (--no_lr_sche: constant)
-  * every --eval_step steps: PSNR / SSIM over the validation pairs (utils/metrics.py, on the host), a checkpoint
+  * every --eval_step steps: PSNR / SSIM over the validation pairs (utils/metrics.py, on the host; --metrics device: the same definitions from
+    the float64 kernel dhz_ssim_pair, no per-image host copy; --metrics ffa: the reference's own FFA_model/metrics.py, main.py:151-173), a checkpoint
     `<model_dir><name>_<step>_psnr: <p>_ssim: <s>.pk` with the reference's keys (step, max_psnr, max_ssim, ssims, psnrs, losses, model),
     and `<model_dir><name>_best.pk` when both metrics improve.  `model` keys carry DataParallel's `module.` prefix like the reference's;
     utils.load_checkpoint reads either form, so `test_long_GPU.py --arch FFA --weights x.pk` evaluates such a file.
@@ -74,6 +75,10 @@ def parse(argv=None):
                         help="train on whole stored images, no crop: the reference's default setting (data_utils.py:21, crop_size = 'whole_img')")
     parser.add_argument('--height', type=int, default=460, help='--whole_img --synthetic: image height (SOTS / ITS frames: 460)')
     parser.add_argument('--width', type=int, default=620, help='--whole_img --synthetic: image width (SOTS / ITS frames: 620)')
+    parser.add_argument('--metrics', choices=('host', 'device', 'ffa'), default='host',
+                        help="validation scores: host = utils/metrics.py on host copies; device = the same definitions from the float64 HIP "
+                             "kernel, read back once per pass; ffa = the reference's FFA_model/metrics.py (11 x 11 Gaussian SSIM, clamped PSNR) "
+                             "from that kernel")
     opt = parser.parse_args(argv)
     opt.model_name = 'My_NH' + '_' + opt.net.split('.')[0] + '_' + str(opt.gps) + '_' + str(opt.blocks)
     opt.model_path = opt.model_dir + opt.model_name          # option.py:38: a prefix, not a directory join
@@ -85,17 +90,32 @@ def load_pairs(path, device):
     return blob["target"].float().to(device), blob["input"].float().to(device)
 
 
-def evaluate(net, vt, vi):
-    """mean (SSIM, PSNR) over the validation pairs, one image at a time (they may differ in size), metrics on the host"""
+def evaluate(net, vt, vi, metrics="host"):
+    """mean (SSIM, PSNR) over the validation pairs, one image at a time (they may differ in size).  metrics: "host" - utils/metrics.py on
+    host copies; "device" - the same two definitions from dhz_ssim_pair, the per-image values read back once; "ffa" - main.py:151-173:
+    the unclamped prediction goes to FFA_model/metrics.py's ssim / psnr, which clamp inside"""
+    if metrics not in ("host", "device", "ffa"):
+        raise ValueError(f"evaluate: metrics={metrics!r}")
     net.eval()
     ssims, psnrs = [], []
     with torch.no_grad():
-        for t, x in zip(vt, vi):
-            pred = torch.clamp(net(x.unsqueeze(0)), 0, 1)[0]
-            a = t.permute(1, 2, 0).cpu().numpy()
-            b = pred.permute(1, 2, 0).cpu().numpy()
-            psnrs.append(float(peak_signal_noise_ratio(a, b)))
-            ssims.append(float(structural_similarity(a, b, multichannel=True)))
+        if metrics == "host":
+            for t, x in zip(vt, vi):
+                pred = torch.clamp(net(x.unsqueeze(0)), 0, 1)[0]
+                a = t.permute(1, 2, 0).cpu().numpy()
+                b = pred.permute(1, 2, 0).cpu().numpy()
+                psnrs.append(float(peak_signal_noise_ratio(a, b)))
+                ssims.append(float(structural_similarity(a, b, multichannel=True)))
+        else:
+            from dehaze_hip.metrics import Scores          # opt-in: a default run never imports it
+            scores = Scores()
+            for t, x in zip(vt, vi):
+                pred = net(x.unsqueeze(0))
+                if metrics == "ffa":
+                    scores.add_ffa(pred, t.unsqueeze(0))
+                else:
+                    scores.add_uniform(torch.clamp(pred, 0, 1), t.unsqueeze(0))
+            ssims, psnrs = scores.read()
     net.train()
     return float(np.mean(ssims)), float(np.mean(psnrs))
 
@@ -185,7 +205,7 @@ def main(argv=None):
             print(f'\rtrain loss : {losses[-1]:.5f}| step :{step}/{opt.steps}|lr :{lr :.7f} |time_used :{(time.time() - t0) / 60 :.1f}',
                   end='', flush=True)
         if step % opt.eval_step == 0:
-            ssim_eval, psnr_eval = evaluate(net, vt, vi)
+            ssim_eval, psnr_eval = evaluate(net, vt, vi, opt.metrics)
             print(f'\nstep :{step} |ssim:{ssim_eval:.4f}| psnr:{psnr_eval:.4f}')
             ssims.append(ssim_eval)
             psnrs.append(psnr_eval)

@@ -206,10 +206,14 @@ SIGNATURES = {
     "dhz_l1_pair_fwd_any": [c_f, c_f, c_f, c_f, c_l, c_p],
     "dhz_l1_pair_bwd_any": [c_f, c_f, c_f, c_f, c_f, c_l, c_p],
     "dhz_crop_augment_pair_rect": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_p],
+    # SSIM / squared error of image pairs in float64 (csrc/metrics.hip)
+    "dhz_ssim_pair_workspace_bytes": [c_i, c_i, c_i, c_i],
+    "dhz_ssim_pair": [c_p, c_p, c_f, c_l, c_l, c_f, c_l, c_l, c_i, c_i, c_i, c_i, c_i, c_f, ctypes.c_double, c_i, ctypes.c_double,
+                      ctypes.c_double, ctypes.c_double, c_i, c_p, ctypes.c_size_t, c_p],
 }
 _RESTYPE = {"dhz_last_error": ctypes.c_char_p, "dhz_build_id": ctypes.c_char_p, "dhz_conv3x3_wgrad_workspace_bytes": ctypes.c_size_t,
             "dhz_ffa_workspace_bytes": ctypes.c_size_t, "dhz_conv3x3_wgrad_workspace_bytes_any": ctypes.c_size_t,
-            "dhz_ffa_workspace_bytes_any": ctypes.c_size_t}
+            "dhz_ffa_workspace_bytes_any": ctypes.c_size_t, "dhz_ssim_pair_workspace_bytes": ctypes.c_size_t}
 
 _lib = None
 

@@ -5,7 +5,12 @@ of equal size restored as ONE forward of up to --batch_size images.  Same argume
 The reference's mask route builds a [B nW, 64, 64] tensor per block and adds the [nW, 64, 64] shift mask to it, which broadcasts for B = 1
 only.  Here the padding reaches the kernels as one 64-bit word per window (bit i: token i is padding; Uformer._stage_pad_bits, five small
 launches per forward), so a masked forward runs the fused window-attention kernels like a mask-free one, at any batch size.  DHZ_PAD_BITS=0
-restores the tensor route (kernel chain, batch 1 only)."""
+restores the tensor route (kernel chain, batch 1 only).
+
+--gpu_metrics: the four printed numbers come from the float64 kernel dhz_ssim_pair (dehaze_hip/metrics.py) on the restored batch as it lies
+in device memory - PSNR / SSIM in utils/metrics.py's form, PSNR2 / SSIM2 in the Gaussian form of utils.SSIM / utils.myPSNR - and are read
+back once at the end; no restored image is copied to the host unless --save_images.  The first pair agrees with the default route to its
+six printed decimals, the second to 2e-4 (the default's utils.SSIM is an fp32 evaluation)."""
 import os
 import sys
 
@@ -41,8 +46,17 @@ def batches_of_equal_size(items, batch_size):
     return out
 
 
+def build_parser():
+    """TA's parser plus --gpu_metrics"""
+    parser = TA.build_parser()
+    parser.add_argument('--gpu_metrics', action='store_true',
+                        help='score on the device in float64 (dhz_ssim_pair): all four printed numbers, no per-image host copy of the restored '
+                             'image (unless --save_images), one read-back at the end')
+    return parser
+
+
 def main(argv=None):
-    args = TA.build_parser().parse_args(argv)
+    args = build_parser().parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("eval_any_resolution.py needs a HIP device")
     dev = torch.device("cuda", int(str(args.gpus).split(",")[0]))
@@ -64,9 +78,22 @@ def main(argv=None):
         items = [(ds[i][0][None], ds[i][1][None], [ds[i][2]]) for i in range(len(ds))]
 
     psnr_val_rgb, ssim_val_rgb, psnr_val_rgb2, ssim_val_rgb2 = [], [], [], []
+    if args.gpu_metrics:
+        from dehaze_hip.metrics import Scores          # opt-in: a default run never imports it
+        first, second = Scores(), Scores()
     with torch.no_grad():
         for batch in batches_of_equal_size(items, max(1, args.batch_size)):
             out = restore_any(model_restoration, torch.cat([it[1] for it in batch]).to(dev), factor=128)
+            if args.gpu_metrics:
+                restored = torch.clamp(out, 0, 1)
+                gts = torch.cat([it[0] for it in batch]).to(dev)
+                first.add_uniform(gts, restored)                         # psnr_loss(restored, gt): the restored image is image_true
+                second.add_ffa(restored, gts, rmse0=float("inf"))        # utils.SSIM / myPSNR: the clamped pair, no special case at rmse 0
+                if args.save_images:
+                    for i, (_, _, filenames) in enumerate(batch):
+                        utils.save_img(os.path.join(args.result_dir, filenames[0]),
+                                       img_as_ubyte(restored[i].permute(1, 2, 0).cpu().numpy()))
+                continue
             for i, (gt, _, filenames) in enumerate(batch):
                 rgb_gt = gt.numpy().squeeze().transpose((1, 2, 0))
                 rgb_restored = torch.clamp(out[i:i + 1], 0, 1).cpu()
@@ -77,6 +104,9 @@ def main(argv=None):
                 ssim_val_rgb.append(ssim_loss(rgb_restored, rgb_gt, multichannel=True))
                 if args.save_images:
                     utils.save_img(os.path.join(args.result_dir, filenames[0]), img_as_ubyte(rgb_restored))
+    if args.gpu_metrics:
+        ssim_val_rgb, psnr_val_rgb = first.read()
+        ssim_val_rgb2, psnr_val_rgb2 = second.read()
     n = len(items)
     out = (sum(psnr_val_rgb) / n, sum(ssim_val_rgb) / n, sum(psnr_val_rgb2) / n, sum(ssim_val_rgb2) / n)
     print("PSNR: %f, SSIM: %f " % out[:2])
