@@ -937,6 +937,35 @@ int dhz_ssim_pair(double* ssim_sum, double* sqerr_sum, const float* a, int64_t a
                   int64_t b_img_stride, int64_t b_ch_stride, int B, int C, int H, int W, int K, const float* window, double wscale,
                   int valid, double C1, double C2, double cov_norm, int clamp01, void* ws, size_t ws_bytes, void* stream);
 
+/* K15  SSIM as a training loss (csrc/ssim_loss.hip): loss = 1 - mean(S) of the Gaussian-window SSIM map and its gradient with respect to the
+ *      prediction, for both forms the reference has: M = FFA_model/metrics.py (`ssim`, M:31-58: zero padding of 5, inputs clamped) and
+ *      A = Uformer_ProbSparse/aaa.py (`ssim`, A:26-75: no padding, A:42-57, no clamp).  x (prediction), y (target): contiguous fp32
+ *      [B, C, H, W]; window: the K x K = 11 x 11 fp32 table of create_window (M:24-28, A:15-19), row-major, on the device, under BOTH border
+ *      rules; valid, C1, C2, clamp01 as in K14 (wscale = cov_norm = 1).  With mux, muy, Exx, Eyy, Exy the five local moments (correlation
+ *      with the window, M:32-39 / A:48-57) of the (clamped) inputs as doubles, all arithmetic in double:
+ *        A1 = 2 mux muy + C1,  A2 = 2 (Exy - mux muy) + C2,  B1 = mux^2 + muy^2 + C1,  B2 = (Exx - mux^2) + (Eyy - muy^2) + C2
+ *        S  = A1 A2 / (B1 B2)                                                                                      (M:42, A:62-66)
+ *      valid == 0: S on all H x W pixels over zero padding (M:32), any H, W >= 1; valid == 1: S on the (H - 10) x (W - 10) pixels whose
+ *        window lies inside the plane (A:42, padd = 0), H, W >= 11.  N = the number of map pixels, B C H' W'.
+ *      dhz_ssim_loss_fwd: loss[0] = (float)(1 - sum S / N) (M:45, A:69), WRITTEN.  With need_grad != 0 it also keeps, per map pixel, in ws
+ *        a = -S / B2,  b = 2 A1 / (B1 B2),  m = 2 muy A2 / (B1 B2) - 2 mux S / B1 - 2 mux a - muy b      (dS/dExx, dS/dExy, dS/dmux)
+ *      dhz_ssim_loss_bwd (after a forward with need_grad on the same ws, same arguments):
+ *        dx(q) = -gloss[0] / N [ (w^T * m)(q) + 2 x(q) (w^T * a)(q) + y(q) (w^T * b)(q) ],  WRITTEN, not accumulated; gloss is a device
+ *        scalar (no host sync); w^T * is the transposed correlation (the same window over zero padding when valid == 0, the full
+ *        correlation of the smaller map when valid == 1).  With clamp01, x and y above are the clamped values and dx is 0 where the raw x
+ *        lies outside [0, 1]; the bounds themselves pass the gradient, as torch.clamp does.  There is no gradient for y.
+ *      Cuts: bands of 32 columns x 64 rows, one workgroup and one double partial sum each; a one-workgroup launch adds them in a fixed
+ *      order.  No atomics; every cut is a function of the shapes: the same bits from run to run, under any dhz_set_reserved_cus, with the
+ *      deterministic mode on or off (the mode's workspace is not used).
+ *      ws: dhz_ssim_loss_workspace_bytes(B, C, H, W, valid) bytes - the partial sums and the three maps as doubles; 0 for an unsupported
+ *      shape - 8-byte aligned.  A null pointer, K != 11, B, C, H or W < 1 (or B C > 65535, H > 4194240, B C H W >= 2^31), H or W < 11
+ *      under the valid rule, a border rule outside {0, 1}, a missing, too small or misaligned workspace: DHZ_EINVAL before any launch. */
+size_t dhz_ssim_loss_workspace_bytes(int B, int C, int H, int W, int valid);
+int dhz_ssim_loss_fwd(float* loss, const float* x, const float* y, int B, int C, int H, int W, int K, const float* window, int valid,
+                      double C1, double C2, int clamp01, int need_grad, void* ws, size_t ws_bytes, void* stream);
+int dhz_ssim_loss_bwd(float* dx, const float* gloss, const float* x, const float* y, int B, int C, int H, int W, int K, const float* window,
+                      int valid, double C1, double C2, int clamp01, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

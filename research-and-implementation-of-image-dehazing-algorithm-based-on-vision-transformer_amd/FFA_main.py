@@ -44,6 +44,13 @@ from PerceptualLoss import PerLoss  # noqa: E402
 from utils.metrics import peak_signal_noise_ratio, structural_similarity  # noqa: E402
 
 
+def nonneg_float(text):
+    v = float(text)
+    if not v >= 0:
+        raise argparse.ArgumentTypeError(f"a weight >= 0, got {text}")
+    return v
+
+
 def parse(argv=None):
     parser = argparse.ArgumentParser(description="FFA-Net, its own training recipe")
     # FFA_model/option.py
@@ -79,6 +86,9 @@ def parse(argv=None):
                         help="validation scores: host = utils/metrics.py on host copies; device = the same definitions from the float64 HIP "
                              "kernel, read back once per pass; ffa = the reference's FFA_model/metrics.py (11 x 11 Gaussian SSIM, clamped PSNR) "
                              "from that kernel")
+    parser.add_argument('--ssimloss', type=nonneg_float, default=0,
+                        help="weight of the SSIM loss 1 - ssim(out, y) on the HIP kernels (FFA_model/metrics.py's ssim: 11 x 11 Gaussian "
+                             "window, both images clamped); 0: off")
     opt = parser.parse_args(argv)
     opt.model_name = 'My_NH' + '_' + opt.net.split('.')[0] + '_' + str(opt.gps) + '_' + str(opt.blocks)
     opt.model_path = opt.model_dir + opt.model_name          # option.py:38: a prefix, not a directory join
@@ -148,6 +158,10 @@ def main(argv=None):
                              "DEHAZE_VGG16_WEIGHTS=/path/to/vgg16-397923af.pth, or DEHAZE_ALLOW_RANDOM_VGG=1 to train against SEEDED "
                              "RANDOM VGG features (not the reference's loss)")
         perloss = PerLoss().to(dev)
+    ssim_term = None
+    if opt.ssimloss > 0:
+        from dehaze_hip.ssim_loss import SSIMLoss          # opt-in: a default run never imports it
+        ssim_term = SSIMLoss()
 
     losses, ssims, psnrs = [], [], []
     start_step, max_ssim, max_psnr = 0, 0.0, 0.0
@@ -197,13 +211,17 @@ def main(argv=None):
             y, x = store.batch(sel.tolist(), None if opt.whole_img else opt.crop_size)
         else:
             y, x = tgt_all[sel.to(dev)], inp_all[sel.to(dev)]
-        loss, _, _ = ffa_train_step(net, perloss, optimizer, None, x, y)
+        if ssim_term is None:
+            loss, _, _ = ffa_train_step(net, perloss, optimizer, None, x, y)
+        else:
+            loss, _, _ = ffa_train_step(net, perloss, optimizer, None, x, y, ssim_loss=ssim_term, w_ssim=opt.ssimloss)
         pending.append(loss)
         if step % opt.log_every == 0 or step % opt.eval_step == 0 or step == opt.steps:
             losses += torch.stack(pending).tolist()
             pending = []
-            print(f'\rtrain loss : {losses[-1]:.5f}| step :{step}/{opt.steps}|lr :{lr :.7f} |time_used :{(time.time() - t0) / 60 :.1f}',
-                  end='', flush=True)
+            ssim_txt = f'| ssim loss : {ssim_term.last_value.item():.5f}' if ssim_term is not None else ''
+            print(f'\rtrain loss : {losses[-1]:.5f}{ssim_txt}| step :{step}/{opt.steps}|lr :{lr :.7f} '
+                  f'|time_used :{(time.time() - t0) / 60 :.1f}', end='', flush=True)
         if step % opt.eval_step == 0:
             ssim_eval, psnr_eval = evaluate(net, vt, vi, opt.metrics)
             print(f'\nstep :{step} |ssim:{ssim_eval:.4f}| psnr:{psnr_eval:.4f}')

@@ -45,7 +45,15 @@ def load_pairs(path, device):
     return blob["target"].float().to(device), blob["input"].float().to(device)
 
 
-def main():
+def nonneg_float(text):
+    v = float(text)
+    if not v >= 0:
+        raise argparse.ArgumentTypeError(f"a weight >= 0, got {text}")
+    return v
+
+
+def build_parser():
+    """options.py's flag set (pinned to the reference's) plus this script's own extra options"""
     parser = options.Options().init(argparse.ArgumentParser(description='remove the haze'))
     parser.add_argument('--synthetic', type=int, default=0, help='train on N synthetic pairs per epoch (HBM resident)')
     parser.add_argument('--val_synthetic', type=int, default=8)
@@ -53,7 +61,14 @@ def main():
     parser.add_argument('--deterministic', action='store_true',
                         help='bit-reproducible steps: fixed-order reductions instead of fp32 atomics (fp32 storage, per process; slower)')
     parser.add_argument('--log_every', type=int, default=10, help='host sync cadence for the progress line')
-    opt = parser.parse_args()
+    parser.add_argument('--w_loss_ssim', type=nonneg_float, default=0,
+                        help='weight of the SSIM loss 1 - ssim(clamped prediction, target) on the HIP kernels (11 x 11 Gaussian window, '
+                             'zero padding); 0: off')
+    return parser
+
+
+def main():
+    opt = build_parser().parse_args()
     torch.backends.cudnn.benchmark = True      # TR:35 - on ROCm: MIOpen measures its convolution algorithms at first use
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -131,6 +146,10 @@ def main():
                          "downloads (My_CR.py:59): set DEHAZE_VGG19_WEIGHTS=/path/to/vgg19-dcbb9e9d.pth (no network here), "
                          "or DEHAZE_ALLOW_RANDOM_VGG=1 to train against SEEDED RANDOM VGG features (not the reference's loss)")
     cr = ContrastLoss(ablation=opt.is_ab).to(dev) if opt.w_loss_vgg7 > 0 else None
+    ssim_term = None
+    if opt.w_loss_ssim > 0:
+        from dehaze_hip.ssim_loss import SSIMLoss          # opt-in: a default run never imports it
+        ssim_term = SSIMLoss(clamp=False)                  # on the clamped prediction: the Charbonnier path carries the clamp's gradient
     if world > 1:
         # identical replicas above (same seed -> same initial weights); from here on every rank draws its own permutations,
         # crops, augmentations, MixUp lambdas, DropPath masks and sampled keys
@@ -205,12 +224,18 @@ def main():
                 target, input_ = tgt_all[sel.to(dev)], inp_all[sel.to(dev)]
             if epoch > 5:
                 target, input_ = mixup.aug(target, input_)
-            loss, loss_rec, loss_cr = train_step(model, char, cr, optimizer, reducer, input_, target,
-                                                 opt.w_loss_CharbonnierLoss, opt.w_loss_vgg7)
+            if ssim_term is None:
+                loss, loss_rec, loss_cr = train_step(model, char, cr, optimizer, reducer, input_, target,
+                                                     opt.w_loss_CharbonnierLoss, opt.w_loss_vgg7)
+            else:
+                loss, loss_rec, loss_cr = train_step(model, char, cr, optimizer, reducer, input_, target,
+                                                     opt.w_loss_CharbonnierLoss, opt.w_loss_vgg7, ssim_loss=ssim_term,
+                                                     w_ssim=opt.w_loss_ssim)
             epoch_loss += loss
             if is_main and (i % opt.log_every == 0):
+                ssim_txt = f'; ssim:{ssim_term.last_value.item():.5f}' if ssim_term is not None else ''
                 print(f'\r{i}/{steps_per_epoch}: loss:{loss.item():.5f} = Charbonnier:{loss_rec.item():.5f}; '
-                      f'contrast:{(loss_cr.item() if loss_cr is not None else 0):.5f} |time_used (Min):'
+                      f'contrast:{(loss_cr.item() if loss_cr is not None else 0):.5f}{ssim_txt} |time_used (Min):'
                       f'{(time.time() - t0) / 60:.1f}', end='', flush=True)
             if (i + 1) % eval_now == 0 and i > 0:
                 val = evaluate()

@@ -210,10 +210,17 @@ SIGNATURES = {
     "dhz_ssim_pair_workspace_bytes": [c_i, c_i, c_i, c_i],
     "dhz_ssim_pair": [c_p, c_p, c_f, c_l, c_l, c_f, c_l, c_l, c_i, c_i, c_i, c_i, c_i, c_f, ctypes.c_double, c_i, ctypes.c_double,
                       ctypes.c_double, ctypes.c_double, c_i, c_p, ctypes.c_size_t, c_p],
+    # SSIM as a training loss: 1 - mean(S) and its gradient with respect to the prediction (csrc/ssim_loss.hip)
+    "dhz_ssim_loss_workspace_bytes": [c_i, c_i, c_i, c_i, c_i],
+    "dhz_ssim_loss_fwd": [c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_i, ctypes.c_double, ctypes.c_double, c_i, c_i, c_p,
+                          ctypes.c_size_t, c_p],
+    "dhz_ssim_loss_bwd": [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_i, ctypes.c_double, ctypes.c_double, c_i, c_p,
+                          ctypes.c_size_t, c_p],
 }
 _RESTYPE = {"dhz_last_error": ctypes.c_char_p, "dhz_build_id": ctypes.c_char_p, "dhz_conv3x3_wgrad_workspace_bytes": ctypes.c_size_t,
             "dhz_ffa_workspace_bytes": ctypes.c_size_t, "dhz_conv3x3_wgrad_workspace_bytes_any": ctypes.c_size_t,
-            "dhz_ffa_workspace_bytes_any": ctypes.c_size_t, "dhz_ssim_pair_workspace_bytes": ctypes.c_size_t}
+            "dhz_ffa_workspace_bytes_any": ctypes.c_size_t, "dhz_ssim_pair_workspace_bytes": ctypes.c_size_t,
+            "dhz_ssim_loss_workspace_bytes": ctypes.c_size_t}
 
 _lib = None
 
