@@ -225,6 +225,23 @@ int dhz_conv4s2_wgrad(const float* dy, const float* x, float* dwp, float* db, in
  *     (all four parity launches share it), 3 = weight gradient (a function of Cin, Cout alone).  0 for a shape the entry refuses.
  *     Host-side only; the dispatch asks the same function, so the answer is what is launched. */
 int dhz_conv4s2_tile(int mode, int B, int H, int W, int Cin, int Cout);
+/* K8 on the bf16 matrix pipe, six-term (csrc/split6_gemm.hip: the plane kernels of the token Linears with a gathered activation operand;
+ *     same x / y / dy / dx as above, fp32, the arithmetic and error class of dhz_linear_fwd_split6).
+ *     dhz_conv4s2_prepack6: from weight [Cout, Cin, 4, 4] the truncation-split bf16 planes (hi | mid | lo, 16 Cin Cout elements each, 96 Cin Cout
+ *                        bytes per set) of weight.permute(0,2,3,1) [Cout][(ky, kx, ci)] -> fwd_planes and of weight.permute(1,2,3,0)
+ *                        [Cin][(ky, kx, co)] -> bwd_planes, bit-identical to dhz_split3_planes of those tensors; one launch; either set may be
+ *                        NULL.  Cin, Cout multiples of 32.
+ *     dhz_conv4s2_fwd6 : y = conv(x) + bias (bias may be NULL).  H, W even, Cin a multiple of 32, Cout a multiple of 64 and <= 2048.
+ *     dhz_conv4s2_dgrad6: dx, every element written exactly once, ONE launch over (parity class, row tile, column tile).  H, W even,
+ *                        Cin, Cout multiples of 32, Cin <= 2048.
+ *     dhz_conv4s2_tile6: the tile of mode 1 = dhz_conv4s2_fwd6, 2 = dhz_conv4s2_dgrad6 under the current dhz_set_reserved_cus /
+ *                        dhz_set_deterministic state, as dhz_linear_split6_tile writes it: 44 = 128 x 128, 42 = 128 x 64, 41 = 128 x 32
+ *                        (backward-data only); 0 for a shape the entry refuses.  Backward-data chooses from the rows of all four classes. */
+int dhz_conv4s2_prepack6(const float* weight, void* fwd_planes, void* bwd_planes, int Cin, int Cout, void* stream);
+int dhz_conv4s2_fwd6(const float* x, const void* fwd_planes, const float* bias, float* y, int B, int H, int W, int Cin, int Cout,
+                     void* stream);
+int dhz_conv4s2_dgrad6(const float* dy, const void* bwd_planes, float* dx, int B, int H, int W, int Cin, int Cout, void* stream);
+int dhz_conv4s2_tile6(int mode, int B, int H, int W, int Cin, int Cout);
 
 /* K8 in bf16 (BASELINE config 4): the same convolution as three token-Linear GEMMs on the bf16 matrix pipe (dhz_linear_fwd_bf16 /
  *     _dgrad_bf16 / _wgrad_bf16 with wp [Cout, 16*Cin]) over an explicit tap-major patch matrix; in the token layout a tap of an

@@ -77,11 +77,38 @@ template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_wai
 // so every global access has two stages of matrix time to land, no fragment read waits on a barrier, and the barrier is only
 // the hand-over of ring slots.  The loop is unrolled six times (ring slots, register sets and fragment sets are compile-time).
 // EPI: the epilogue is the block's residual step (csrc/tok_epilogue.h): C[dst(m)] = res[dst(m)] + scale[img(m)] (acc + bias).
-template <int WM, int WN, int WAVES_M, bool BTR, bool EPI>
+//
+// SRC: where an activation row comes from.  0 = a row of A (the token Linears).  1 / 2 = the 4 x 4 / stride-2 / pad-1 convolution of
+// Downsample as an implicit GEMM (the arithmetic of csrc/conv_gemm.hip): a 32-deep stage lies inside one tap (channels in 32s), so a
+// gathered row is a row pointer, computed once per tile, plus a stage offset that is uniform over the workgroup and a validity bit per
+// row and stage.  The load goes to an in-bounds address either way and the registers are zeroed after the counted wait.
+//     1  forward        row m = (b, oy, ox), stage -> (tap (ky, kx), c0): &x[b, 2 oy - 1 + ky, 2 ox - 1 + kx, c0 + ...]; weights [Cout][(ky, kx, ci)]
+//     2  backward-data  tile -> (parity class (py, px), row tile, column tile); row m = (b, iy2, ix2) of the class, stage -> (tap (a2, c2)
+//                       of the class's 2 x 2 set, c0): &dy[b, iy2 + py - a2, ix2 + px - c2, c0 + ...]; weights [Cin][(ky, kx, co)] with
+//                       ky = 1 - py + 2 a2, kx = 1 - px + 2 c2 (four Cout-wide blocks of the 16 Cout axis); the result row is token
+//                       (b, 2 iy2 + py, 2 ix2 + px) of dx.  M = rows of ONE class.
+struct ConvSrc {
+    int H, W;            // the map with 2x the pixels (x, dx)
+    int Ho, Wo;          // = H / 2, W / 2 (y, dy)
+    int Cin, Cout;
+    int tiles_cls;       // SRC 2: tiles of one parity class
+};
+struct NoSrc {};
+// the kernel's last argument: the residual epilogue's description (SRC 0) or the convolution's geometry (SRC 1 / 2)
+__device__ __forceinline__ const TokEpi& epi_of(const TokEpi& e) { return e; }
+__device__ __forceinline__ TokEpi epi_of(const ConvSrc&) { return TokEpi{}; }
+__device__ __forceinline__ NoSrc geom_of(const TokEpi&) { return NoSrc{}; }
+__device__ __forceinline__ const ConvSrc& geom_of(const ConvSrc& g) { return g; }
+
+template <int WM, int WN, int WAVES_M, bool BTR, bool EPI, int SRC = 0, typename Tail = TokEpi>
 __global__ __launch_bounds__(NT, 1) void split6_gemm_kernel(const float* __restrict__ A, int lda, const uint16_t* __restrict__ Bh,
                                                             const uint16_t* __restrict__ Bm, const uint16_t* __restrict__ Bl,
                                                             int ldb, const float* __restrict__ bias, float* __restrict__ C, int ldc,
-                                                            int M, int NF, int KC, int tiles_n, int ntiles, const TokEpi epi) {
+                                                            int M, int NF, int KC, int tiles_n, int ntiles, const Tail tail) {
+    static_assert((SRC == 0) == std::is_same<Tail, TokEpi>::value, "TokEpi for the Linears, ConvSrc for the gathered forms");
+    const auto& epi = epi_of(tail);
+    const auto& G = geom_of(tail);
+    static_assert(SRC == 0 || (!BTR && !EPI), "the gathered forms run the forward kernel form");
     constexpr int WAVES_N = 8 / WAVES_M;
     constexpr int BM = 16 * WM * WAVES_M, BN = 16 * WN * WAVES_N;
     constexpr int A_BYTES = BM * 64, B_BYTES = BN * 64;            // one piece of one stage
@@ -144,15 +171,22 @@ __global__ __launch_bounds__(NT, 1) void split6_gemm_kernel(const float* __restr
 
     // (tile, stage) position of the stream; the tile's row / column origin is derived once per tile (an integer division per stage
     // and use costs ~20 scalar instructions of an in-order wave)
-    struct Pos { int tile, st, ti, m0, n0; };
+    struct Pos { int tile, st, ti, m0, n0, cls; };
     auto at_tile = [&](int ti) -> Pos {
         const int tile = tile_of(ti);
-        const int tm = tile < 0 ? 0 : tile / tiles_n;
-        return Pos{tile, 0, ti, tm * BM, (tile - tm * tiles_n) * BN};
+        if constexpr (SRC == 2) {                       // tile = (parity class, row tile, column tile)
+            const int tl = tile < 0 ? 0 : tile;
+            const int cls = tl / G.tiles_cls, rest = tl - cls * G.tiles_cls;
+            const int tm = rest / tiles_n;
+            return Pos{tile, 0, ti, tm * BM, (rest - tm * tiles_n) * BN, cls};
+        } else {
+            const int tm = tile < 0 ? 0 : tile / tiles_n;
+            return Pos{tile, 0, ti, tm * BM, (tile - tm * tiles_n) * BN, 0};
+        }
     };
     auto next = [&](const Pos& p) -> Pos {
         if (p.tile < 0) return p;
-        if (p.st + 1 < nst) return Pos{p.tile, p.st + 1, p.ti, p.m0, p.n0};
+        if (p.st + 1 < nst) return Pos{p.tile, p.st + 1, p.ti, p.m0, p.n0, p.cls};
         return at_tile(p.ti + 1);
     };
     const Pos pz = at_tile(0);
@@ -162,14 +196,82 @@ __global__ __launch_bounds__(NT, 1) void split6_gemm_kernel(const float* __restr
     auto valid = [&](const Pos& p) -> Pos { return p.tile >= 0 ? p : pz; };
 
     f32x4 ra[2][NA][2];                                            // raw activations: stage q in set q & 1
-    auto a_addr = [&](const Pos& q, int i) -> const float* {
-        const int m0 = q.m0, k0 = q.st * BK;
-        return A + (size_t)min(m0 + a_row[i], M - 1) * lda + k0 + 8 * a_kc[i];
+    // gathered forms: the row state of the tile the loads are in (loads are issued in stream order), and per register set the
+    // validity bits of the stage it holds (bit i: chunk i lies inside the map)
+    const float* g_pa[NA];     // SRC 1: &x[b, 2 oy - 1, 2 ox - 1, 8 kc]   SRC 2: &dy[b, iy2, ix2, 8 kc]   (may lie outside the map: see ok)
+    int g_y[NA], g_x[NA];      // SRC 1: 2 oy - 1, 2 ox - 1                SRC 2: iy2, ix2
+    int g_ti = -1;
+    unsigned vm[2] = {0u, 0u};
+    auto a_tile = [&](const Pos& q) {
+        if constexpr (SRC != 0) {
+            if (q.ti == g_ti) return;                              // uniform
+            g_ti = q.ti;
+#pragma unroll
+            for (int i = 0; i < NA; ++i) {
+                const int m = min(q.m0 + a_row[i], M - 1);
+                const int b = m / (G.Ho * G.Wo), r = m - b * (G.Ho * G.Wo);
+                const int oy = r / G.Wo, ox = r - oy * G.Wo;
+                if (SRC == 1) {
+                    g_y[i] = 2 * oy - 1; g_x[i] = 2 * ox - 1;
+                    g_pa[i] = A + ((long long)(b * G.H + g_y[i]) * G.W + g_x[i]) * G.Cin + 8 * a_kc[i];
+                } else {
+                    g_y[i] = oy; g_x[i] = ox;
+                    g_pa[i] = A + ((long long)(b * G.Ho + oy) * G.Wo + ox) * G.Cout + 8 * a_kc[i];
+                }
+            }
+        }
+    };
+    // the stage of a gathered form: (tap, first channel), uniform
+    auto tap_of = [&](int st, int& c0) -> int {
+        if constexpr (SRC != 0) {
+            const int spt = (SRC == 1 ? G.Cin : G.Cout) / BK;
+            const int tap = st / spt;
+            c0 = (st - tap * spt) * BK;
+            return tap;
+        } else {
+            c0 = 0;
+            return 0;
+        }
+    };
+    auto a_addr = [&](const Pos& q, int i, unsigned& okbits) -> const float* {
+        if constexpr (SRC == 0) {
+            const int m0 = q.m0, k0 = q.st * BK;
+            return A + (size_t)min(m0 + a_row[i], M - 1) * lda + k0 + 8 * a_kc[i];
+        } else {
+            int c0;
+            const int tap = tap_of(q.st, c0);
+            int dy_, dx_, hy, hx;
+            long long delta;
+            if (SRC == 1) {
+                dy_ = tap >> 2; dx_ = tap & 3; hy = G.H; hx = G.W;
+                delta = (long long)(dy_ * G.W + dx_) * G.Cin + c0;
+            } else {
+                dy_ = (q.cls >> 1) - (tap >> 1); dx_ = (q.cls & 1) - (tap & 1); hy = G.Ho; hx = G.Wo;
+                delta = (long long)(dy_ * G.Wo + dx_) * G.Cout + c0;
+            }
+            const bool ok = (unsigned)(g_y[i] + dy_) < (unsigned)hy && (unsigned)(g_x[i] + dx_) < (unsigned)hx;
+            okbits |= ok ? 1u << i : 0u;
+            return ok ? g_pa[i] + delta : A + 8 * a_kc[i];         // outside the map: the operand's first row, zeroed after the wait
+        }
     };
     auto a_load = [&](auto set, const Pos& q) {
         constexpr int S = decltype(set)::value;
+        a_tile(q);
+        unsigned ok = 0u;
 #pragma unroll
-        for (int i = 0; i < NA; ++i) gload32(a_addr(q, i), ra[S][i][0], ra[S][i][1]);
+        for (int i = 0; i < NA; ++i) gload32(a_addr(q, i, ok), ra[S][i][0], ra[S][i][1]);
+        if constexpr (SRC != 0) vm[S] = ok;
+    };
+    auto a_mask = [&](auto set) {                                  // after the set's wait: zero the chunks that lie outside the map
+        constexpr int S = decltype(set)::value;
+        if constexpr (SRC != 0) {
+#pragma unroll
+            for (int i = 0; i < NA; ++i) {
+                const bool ok = (vm[S] >> i) & 1u;
+                ra[S][i][0] = ok ? ra[S][i][0] : f32x4{0.f, 0.f, 0.f, 0.f};
+                ra[S][i][1] = ok ? ra[S][i][1] : f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+        }
     };
     auto a_wait = [&](auto set, auto tag) {                        // set's loads are complete; the tag's count of younger operations stays in flight
         constexpr int S = decltype(set)::value, N = decltype(tag)::value;
@@ -179,6 +281,7 @@ __global__ __launch_bounds__(NT, 1) void split6_gemm_kernel(const float* __restr
     auto a_split_write = [&](auto set, int slot) {
         constexpr int S = decltype(set)::value;
         if (abl & 4) return;
+        a_mask(set);
         unsigned char* As = Aring + slot * A_SLOT;
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
@@ -191,7 +294,14 @@ __global__ __launch_bounds__(NT, 1) void split6_gemm_kernel(const float* __restr
     };
     auto b_dma = [&](const Pos& q, int slot) {
         if (abl & 8) return;
-        const int n0 = q.n0, k0 = q.st * BK;
+        const int n0 = q.n0;
+        int k0 = q.st * BK;
+        if constexpr (SRC == 2) {                                  // the class's tap -> its Cout-wide block of the (ky, kx, co) axis
+            int c0;
+            const int tap = tap_of(q.st, c0);
+            const int ky = 1 - (q.cls >> 1) + 2 * (tap >> 1), kx = 1 - (q.cls & 1) + 2 * (tap & 1);
+            k0 = (4 * ky + kx) * G.Cout + c0;
+        }
         const size_t base = BTR ? (size_t)k0 * ldb + n0 : (size_t)n0 * ldb + k0;
         unsigned char* Bs = Bring + slot * B_SLOT;
 #pragma unroll
@@ -303,6 +413,41 @@ __global__ __launch_bounds__(NT, 1) void split6_gemm_kernel(const float* __restr
             for (int b = 0; b < WN; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
         return full;
     };
+    // SRC 2: rows of the tile's parity class -> tokens (b, 2 iy2 + py, 2 ix2 + px) of dx; no bias.  Store count as above.
+    auto epilogue_dgrad = [&](const Pos& p) -> bool {
+        bool full = true;
+        if constexpr (SRC == 2) {
+            const int m0 = p.m0 + wm * WM * 16 + i16, n0 = p.n0 + wn * WN * 16 + 4 * g;
+            const int py = p.cls >> 1, px = p.cls & 1;
+            float* cr[WM];
+#pragma unroll
+            for (int a = 0; a < WM; ++a) {
+                const int m = min(m0 + 16 * a, M - 1);
+                const int b = m / (G.Ho * G.Wo), r = m - b * (G.Ho * G.Wo);
+                const int iy2 = r / G.Wo, ix2 = r - iy2 * G.Wo;
+                cr[a] = C + (((size_t)b * G.H + 2 * iy2 + py) * G.W + 2 * ix2 + px) * ldc + n0;
+            }
+            full = p.m0 + BM <= M;                                 // wave-uniform
+            if (full) {
+#pragma unroll
+                for (int a = 0; a < WM; ++a)
+#pragma unroll
+                    for (int b = 0; b < WN; ++b) *reinterpret_cast<f32x4*>(cr[a] + 16 * b) = acc[a][b];
+            } else {
+#pragma unroll
+                for (int a = 0; a < WM; ++a)
+                    if (m0 + 16 * a < M) {
+#pragma unroll
+                        for (int b = 0; b < WN; ++b) *reinterpret_cast<f32x4*>(cr[a] + 16 * b) = acc[a][b];
+                    }
+            }
+#pragma unroll
+            for (int a = 0; a < WM; ++a)
+#pragma unroll
+                for (int b = 0; b < WN; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        return full;
+    };
     using I0 = std::integral_constant<int, 0>;
     using I1 = std::integral_constant<int, 1>;
 
@@ -347,11 +492,15 @@ __global__ __launch_bounds__(NT, 1) void split6_gemm_kernel(const float* __restr
         b_dma(valid(p3), S0);
         if (HALF < WM) read_a(F{}, S0, HALF, WM);
         const float* pa[NA];
+        unsigned okn = 0u;                                         // gathered forms: the validity bits of stage p + 4
+        a_tile(valid(p4));
 #pragma unroll
-        for (int i = 0; i < NA; ++i) pa[i] = a_addr(valid(p4), i);
+        for (int i = 0; i < NA; ++i) pa[i] = a_addr(valid(p4), i, okn);
         dhz_u32x4 sh[NA], sm[NA], sl[NA];
+        a_mask(F{});
 #pragma unroll
         for (int i = 0; i < NA; ++i) dhz_split8x3_np(ra[R & 1][i][0], ra[R & 1][i][1], sh[i], sm[i], sl[i]);
+        if constexpr (SRC != 0) vm[R & 1] = okn;
         mma_rows(F{}, 0, HALF);
 #pragma unroll
         for (int i = 0; i < HALF * WN * 6; ++i) {
@@ -384,7 +533,10 @@ __global__ __launch_bounds__(NT, 1) void split6_gemm_kernel(const float* __restr
         __builtin_amdgcn_sched_barrier(0);
         const bool stored = p0.st == nst - 1;
         bool full = true;
-        if (stored) full = epilogue(p0.tile);
+        if (stored) {
+            if constexpr (SRC == 2) full = epilogue_dgrad(p0);
+            else full = epilogue(p0.tile);
+        }
         if (!have1) { done = true; return; }
         __builtin_amdgcn_sched_barrier(0);
         // the DMA of stage p + 2 (issued one iteration ago) has landed: it is older than 2 NA loads + one DMA set + 2 NA loads and
@@ -793,8 +945,126 @@ __global__ __launch_bounds__(256) void split3_planes_t_kernel(const float* __res
     }
 }
 
+// ---- the Downsample convolution (4 x 4, stride 2, pad 1) on the gathered forms
+// Weight planes of one layer, both operand layouts, from w [Cout][Cin][4][4] in one launch (the weights change every step):
+//     fwd [Cout][(ky, kx, ci)]  - the planes of w.permute(0, 2, 3, 1)      bwd [Cin][(ky, kx, co)]  - the planes of w.permute(1, 2, 3, 0)
+// three planes of 16 Cin Cout bf16 each, hi | mid | lo, the truncation split of split3_planes_kernel (bit-identical pieces).  A thread
+// reads the 16 taps of one (co, ci) pair (64 contiguous bytes); the first half of the grid walks ci with its lanes and writes fwd,
+// the second half walks co and writes bwd: every store instruction of a wave covers 128 contiguous bytes.
+__global__ __launch_bounds__(256) void conv4s2_prepack6_kernel(const float* __restrict__ w, uint16_t* __restrict__ fwd, uint16_t* __restrict__ bwd,
+                                                               int Cin, int Cout, int half) {
+    const bool second = (int)blockIdx.x >= half;
+    if ((second ? bwd : fwd) == nullptr) return;
+    const long n = (long)Cin * Cout, plane = 16 * n;
+    const long stride = (long)half * 256;
+    for (long e = (long)((int)blockIdx.x - (second ? half : 0)) * 256 + threadIdx.x; e < n; e += stride) {
+        const int co = second ? (int)(e % Cout) : (int)(e / Cin), ci = second ? (int)(e / Cout) : (int)(e % Cin);
+        const float* src = w + ((size_t)co * Cin + ci) * 16;
+        f32x4 v[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = *reinterpret_cast<const f32x4*>(src + 4 * q);
+        uint16_t* dst = second ? bwd + (size_t)ci * 16 * Cout + co : fwd + (size_t)co * 16 * Cin + ci;
+        const int step = second ? Cout : Cin;
+#pragma unroll
+        for (int tap = 0; tap < 16; ++tap) {
+            const float x = v[tap >> 2][tap & 3];
+            const float r1 = x - __uint_as_float(__float_as_uint(x) & 0xffff0000u);
+            const float r2 = r1 - __uint_as_float(__float_as_uint(r1) & 0xffff0000u);
+            dst[(size_t)tap * step] = (uint16_t)(__float_as_uint(x) >> 16);
+            dst[(size_t)tap * step + plane] = (uint16_t)(__float_as_uint(r1) >> 16);
+            dst[(size_t)tap * step + 2 * plane] = (uint16_t)(__float_as_uint(r2) >> 16);
+        }
+    }
+}
+
+// grid = min(tiles, dhz_num_cus()), one workgroup per CU, as launch() above
+template <int WM, int WN, int WAVES_M, int SRC>
+void launch_conv(const float* A, const uint16_t* planes, const float* bias, float* C, int M, int NF, int KC, const ConvSrc& geom, hipStream_t s) {
+    constexpr int BM = 16 * WM * WAVES_M, BN = 16 * WN * (8 / WAVES_M);
+    const size_t smem = 3 * 3 * (size_t)(BM * 64 + BN * 64) + (size_t)NF * sizeof(float);
+    const int tiles_n = NF / BN, tiles_m = (M + BM - 1) / BM;
+    ConvSrc G = geom;
+    G.tiles_cls = tiles_n * tiles_m;
+    const int ntiles = (SRC == 2 ? 4 : 1) * G.tiles_cls;
+    const int slots = dhz_num_cus();
+    const int grid = ntiles < slots ? ntiles : slots;
+    const size_t plane = (size_t)16 * geom.Cin * geom.Cout;
+    const int ldb = 16 * (SRC == 1 ? geom.Cin : geom.Cout);
+    auto* kernel = &split6_gemm_kernel<WM, WN, WAVES_M, false, false, SRC, ConvSrc>;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(NT), smem, s, A, 0, planes, planes + plane, planes + 2 * plane, ldb, bias, C, NF, M, NF, KC, tiles_n,
+                       ntiles, G);
+}
+
+bool conv6_shape_ok(int mode, int B, int H, int W, int Cin, int Cout) {
+    if (!(B > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && Cin > 0 && Cout > 0 && Cin % 32 == 0 && Cout % 32 == 0)) return false;
+    if (mode == 1 && Cout % 64) return false;                    // the forward's tiles are 64 or 128 features wide
+    if ((mode == 1 ? Cout : Cin) > 2048 || (long)16 * Cin * Cout >= (1L << 31)) return false;
+    return (long)B * H * W < (1L << 31);
+}
+
+// The tile of the gathered forms, as split6_tile names it: 44 = 128 x 128, 42 = 128 x 64, 41 = 128 x 32 (backward-data at Cin = 32 (2 k + 1)
+// only).  Backward-data chooses from the rows of all four parity classes: they are one launch.  (The 256 x 128 kernel has no gathered
+// form: a shape that would take it runs 128 x 128.)
+int conv6_tile(int mode, int B, int H, int W, int Cin, int Cout) {
+    if ((mode != 1 && mode != 2) || !conv6_shape_ok(mode, B, H, W, Cin, Cout)) return 0;
+    const long rows = (long)B * (H / 2) * (W / 2) * (mode == 2 ? 4 : 1);
+    const int tile = split6_tile(false, (int)rows, mode == 1 ? Cout : Cin, mode == 1 ? 16 * Cin : 4 * Cout);
+    return tile == 84 ? 44 : tile;
+}
+
 }  // namespace
 
+extern "C" int dhz_conv4s2_prepack6(const float* w, void* fwd_planes, void* bwd_planes, int Cin, int Cout, void* stream) {
+    const char* who = "dhz_conv4s2_prepack6";
+    DHZ_REQUIRE(w && (fwd_planes || bwd_planes), "%s: null pointer", who);
+    DHZ_REQUIRE(Cin > 0 && Cout > 0 && Cin % 32 == 0 && Cout % 32 == 0 && (long)16 * Cin * Cout < (1L << 31),
+                "%s: Cin=%d Cout=%d (multiples of 32, 16 Cin Cout < 2^31)", who, Cin, Cout);
+    DHZ_REQUIRE((((uintptr_t)w | (uintptr_t)fwd_planes | (uintptr_t)bwd_planes) & 15) == 0, "%s: 16-byte alignment", who);
+    const long pairs = (long)Cin * Cout;
+    long half = (pairs + 255) / 256;
+    const long cap = 4L * dhz_num_cus();
+    if (half > cap) half = cap;
+    hipLaunchKernelGGL(conv4s2_prepack6_kernel, dim3((unsigned)(2 * half)), dim3(256), 0, (hipStream_t)stream, w, (uint16_t*)fwd_planes,
+                       (uint16_t*)bwd_planes, Cin, Cout, (int)half);
+    DHZ_CHECK_LAUNCH(who);
+    return DHZ_OK;
+}
+
+extern "C" int dhz_conv4s2_fwd6(const float* x, const void* fwd_planes, const float* bias, float* y, int B, int H, int W, int Cin, int Cout,
+                                void* stream) {
+    const char* who = "dhz_conv4s2_fwd6";
+    DHZ_REQUIRE(x && fwd_planes && y, "%s: null pointer", who);
+    DHZ_REQUIRE(conv6_shape_ok(1, B, H, W, Cin, Cout), "%s: map %dx%d (even sizes) Cin=%d (multiple of 32) Cout=%d (multiple of 64, at most 2048)", who,
+                H, W, Cin, Cout);
+    DHZ_REQUIRE((((uintptr_t)x | (uintptr_t)fwd_planes | (uintptr_t)y | (uintptr_t)bias) & 15) == 0, "%s: operands must be 16-byte aligned", who);
+    const ConvSrc G = {H, W, H / 2, W / 2, Cin, Cout, 0};
+    const int M = B * G.Ho * G.Wo;
+    const uint16_t* pl = (const uint16_t*)fwd_planes;
+    if (conv6_tile(1, B, H, W, Cin, Cout) == 44) launch_conv<4, 2, 2, 1>(x, pl, bias, y, M, Cout, 16 * Cin, G, (hipStream_t)stream);
+    else launch_conv<2, 2, 4, 1>(x, pl, bias, y, M, Cout, 16 * Cin, G, (hipStream_t)stream);
+    DHZ_CHECK_LAUNCH(who);
+    return DHZ_OK;
+}
+
+extern "C" int dhz_conv4s2_dgrad6(const float* dy, const void* bwd_planes, float* dx, int B, int H, int W, int Cin, int Cout, void* stream) {
+    const char* who = "dhz_conv4s2_dgrad6";
+    DHZ_REQUIRE(dy && bwd_planes && dx, "%s: null pointer", who);
+    DHZ_REQUIRE(conv6_shape_ok(2, B, H, W, Cin, Cout), "%s: map %dx%d (even sizes) Cin=%d (multiple of 32, at most 2048) Cout=%d (multiple of 32)", who,
+                H, W, Cin, Cout);
+    DHZ_REQUIRE((((uintptr_t)dy | (uintptr_t)bwd_planes | (uintptr_t)dx) & 15) == 0, "%s: operands must be 16-byte aligned", who);
+    const ConvSrc G = {H, W, H / 2, W / 2, Cin, Cout, 0};
+    const int M = B * G.Ho * G.Wo;                                // rows of one parity class
+    const uint16_t* pl = (const uint16_t*)bwd_planes;
+    const int tile = conv6_tile(2, B, H, W, Cin, Cout);
+    if (tile == 44) launch_conv<4, 2, 2, 2>(dy, pl, nullptr, dx, M, Cin, 4 * Cout, G, (hipStream_t)stream);
+    else if (tile == 42) launch_conv<2, 2, 4, 2>(dy, pl, nullptr, dx, M, Cin, 4 * Cout, G, (hipStream_t)stream);
+    else launch_conv<1, 2, 8, 2>(dy, pl, nullptr, dx, M, Cin, 4 * Cout, G, (hipStream_t)stream);
+    DHZ_CHECK_LAUNCH(who);
+    return DHZ_OK;
+}
+
+extern "C" int dhz_conv4s2_tile6(int mode, int B, int H, int W, int Cin, int Cout) { return conv6_tile(mode, B, H, W, Cin, Cout); }
 
 extern "C" int dhz_split3_planes_t(const float* src, void* hi, void* mid, void* lo, const int* desc, int nmat, int ntiles, void* stream) {
     const char* who = "dhz_split3_planes_t";

@@ -172,6 +172,11 @@ SIGNATURES = {
     "dhz_conv3x3_wgrad_workspace_bytes": [c_i, c_i, c_i, c_i, c_i],
     "dhz_conv3x3_wgrad_parts": [c_i, c_i, c_i, c_i, c_i],
     "dhz_conv4s2_tile": [c_i, c_i, c_i, c_i, c_i, c_i],
+    # Downsample on the six-term plane kernels (csrc/split6_gemm.hip)
+    "dhz_conv4s2_prepack6": [c_f, c_p, c_p, c_i, c_i, c_p],
+    "dhz_conv4s2_fwd6": [c_f, c_p, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_p],
+    "dhz_conv4s2_dgrad6": [c_f, c_p, c_f, c_i, c_i, c_i, c_i, c_i, c_p],
+    "dhz_conv4s2_tile6": [c_i, c_i, c_i, c_i, c_i, c_i],
     "dhz_linear_tile": [c_i, c_i],
     "dhz_linear_split6_tile": [c_i, c_i, c_i, c_i],
     "dhz_conv3x3_wgrad": [c_f, c_f, c_f, c_f, c_f, ctypes.c_size_t, c_i, c_i, c_i, c_i, c_i, c_p],

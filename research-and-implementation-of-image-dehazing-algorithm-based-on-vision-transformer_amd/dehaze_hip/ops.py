@@ -1240,6 +1240,23 @@ def _conv4s2_wgrad(w, b, zeros, launch):
     return None if wbuf is not None else dw.contiguous(), None if gbuf is not None else dbv
 
 
+# Forward and backward-data on the six-term plane kernels (dhz_conv4s2_fwd6 / _dgrad6, csrc/split6_gemm.hip) instead of the fp32 matrix
+# pipe: fp32 storage, SPLIT_BF16 == 6, deterministic mode off (it keeps the fp32 entries, whose tile choice is a function of the shape),
+# and a (Cin, Cout) that is listed for the product.  A level is listed only where the new entry beat the fp32 one by more than the spread
+# between rounds at the headline shapes (B = 32, 128-pixel patches; DESIGN.md section 7d, profiles/conv4s2_split6.txt), each product on
+# its own.  The weight gradient stays on dhz_conv4s2_wgrad.  DHZ_CONV4S2_SPLIT6=0 is the A/B switch.
+CONV4S2_SPLIT6 = os.environ.get("DHZ_CONV4S2_SPLIT6", "1") != "0"
+CONV4S2_SPLIT6_FWD = {(32, 64), (64, 128), (128, 256)}       # 256 -> 512: 128 tiles of 128 x 64 on 256 CUs, level with the fp32 entry
+CONV4S2_SPLIT6_DGRAD = {(32, 64), (64, 128), (128, 256), (256, 512)}
+
+
+def _conv4s2_split6(Cin, Cout):
+    """(forward, backward-data): which products of this fp32 Downsample layer run the six-term entries"""
+    if not CONV4S2_SPLIT6 or SPLIT_BF16 != 6 or DETERMINISTIC:
+        return False, False
+    return (Cin, Cout) in CONV4S2_SPLIT6_FWD, (Cin, Cout) in CONV4S2_SPLIT6_DGRAD
+
+
 class _Conv4s2(Function):
     """Downsample.conv on the token layout (M1:606-622): x [B, H*W, Cin] -> [B, (H/2)*(W/2), Cout]."""
 
@@ -1250,11 +1267,21 @@ class _Conv4s2(Function):
         B, L, Cin = x.shape
         Cout = w.shape[0]
         assert L == H * W and tuple(w.shape) == (Cout, Cin, 4, 4)
-        wp = w.detach().permute(0, 2, 3, 1).reshape(Cout, 16 * Cin).contiguous()      # [co][(ky, kx, ci)]
         y = torch.empty((B, L // 4, Cout), device=x.device, dtype=torch.float32)
-        _lib.call("dhz_conv4s2_fwd", _p(x), _p(wp), _p(b), _p(y), B, H, W, Cin, Cout, _stream())
+        fwd6, dgrad6 = _conv4s2_split6(Cin, Cout)
+        dgrad6 = dgrad6 and ctx.needs_input_grad[0]
+        pf = pb = None
+        if fwd6 or dgrad6:                                 # one launch writes the weight planes of both products (the weights change every step)
+            pf = torch.empty((3, 16 * Cin * Cout), device=x.device, dtype=torch.int16) if fwd6 else None
+            pb = torch.empty((3, 16 * Cin * Cout), device=x.device, dtype=torch.int16) if dgrad6 else None
+            _lib.call("dhz_conv4s2_prepack6", _p(w.detach().contiguous()), _p(pf), _p(pb), Cin, Cout, _stream())
+        if fwd6:
+            _lib.call("dhz_conv4s2_fwd6", _p(x), _p(pf), _p(b), _p(y), B, H, W, Cin, Cout, _stream())
+        else:
+            wp = w.detach().permute(0, 2, 3, 1).reshape(Cout, 16 * Cin).contiguous()      # [co][(ky, kx, ci)]
+            _lib.call("dhz_conv4s2_fwd", _p(x), _p(wp), _p(b), _p(y), B, H, W, Cin, Cout, _stream())
         ctx.save_for_backward(x, w)
-        ctx.params, ctx.geom = (w, b), (B, H, W, Cin, Cout)
+        ctx.params, ctx.geom, ctx.planes_t = (w, b), (B, H, W, Cin, Cout), pb
         return y
 
     @staticmethod
@@ -1264,7 +1291,10 @@ class _Conv4s2(Function):
         B, H, W, Cin, Cout = ctx.geom
         dy = dy.contiguous()
         dx = None
-        if ctx.needs_input_grad[0]:
+        if ctx.needs_input_grad[0] and ctx.planes_t is not None:
+            dx = torch.empty_like(x)
+            _lib.call("dhz_conv4s2_dgrad6", _p(dy), _p(ctx.planes_t), _p(dx), B, H, W, Cin, Cout, _stream())
+        elif ctx.needs_input_grad[0]:
             wq = w_.detach().permute(2, 3, 0, 1).contiguous()                         # [(ky, kx, co)][ci]
             dx = torch.empty_like(x)
             _lib.call("dhz_conv4s2_dgrad", _p(dy), _p(wq), _p(dx), B, H, W, Cin, Cout, _stream())
