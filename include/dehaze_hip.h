@@ -691,6 +691,23 @@ int dhz_crop_augment_pair(const uint8_t* gt, const uint8_t* hazy, const int* tab
  *     eight, bit for bit dhz_crop_augment_pair.  The caller keeps r + h <= Hs and c + w <= Ws. */
 int dhz_crop_augment_pair_rect(const uint8_t* gt, const uint8_t* hazy, const int* table, float* out_gt, float* out_hazy,
                                int n, int Hs, int Ws, int h, int w, void* stream);
+/*     dhz_crop_augment_pair_ragged: the same feed for images that each have their own size - what FFA_model/data_utils.py:51-81 does per
+ *     item on the host (PIL open, CenterCrop of the clear frame, RandomCrop, flip / rotate, ToTensor, Normalize).  gt_pool / hazy_pool are
+ *     uint8 pools in device memory, every image HWC (RGB) at its own offset; a pool may exceed 4 GiB, all addresses are formed in 64 bits.
+ *     desc: device memory, one row of DHZ_RAGGED_DESC_WORDS int64 per batch item, computed on the host:
+ *       [0] pixel offset (bytes / 3) in hazy_pool of the crop's origin: image base + r * hazy stride + c
+ *       [1] hazy row stride in pixels (the hazy image's width)
+ *       [2] pixel offset in gt_pool of the crop's origin: image base + (top + r) * clear stride + left + c, (top, left) the centre-crop
+ *           origin of the larger clear frame
+ *       [3] clear row stride in pixels (the clear image's width)
+ *       [4] the map k, 0..7 as in dhz_crop_augment_pair; on h != w the kernel reads k & 6 as the rect entry does
+ *     Output float32 [n,3,h,w] for both, position for position the rect entry's.  norm: NULL, or six floats in HOST memory (mean[3],
+ *     std[3]) read during the call; then out_hazy = ((float)v / 255.f - mean[ch]) / std[ch], two IEEE operations after the division
+ *     (ToTensor + Normalize in fp32); out_gt is never normalised.  n * h * w < 2^31.  The entry cannot see the images' sizes: the caller
+ *     keeps every crop inside its image (dataset.ImageStoreHBM.batch checks it). */
+#define DHZ_RAGGED_DESC_WORDS 5
+int dhz_crop_augment_pair_ragged(const uint8_t* gt_pool, const uint8_t* hazy_pool, const int64_t* desc, float* out_gt, float* out_hazy,
+                                 const float* norm, int n, int h, int w, void* stream);
 
 /* K6  shift mask builder: mask[nW,64,64] in {0,-100}  (M1:803-836), Hres x Wres map, win 8. */
 int dhz_shift_mask(float* mask, int Hres, int Wres, int shift, void* stream);

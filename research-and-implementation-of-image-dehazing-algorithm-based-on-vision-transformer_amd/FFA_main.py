@@ -21,7 +21,19 @@ trains its FFA baseline with, as opposed to My_train.py --arch FFA, which trains
 
 Differences from the reference's script: one process, no DataParallel; data in HBM like My_train.py (--synthetic N, --train_dir / --val_dir
 directories of PNG pairs through dataset.PatchStoreHBM and the crop / augment kernel, or `.pt` files); the loss values are fetched every
---log_every steps instead of every step (no host sync inside the step); --deterministic.  The ITS / OTS loaders are not restated.
+--log_every steps instead of every step (no host sync inside the step); --deterministic.
+
+The reference's loader (FFA_model/data_utils.py, RESIDE_Dataset) is restated by dataset.ImageStoreHBM and the feed kernel
+dhz_crop_augment_pair_ragged: folders whose images differ in size (I-HAZE, O-HAZE), RESIDE's layout with --pairing reside (hazy `1400_1.png` /
+`1400_1_0.85.png` -> clear `1400` + --clear_format, many hazy frames per clear frame, the larger clear frame centre-cropped to the hazy
+frame's size) and, with --normalize, the input normalisation of data_utils.py:79 (mean 0.64 / 0.6 / 0.58, std 0.14 / 0.15 / 0.152) on the
+training batches in the feed kernel and on the validation inputs once at load time.  A checkpoint trained with --normalize has the same
+keys as any other; evaluate it with `FFA_test.py --normalize`.  The store is chosen by dataset.train_store: a folder of equally many gt and
+hazy PNGs of one size without these options stays on PatchStoreHBM, draw for draw as before; crops are drawn from the items that hold them
+(ImageStoreHBM.eligible - the same torch.randint draw when all do) and --whole_img batches of a mixed-size store from one size bucket
+(draw_whole_batch).  NOT restated: the reference's redraw loop for images smaller than the crop (data_utils.py:54-56), the zero-padding of a
+clear frame smaller than its hazy frame (an error here) and PIL's no-expand 90 degree rotation of non-square frames.  Stores larger than
+one device's memory (OTS) are out of scope.
 """
 import argparse
 import math
@@ -89,6 +101,12 @@ def parse(argv=None):
     parser.add_argument('--ssimloss', type=nonneg_float, default=0,
                         help="weight of the SSIM loss 1 - ssim(out, y) on the HIP kernels (FFA_model/metrics.py's ssim: 11 x 11 Gaussian "
                              "window, both images clamped); 0: off")
+    parser.add_argument('--pairing', choices=('sorted', 'reside'), default='sorted',
+                        help="how <train_dir>/hazy maps to <train_dir>/gt: sorted = one to one in sorted order; reside = hazy `1400_1.png` "
+                             "-> gt `1400` + --clear_format (FFA_model/data_utils.py:58-60)")
+    parser.add_argument('--clear_format', type=str, default='.png', help="--pairing reside: extension of the clear frames (OTS: .jpg)")
+    parser.add_argument('--normalize', action='store_true',
+                        help="normalise the hazy input with the mean / std of FFA_model/data_utils.py:79 (evaluate with FFA_test.py --normalize)")
     opt = parser.parse_args(argv)
     opt.model_name = 'My_NH' + '_' + opt.net.split('.')[0] + '_' + str(opt.gps) + '_' + str(opt.blocks)
     opt.model_path = opt.model_dir + opt.model_name          # option.py:38: a prefix, not a directory join
@@ -178,20 +196,34 @@ def main(argv=None):
 
     # ---- data (HBM resident)
     store = tgt_all = inp_all = None
+    ragged = False                                 # an ImageStoreHBM: sizes differ, RESIDE pairing or --normalize
     if opt.synthetic > 0:
         size = (opt.height, opt.width) if opt.whole_img else opt.crop_size
         tgt_all, inp_all = synthetic_batch(opt.synthetic, size, seed=1234, device=dev)
         vt, vi = synthetic_batch(opt.val_synthetic, size, seed=4321, device=dev)
     elif os.path.isdir(opt.train_dir):
-        from dataset import DataLoaderVal, PatchStoreHBM
-        store = PatchStoreHBM.from_dir(opt.train_dir, dev)
+        from dataset import DataLoaderVal, ImageStoreHBM, train_store
+        store = train_store(opt.train_dir, dev, pairing=opt.pairing, clear_format=opt.clear_format, normalize=opt.normalize)
+        ragged = isinstance(store, ImageStoreHBM)
         val_set = DataLoaderVal(opt.val_dir)
         items = [val_set[i] for i in range(len(val_set))]
         vt, vi = [v[0].to(dev) for v in items], [v[1].to(dev) for v in items]
     else:
         tgt_all, inp_all = load_pairs(opt.train_dir, dev)
         vt, vi = load_pairs(opt.val_dir, dev)
+    norm = None
+    if opt.normalize:                              # data_utils.py:79; the store's batches are normalised by the feed kernel
+        from dataset import RESIDE_MEAN, RESIDE_STD
+        norm = (RESIDE_MEAN, RESIDE_STD)
+        mean, std = (torch.tensor(v, device=dev).view(3, 1, 1) for v in norm)
+        vi = [(v - mean) / std for v in vi] if isinstance(vi, list) else (vi - mean) / std
+        if inp_all is not None:
+            inp_all = (inp_all - mean) / std
     n_train = len(store) if store is not None else tgt_all.shape[0]
+    pick = None                                    # the item ids a crop batch is drawn from, where not all of them hold the crop
+    if store is not None and ragged and not opt.whole_img:
+        pick = store.eligible(opt.crop_size, opt.crop_size)
+        n_train = len(pick)
 
     def state(step):
         return {'step': step, 'max_psnr': max_psnr, 'max_ssim': max_ssim, 'ssims': ssims, 'psnrs': psnrs, 'losses': losses,
@@ -206,8 +238,15 @@ def main(argv=None):
             lr = lr_schedule_cosdecay(step, opt.steps, opt.lr)
             for g in optimizer.param_groups:
                 g["lr"] = lr
-        sel = torch.randint(n_train, (opt.bs,))          # main.py:84: a fresh shuffled batch every step
-        if store is not None:
+        if ragged and opt.whole_img and store.uniform is None:
+            sel = store.draw_whole_batch(opt.bs)         # whole images of mixed sizes: one size per batch
+        else:
+            sel = torch.randint(n_train, (opt.bs,))      # main.py:84: a fresh shuffled batch every step
+            if pick is not None:
+                sel = pick[sel]
+        if ragged:
+            y, x = store.batch(sel.tolist(), None if opt.whole_img else opt.crop_size, normalize=norm)
+        elif store is not None:
             y, x = store.batch(sel.tolist(), None if opt.whole_img else opt.crop_size)
         else:
             y, x = tgt_all[sel.to(dev)], inp_all[sel.to(dev)]

@@ -13,7 +13,9 @@ What is different by design:
     2/3 ask for fp32);
   * data lives in HBM: `--train_dir/--val_dir` directories of PNG pairs (<dir>/gt, <dir>/hazy; dataset.py) are decoded
     once into uint8 tensors on the device and every batch (random crop, 8 rotate/flip augmentations, /255) is one kernel
-    launch (dataset.PatchStoreHBM, dhz_crop_augment_pair) instead of DataLoader workers + PCIe per step; a `.pt` file
+    launch (dataset.PatchStoreHBM, dhz_crop_augment_pair) instead of DataLoader workers + PCIe per step; a folder whose images
+    differ in size (I-HAZE, O-HAZE frames instead of pre-cut patches) goes to dataset.ImageStoreHBM and dhz_crop_augment_pair_ragged,
+    and the --train_ps crops are drawn from the images that hold one; a `.pt` file
     holding {'target': [N,3,H,W], 'input': [N,3,H,W]} float tensors in [0,1] is accepted too; `--synthetic N` trains
     on N synthetic haze pairs per epoch.
 """
@@ -159,13 +161,16 @@ def main():
         torch.cuda.manual_seed_all(1234 + rank)
 
     # ---- data (HBM resident)
-    store = None
+    store = pick = None
     if opt.synthetic > 0:
         tgt_all, inp_all = synthetic_batch(opt.synthetic, opt.train_ps, seed=1234 + rank, device=dev)
         vt, vi = synthetic_batch(opt.val_synthetic, opt.train_ps, seed=4321, device=dev)
     elif os.path.isdir(opt.train_dir):
-        from dataset import PatchStoreHBM, DataLoaderVal
-        store = PatchStoreHBM.from_dir(opt.train_dir, dev, rank, world)       # this rank's share of the patch pairs
+        from dataset import ImageStoreHBM, DataLoaderVal, train_store
+        # this rank's share of the patch pairs: PatchStoreHBM as before for patches of one size, ImageStoreHBM for images of mixed sizes
+        store = train_store(opt.train_dir, dev, rank, world)
+        if isinstance(store, ImageStoreHBM):
+            pick = store.eligible(opt.train_ps, opt.train_ps)               # crops come from the images that hold them
         val_set = DataLoaderVal(opt.val_dir)
         val_items = [val_set[i] for i in range(len(val_set))]
         vt = torch.stack([v[0] for v in val_items]).to(dev)
@@ -176,6 +181,8 @@ def main():
         vt, vi = load_pairs(opt.val_dir, dev)
         tgt_all, inp_all = tgt_all[rank::world], inp_all[rank::world]
     n_train = len(store) if store is not None else tgt_all.shape[0]
+    if pick is not None:
+        n_train = len(pick)
     n_epoch = n_train
     if world > 1:
         # rank::world shards differ by one item when N % world != 0: every rank must run the SAME number of steps (a rank
@@ -218,6 +225,8 @@ def main():
         epoch_loss = torch.zeros((), device=dev)
         for i in range(steps_per_epoch):
             sel = perm[:n_epoch][i * opt.batch_size:(i + 1) * opt.batch_size]
+            if pick is not None:
+                sel = pick[sel]
             if store is not None:
                 target, input_ = store.batch(sel.tolist(), opt.train_ps)
             else:

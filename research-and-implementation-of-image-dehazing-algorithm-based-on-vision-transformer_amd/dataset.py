@@ -195,3 +195,203 @@ class PatchStoreHBM:
         _lib.call("dhz_crop_augment_pair", self.gt.data_ptr(), self.hazy.data_ptr(), tab_d.data_ptr(), _p(clean), _p(noisy),
                   n, self.H, self.W, ps, _stream())
         return clean, noisy
+
+
+RESIDE_MEAN, RESIDE_STD = (0.64, 0.6, 0.58), (0.14, 0.15, 0.152)          # FFA_model/data_utils.py:79, test.py:54
+_PIL_EXT = ('.png', '.jpg', '.jpeg')
+
+
+def center_crop_origin(Hc, Wc, Hh, Wh):
+    """(top, left) of torchvision's CenterCrop((Hh, Wh)) on an Hc x Wc image, restated: int(round(d / 2.0)) with Python's round, half to
+    even - differences 1, 3, 5, 7 give 0, 2, 2, 4."""
+    return int(round((Hc - Hh) / 2.0)), int(round((Wc - Wh) / 2.0))
+
+
+def _image_hw(path):
+    """(H, W) from the file's header, nothing decoded"""
+    from PIL import Image
+    with Image.open(path) as im:
+        return im.size[1], im.size[0]
+
+
+class ImageStoreHBM:
+    """Image pairs of ANY sizes in HBM: FFA_model/data_utils.py's RESIDE_Dataset (lines 51-81) as two uint8 pools + one kernel launch per
+    batch (dhz_crop_augment_pair_ragged).  Item i is hazy frame i; several hazy frames may share one clear frame, which is stored once
+    (RESIDE ITS: 13 990 hazy frames for 1 399 clear ones), and a clear frame larger than its hazy frame is centre-cropped to it
+    (data_utils.py:61; ITS: 640 x 480 against 620 x 460) - kept as an origin per item (center_crop_origin), no copy of the clear frame.
+
+    pairs: a sequence of (clear, hazy) uint8 [H,W,3] tensors or arrays.  Pairs that hold the SAME clear object share its storage.
+
+    Not restated: the reference zero-pads a clear frame smaller than its hazy frame (CenterCrop pads) - here that is an error; it redraws
+    the index until the image holds the crop (data_utils.py:54-56, randint(0, 20000)) - here callers draw from eligible(h, w); and
+    FF.rotate's no-expand 90 degree turns of non-square frames (see PatchStoreHBM.batch)."""
+
+    def __init__(self, pairs, device):
+        pairs = list(pairs)
+        if not pairs:
+            raise ValueError("ImageStoreHBM: no image pairs")
+        clear_of, clears, seen = [], [], {}
+        for clear, _ in pairs:
+            if id(clear) not in seen:
+                seen[id(clear)] = len(clears)
+                clears.append(clear)
+            clear_of.append(seen[id(clear)])
+        self._layout([tuple(h.shape[:2]) for _, h in pairs], [tuple(c.shape[:2]) for c in clears], clear_of, device)
+        for j, c in enumerate(clears):
+            self._put(self.gt_pool, self.clear_off[j], self.clear_hw[j], c)
+        for i, (_, h) in enumerate(pairs):
+            self._put(self.hazy_pool, self.hazy_off[i], self.hazy_hw[i], h)
+
+    def _layout(self, hazy_hw, clear_hw, clear_of, device, names=None):
+        """offsets (in pixels) of every image in its pool, the centre-crop origins, the size buckets; allocates the pools"""
+        self.device = torch.device(device)
+        self.hazy_hw, self.clear_hw, self.clear_of = list(hazy_hw), list(clear_hw), list(clear_of)
+        self.N = len(self.hazy_hw)
+        self.hazy_off, self.clear_off, self.origin = [], [], []
+        at = 0
+        for H, W in self.hazy_hw:
+            self.hazy_off.append(at)
+            at += H * W
+        n_hazy, at = at, 0
+        for H, W in self.clear_hw:
+            self.clear_off.append(at)
+            at += H * W
+        for i, ((Hh, Wh), j) in enumerate(zip(self.hazy_hw, self.clear_of)):
+            Hc, Wc = self.clear_hw[j]
+            if Hc < Hh or Wc < Wh:
+                who = f" ({names[i]})" if names else ""
+                raise ValueError(f"ImageStoreHBM: item {i}{who}: the clear frame {Hc} x {Wc} is smaller than its hazy frame {Hh} x {Wh} "
+                                 "(the reference would zero-pad it; not restated)")
+            self.origin.append(center_crop_origin(Hc, Wc, Hh, Wh))
+        self.hazy_pool = torch.empty(n_hazy * 3, dtype=torch.uint8, device=self.device)
+        self.gt_pool = torch.empty(at * 3, dtype=torch.uint8, device=self.device)
+        self._buckets = {}
+        for i, hw in enumerate(self.hazy_hw):
+            self._buckets.setdefault(hw, []).append(i)
+        self._buckets = {hw: torch.tensor(ids, dtype=torch.long) for hw, ids in self._buckets.items()}
+        self.uniform = self.hazy_hw[0] if len(self._buckets) == 1 else None          # (H, W) when every hazy frame has it
+        self._eligible = {}
+        self._table = self._draws = None
+
+    @staticmethod
+    def _put(pool, off, hw, img):
+        if isinstance(img, np.ndarray):
+            img = torch.from_numpy(np.array(img))               # (a copy: PIL's arrays are read-only)
+        assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[-1] == 3 and tuple(img.shape[:2]) == tuple(hw)
+        pool[off * 3:(off + hw[0] * hw[1]) * 3].copy_(img.contiguous().view(-1))
+
+    @classmethod
+    def from_dir(cls, rgb_dir, device, rank=0, world=1, pairing="sorted", clear_format=".png"):
+        """pairing "sorted": sorted <dir>/gt PNGs against sorted <dir>/hazy PNGs one to one (PatchStoreHBM's rule), sizes free.
+        pairing "reside": every <dir>/hazy file PIL opens (.png, .jpg, .jpeg) belongs to <dir>/gt/<stem up to the first "_"> +
+        clear_format (`1400_1.png`, `1400_1_0.85.png` -> `1400.png`).  Ranks take hazy[rank::world] and load only the clear frames their
+        share names.  Sizes are read from the headers first, then every file is decoded once, straight into its place in the pool."""
+        if pairing == "sorted":
+            clean, noisy = _pair_files(rgb_dir)
+            if len(clean) != len(noisy):
+                raise ValueError(f"ImageStoreHBM.from_dir: {len(clean)} gt against {len(noisy)} hazy PNGs under {rgb_dir} cannot pair one to "
+                                 "one (pairing='sorted'); RESIDE's layout is pairing='reside'")
+            clean, noisy = clean[rank::world], noisy[rank::world]
+            clear_files, clear_of = clean, list(range(len(clean)))
+        elif pairing == "reside":
+            noisy = [os.path.join(rgb_dir, 'hazy', f) for f in sorted(os.listdir(os.path.join(rgb_dir, 'hazy')))
+                     if f.lower().endswith(_PIL_EXT)][rank::world]
+            clear_files, clear_of, seen = [], [], {}
+            for f in noisy:
+                want = os.path.join(rgb_dir, 'gt', os.path.splitext(os.path.basename(f))[0].split('_')[0] + clear_format)
+                if want not in seen:
+                    if not os.path.exists(want):
+                        raise FileNotFoundError(f"ImageStoreHBM.from_dir: hazy frame {f} has no clear frame {want}")
+                    seen[want] = len(clear_files)
+                    clear_files.append(want)
+                clear_of.append(seen[want])
+        else:
+            raise ValueError(f"ImageStoreHBM.from_dir: pairing={pairing!r}")
+        if not noisy:
+            raise ValueError(f"no image pairs under {rgb_dir}/gt and {rgb_dir}/hazy")
+        self = cls.__new__(cls)
+        self._layout([_image_hw(f) for f in noisy], [_image_hw(f) for f in clear_files], clear_of, device, names=noisy)
+        self.hazy_files, self.clear_files = noisy, clear_files
+        for j, f in enumerate(clear_files):
+            self._put(self.gt_pool, self.clear_off[j], self.clear_hw[j], load_img_u8(f))
+        for i, f in enumerate(noisy):
+            self._put(self.hazy_pool, self.hazy_off[i], self.hazy_hw[i], load_img_u8(f))
+        return self
+
+    def __len__(self):
+        return self.N
+
+    def eligible(self, h, w):
+        """LongTensor of the item ids whose hazy frame holds an h x w crop (cached per size): what a caller draws from instead of the
+        reference's redraw loop"""
+        key = (int(h), int(w))
+        if key not in self._eligible:
+            ids = [i for i, (H, W) in enumerate(self.hazy_hw) if H >= key[0] and W >= key[1]]
+            if not ids:
+                raise ValueError(f"ImageStoreHBM.eligible: no stored image holds a {key[0]} x {key[1]} crop")
+            self._eligible[key] = torch.tensor(ids, dtype=torch.long)
+        return self._eligible[key]
+
+    def draw_whole_batch(self, bs):
+        """item ids of ONE size for a batch of whole images: torch.randint(N) picks an anchor, whose size names the bucket - so buckets
+        come up in proportion to their counts -, then torch.randint(len(bucket), (bs,)) picks the items"""
+        anchor = int(torch.randint(self.N, (1,)))
+        bucket = self._buckets[self.hazy_hw[anchor]]
+        return bucket[torch.randint(len(bucket), (bs,))]
+
+    def batch(self, indices, ps, normalize=None):
+        """(clean, noisy) float32 [n,3,h,w] on the device.  ps: an int, (h, w), or None - whole images, which then must share one size.  Per
+        item, in item order, (r, c, k) = draw_rect_aug(H_i, W_i, h, w) with the item's own size (an int ps: draw_crop_aug), so on a store
+        whose images share one size the draws and the output are PatchStoreHBM.batch's bit for bit.  normalize: None, or (mean, std) of
+        three floats each - the hazy output becomes (v / 255 - mean) / std in fp32 (ToTensor + Normalize, data_utils.py:78-79); the clear
+        output never is.  One pinned descriptor upload per batch."""
+        import ctypes
+        from dehaze_hip import _lib
+        from dehaze_hip.ops import _p, _stream
+        idx = [int(i) % self.N for i in indices]
+        n = len(idx)
+        if ps is None:
+            sizes = {self.hazy_hw[i] for i in idx}
+            if len(sizes) != 1:
+                raise ValueError(f"ImageStoreHBM.batch: whole images of {len(sizes)} different sizes in one batch (draw_whole_batch)")
+            h, w = next(iter(sizes))
+        else:
+            h, w = (int(ps), int(ps)) if isinstance(ps, int) else (int(ps[0]), int(ps[1]))
+        for i in idx:
+            H, W = self.hazy_hw[i]
+            if not (0 < h <= H and 0 < w <= W):
+                raise ValueError(f"ImageStoreHBM.batch: a {h} x {w} crop does not fit the stored {H} x {W} image {i} (eligible)")
+        rows, draws = [], []
+        for i in idx:
+            (H, W), j = self.hazy_hw[i], self.clear_of[i]
+            r, c, k = draw_rect_aug(H, W, h, w)
+            top, left = self.origin[i]
+            Wc = self.clear_hw[j][1]
+            rows.append((self.hazy_off[i] + r * W + c, W, self.clear_off[j] + (top + r) * Wc + left + c, Wc, k))
+            draws.append((i, r, c, k))
+        tab = torch.tensor(rows, dtype=torch.int64)
+        if self.device.type == "cuda":
+            tab = tab.pin_memory()
+        self._table = tab                                       # keep the pinned buffer alive until the copy ran
+        self._draws = torch.tensor(draws, dtype=torch.int32)    # (id, r, c, k) per item: PatchStoreHBM's table
+        tab_d = tab.to(self.device, non_blocking=True)
+        norm = None
+        if normalize is not None:
+            mean, std = normalize
+            norm = (ctypes.c_float * 6)(*[float(v) for v in tuple(mean) + tuple(std)])
+        clean = torch.empty((n, 3, h, w), device=self.device, dtype=torch.float32)
+        noisy = torch.empty_like(clean)
+        _lib.call("dhz_crop_augment_pair_ragged", self.gt_pool.data_ptr(), self.hazy_pool.data_ptr(), tab_d.data_ptr(), _p(clean),
+                  _p(noisy), norm, n, h, w, _stream())
+        return clean, noisy
+
+
+def train_store(rgb_dir, device, rank=0, world=1, pairing="sorted", clear_format=".png", normalize=False):
+    """The store a training script feeds from.  PatchStoreHBM, built exactly as before, wherever it can serve: sorted pairing, as many gt
+    as hazy PNGs, one size throughout (read from the headers of the WHOLE folder, so every rank decides alike), no normalisation.
+    ImageStoreHBM otherwise."""
+    if pairing == "sorted" and not normalize:
+        clean, noisy = _pair_files(rgb_dir)
+        if len(clean) == len(noisy) and len({_image_hw(f) for f in clean + noisy}) <= 1:
+            return PatchStoreHBM.from_dir(rgb_dir, device, rank, world)
+    return ImageStoreHBM.from_dir(rgb_dir, device, rank, world, pairing=pairing, clear_format=clear_format)

@@ -211,6 +211,8 @@ SIGNATURES = {
     "dhz_l1_pair_fwd_any": [c_f, c_f, c_f, c_f, c_l, c_p],
     "dhz_l1_pair_bwd_any": [c_f, c_f, c_f, c_f, c_f, c_l, c_p],
     "dhz_crop_augment_pair_rect": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_p],
+    # the feed for pools of images of any sizes: (gt pool, hazy pool, int64 descriptor rows, out gt, out hazy, host norm[6] | NULL, n, h, w)
+    "dhz_crop_augment_pair_ragged": [c_p, c_p, c_p, c_f, c_f, c_p, c_i, c_i, c_i, c_p],
     # SSIM / squared error of image pairs in float64 (csrc/metrics.hip)
     "dhz_ssim_pair_workspace_bytes": [c_i, c_i, c_i, c_i],
     "dhz_ssim_pair": [c_p, c_p, c_f, c_l, c_l, c_f, c_l, c_l, c_i, c_i, c_i, c_i, c_i, c_f, ctypes.c_double, c_i, ctypes.c_double,
