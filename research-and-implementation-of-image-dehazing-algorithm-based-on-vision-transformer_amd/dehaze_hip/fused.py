@@ -1,9 +1,9 @@
 """The two branches of a LeWin block (M1:839-873) as hand-sequenced kernel chains behind autograd nodes.
 
 attention branch : out = x + drop_scale * OutProj(ProbAttn(QKV(partition(roll(LN(x))))))           (M1:839-872)
-    forward  : ONE kernel (dhz_fused_window_attn_fwd) where it wins, else dhz_ln_partition_fwd -> QKV GEMM -> dhz_ps_attn_fwd ->
+    forward  : ONE kernel (dhz_fused_window_attn_fwd) where it wins, else dhz_ln_partition_fwd -> QKV GEMM -> dhz_ps_attn_fwd_w ->
                out-projection GEMM whose EPILOGUE is window reverse + un-roll + DropPath factor + residual (ops.gemm_fwd_res)
-    backward : out-proj dgrad + wgrad -> dhz_ps_attn_bwd (+ bias table gradient) -> QKV dgrad + wgrad (ONE kernel over d(qkv) at C = 64,
+    backward : out-proj dgrad + wgrad -> dhz_ps_attn_bwd_w (+ bias table gradient) -> QKV dgrad + wgrad (ONE kernel over d(qkv) at C = 64,
                ops.linear_bwd_pair; so is linear1's backward of the LeFF / Mlp branch at C = 32 / 64) -> dhz_ln_partition_bwd with
                the shortcut gradient folded in (dx = dout + dLN) - no autograd-side accumulation kernels at all
 LeFF / Mlp branch: out = x + drop_scale * linear2(gelu(dwconv(gelu(linear1(LN(x))))))                (M1:873)
@@ -126,7 +126,7 @@ def _flush_table_grads():
                   arr([_p(g) for _, _, g, _ in part]), ints([H for _, _, _, H in part]), len(part), _stream())
 
 
-def _table_backward(dpart, parts, table_p, H, dev):
+def _table_backward(dpart, parts, table_p, H):
     gt = _grad_buf(table_p)
     if gt is not None and DEFER_TABLE_GRADS and ops.GRAD_READY is None:
         queued = bool(_PENDING_TABLES)
@@ -140,12 +140,10 @@ def _table_backward(dpart, parts, table_p, H, dev):
             _PENDING_TABLES.append((dpart, parts, gt, H))
             return None
     if gt is not None:
-        _lib.call("dhz_bias_table_grad", _p(dpart), parts, _p(gt), H, 1, _stream())
+        ops.bias_table_grad(dpart, parts, H, out=gt, accumulate=True)
         _ready(table_p)
         return None
-    dtable = torch.empty((225, H), device=dev, dtype=torch.float32)
-    _lib.call("dhz_bias_table_grad", _p(dpart), parts, _p(dtable), H, 0, _stream())
-    return dtable
+    return ops.bias_table_grad(dpart, parts, H)
 
 
 # ----------------------------------------------------------------------------- per-forward staging of parameter-derived operands
@@ -230,9 +228,7 @@ def _bias_tile(table, H, dev):
     hit = STAGED_BIAS.pop(id(table), None)
     if hit is not None and hit[0] is table and hit[1].shape[0] == H and hit[1].device == dev:
         return hit[1]
-    bias = torch.empty((H, NTOK, NTOK), device=dev, dtype=torch.float32)
-    _lib.call("dhz_bias_gather", _p(table.contiguous()), _p(bias), H, _stream())
-    return bias
+    return ops.bias_tile(table, H)
 
 
 # ----------------------------------------------------------------------------- attention branch: forward / backward as functions
@@ -307,8 +303,8 @@ def _attn_fused_fwd(train, x, gamma, beta, wq, bq, wk, bk, wv, bv, wo, bo, table
 
 
 def _attn_chain_fwd(train, x, gamma, beta, wq, bq, wk, bk, wv, bv, wo, bo, table, idx, mask, dscale, Hres, Wres, shift, H, pad=None):
-    """dhz_ln_partition_fwd -> QKV GEMM -> dhz_ps_attn_fwd -> out-projection GEMM with the residual epilogue (K4 inside the GEMM); pad: the
-    padding words of the B nW windows (inference only: dhz_ps_attn_fwd_dt_pad)"""
+    """dhz_ln_partition_fwd -> QKV GEMM -> dhz_ps_attn_fwd_w -> out-projection GEMM with the residual epilogue (K4 inside the GEMM); pad:
+    the padding words of the B nW windows (inference only: dhz_ps_attn_fwd_w_pad)"""
     _require_gpu(x, gamma, beta, wq, wo, table, idx, mask, dscale)
     assert pad is None or not train, "padding words under autograd: LeWinTransformerBlock.forward runs ops.ps_window_attention"
     x = x.contiguous()
@@ -355,7 +351,7 @@ def _attn_bwd_fused(rec, dout):
     _lib.call("dhz_fused_window_attn_bwd", _p(x), _p(dout.contiguous()), _p(gamma), _p(beta), _p(wqkv_p), _p(bqkv), _p(wt),
               _p(bias), _p(mask), _p(dscale), _p(rank), _p(dx), _p(gwq), _p(gwk), _p(gwv), _p(gbq), _p(gbk), _p(gbv), _p(gwo),
               _p(gbo), _p(gg), _p(gb), _p(dpart), B, Hres, Wres, C, shift, _stream())
-    dtable = _table_backward(dpart, parts, table_p, H, dev) if bias is not None else None
+    dtable = _table_backward(dpart, parts, table_p, H) if bias is not None else None
     if inplace:
         _ready(*[p for p in plist if p is not None])
         return (dx, None, None, None, None, None, None, None, None, None, None, dtable)
@@ -398,10 +394,10 @@ def _attn_bwd(rec, dout, windowed=False, daw_pre=None):
         g_wo, g_bo = _wgrad(daw, 0, cx, wo, bo)
     # (3) attention core
     dqkv = torch.empty_like(qkv)
-    parts = _lib.load().dhz_ps_attn_bwd_parts_d(B_, H, d)
+    parts = ops.ps_attn_bwd_parts(B_, H, d)
     dpart = torch.empty((parts, NTOK, NTOK), **f32) if bias is not None else None
     ops.ps_attn_bwd_launch(qkv, dqkv, bias, mask, rank, dctx, dpart, B_, H, d)
-    dtable = _table_backward(dpart, parts, table_p, H, dev) if bias is not None else None
+    dtable = _table_backward(dpart, parts, table_p, H) if bias is not None else None
     # (4) QKV projection
     dxn, (g_wq, g_bq, g_wk, g_bk, g_wv, g_bv) = ops.linear_bwd_pair(dqkv, xn, ops.cat_rows([wq_.detach(), wk_.detach(), wv_.detach()]),
                                                                     [(wq, bq), (wk, bk), (wv, bv)])          # x read once

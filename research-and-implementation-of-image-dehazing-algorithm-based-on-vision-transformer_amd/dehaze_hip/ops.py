@@ -536,75 +536,58 @@ def _pad_nw(pad, mask, B_, nW):
     return mask.shape[0] if mask is not None else (nW or B_)
 
 
+# Every window-side op below makes ONE call, to the `_w` entry of include/dehaze_hip.h with win = _win_of(N): at win = 8 that entry runs
+# the function behind the entry without `_w` (dhz_ps_attn_fwd_dt, dhz_bias_gather, ...) with the same arguments - the same kernel
+# instance, the same bits (tests/test_gpu_win4_kernels.py pins it) - so there is nothing for Python to choose.
+def _pad_splice(pad, mask, B_, nW):
+    """("_pad", the pad word as the argument behind `mask`, windows per image) of a launch with padding words, else ("", nothing, the
+    shift mask's window count)"""
+    if pad is None:
+        return "", (), (mask.shape[0] if mask is not None else 1)
+    return "_pad", (_p(pad),), _pad_nw(pad, mask, B_, nW)
+
+
 def ps_attn_fwd_launch(qkv, idx, bias, mask, out, rank, B_, H, d, N=NTOK, pad=None, nW=None):
-    """dhz_ps_attn_fwd_dt (N = 64) / dhz_ps_attn_fwd_w (N = 16) on a packed [T, 3C] buffer (columns [Q | K | V]), inside bench.py's
-    timing bracket; pad: the padding words of the B_ windows (dhz_ps_attn_fwd_dt_pad / dhz_ps_attn_fwd_w_pad), nW: windows per image"""
+    """dhz_ps_attn_fwd_w on a packed [T, 3C] buffer (columns [Q | K | V]), inside bench.py's timing bracket; pad: the padding words of
+    the B_ windows (dhz_ps_attn_fwd_w_pad), nW: windows per image"""
     C, es, base = H * d, qkv.element_size(), qkv.data_ptr()
-    if pad is not None:
-        nW = _pad_nw(pad, mask, B_, nW)
-        ev = _timed("dhz_ps_attn_fwd")
-        if N == NTOK:
-            _lib.call("dhz_ps_attn_fwd_dt_pad", base, base + es * C, base + 2 * es * C, 3 * C, _p(idx), _p(bias), _p(mask), _p(pad), _p(out), C,
-                      _p(rank), B_, H, nW, d, _dt(qkv), _stream())
-        else:
-            _lib.call("dhz_ps_attn_fwd_w_pad", base, base + es * C, base + 2 * es * C, 3 * C, _p(idx), _p(bias), _p(mask), _p(pad), _p(out), C,
-                      _p(rank), B_, H, nW, d, _win_of(N), _dt(qkv), _stream())
-        _timed_end(ev, B_ * H * 4 * N * d * es)
-        return
-    nW = mask.shape[0] if mask is not None else 1
+    sfx, padarg, nW = _pad_splice(pad, mask, B_, nW)
     ev = _timed("dhz_ps_attn_fwd")
-    if N == NTOK:
-        _lib.call("dhz_ps_attn_fwd_dt", base, base + es * C, base + 2 * es * C, 3 * C, _p(idx), _p(bias), _p(mask), _p(out), C, _p(rank), B_, H,
-                  nW, d, _dt(qkv), _stream())
-    else:
-        _lib.call("dhz_ps_attn_fwd_w", base, base + es * C, base + 2 * es * C, 3 * C, _p(idx), _p(bias), _p(mask), _p(out), C, _p(rank), B_, H,
-                  nW, d, _win_of(N), _dt(qkv), _stream())
+    _lib.call("dhz_ps_attn_fwd_w" + sfx, base, base + es * C, base + 2 * es * C, 3 * C, _p(idx), _p(bias), _p(mask), *padarg, _p(out), C,
+              _p(rank), B_, H, nW, d, _win_of(N), _dt(qkv), _stream())
     _timed_end(ev, B_ * H * 4 * N * d * es)
 
 
 def ps_attn_bwd_launch(qkv, dqkv, bias, mask, rank, dout, dpart, B_, H, d, N=NTOK, pad=None, nW=None):
-    """dhz_ps_attn_bwd_dt (N = 64) / dhz_ps_attn_bwd_w (N = 16): packed qkv / dqkv [T, 3C]; pad / nW as in ps_attn_fwd_launch
-    (dhz_ps_attn_bwd_dt_pad / dhz_ps_attn_bwd_w_pad)"""
+    """dhz_ps_attn_bwd_w: packed qkv / dqkv [T, 3C]; pad / nW as in ps_attn_fwd_launch (dhz_ps_attn_bwd_w_pad)"""
     C, es, base, gb = H * d, qkv.element_size(), qkv.data_ptr(), dqkv.data_ptr()
-    if pad is not None:
-        nW = _pad_nw(pad, mask, B_, nW)
-        if N == NTOK:
-            _lib.call("dhz_ps_attn_bwd_dt_pad", base, base + es * C, base + 2 * es * C, 3 * C, _p(bias), _p(mask), _p(pad), _p(rank), _p(dout), C,
-                      gb, gb + es * C, gb + 2 * es * C, 3 * C, _p(dpart), B_, H, nW, d, _dt(qkv), _stream())
-        else:
-            _lib.call("dhz_ps_attn_bwd_w_pad", base, base + es * C, base + 2 * es * C, 3 * C, _p(bias), _p(mask), _p(pad), _p(rank), _p(dout), C,
-                      gb, gb + es * C, gb + 2 * es * C, 3 * C, _p(dpart), B_, H, nW, d, _win_of(N), _dt(qkv), _stream())
-        return
-    nW = mask.shape[0] if mask is not None else 1
-    if N == NTOK:
-        _lib.call("dhz_ps_attn_bwd_dt", base, base + es * C, base + 2 * es * C, 3 * C, _p(bias), _p(mask), _p(rank), _p(dout), C,
-                  gb, gb + es * C, gb + 2 * es * C, 3 * C, _p(dpart), B_, H, nW, d, _dt(qkv), _stream())
-    else:
-        _lib.call("dhz_ps_attn_bwd_w", base, base + es * C, base + 2 * es * C, 3 * C, _p(bias), _p(mask), _p(rank), _p(dout), C,
-                  gb, gb + es * C, gb + 2 * es * C, 3 * C, _p(dpart), B_, H, nW, d, _win_of(N), _dt(qkv), _stream())
+    sfx, padarg, nW = _pad_splice(pad, mask, B_, nW)
+    _lib.call("dhz_ps_attn_bwd_w" + sfx, base, base + es * C, base + 2 * es * C, 3 * C, _p(bias), _p(mask), *padarg, _p(rank), _p(dout), C,
+              gb, gb + es * C, gb + 2 * es * C, 3 * C, _p(dpart), B_, H, nW, d, _win_of(N), _dt(qkv), _stream())
+
+
+def ps_attn_bwd_parts(B_, H, d, N=NTOK):
+    """rows of the [parts, N, N] partial bias gradient that dhz_ps_attn_bwd_w / dhz_dense_attn_bwd_w write (dhz_ps_attn_bwd_parts_w)"""
+    return _lib.load().dhz_ps_attn_bwd_parts_w(B_, H, d, _win_of(N))
 
 
 def bias_tile(table, H, N=NTOK):
-    """[H, N, N] relative-position bias of a [(2 win - 1)^2, H] table (M1:408-410)"""
+    """[H, N, N] relative-position bias of a [(2 win - 1)^2, H] table (M1:408-410; dhz_bias_gather_w)"""
     win = _win_of(N)
     assert tuple(table.shape) == ((2 * win - 1) ** 2, H), f"bias table {tuple(table.shape)} for {win}x{win} windows, {H} heads"
     bias = torch.empty((H, N, N), device=table.device, dtype=torch.float32)
-    if N == NTOK:
-        _lib.call("dhz_bias_gather", _p(table.contiguous()), _p(bias), H, _stream())
-    else:
-        _lib.call("dhz_bias_gather_w", _p(table.contiguous()), _p(bias), H, win, _stream())
+    _lib.call("dhz_bias_gather_w", _p(table.contiguous()), _p(bias), H, win, _stream())
     return bias
 
 
-def bias_table_grad(dpart, parts, H, N=NTOK):
-    """[(2 win - 1)^2, H] table gradient from the partial [parts, N, N] tiles of a backward kernel"""
+def bias_table_grad(dpart, parts, H, N=NTOK, out=None, accumulate=False):
+    """[(2 win - 1)^2, H] table gradient from the partial [parts, N, N] tiles of a backward kernel (dhz_bias_table_grad_w), written to a
+    new tensor or to `out`, which it is added to when accumulate"""
     win = _win_of(N)
-    dtable = torch.empty(((2 * win - 1) ** 2, H), device=dpart.device, dtype=torch.float32)
-    if N == NTOK:
-        _lib.call("dhz_bias_table_grad", _p(dpart), parts, _p(dtable), H, 0, _stream())
-    else:
-        _lib.call("dhz_bias_table_grad_w", _p(dpart), parts, _p(dtable), H, 0, win, _stream())
-    return dtable
+    if out is None:
+        out = torch.empty(((2 * win - 1) ** 2, H), device=dpart.device, dtype=torch.float32)
+    _lib.call("dhz_bias_table_grad_w", _p(dpart), parts, _p(out), H, int(accumulate), win, _stream())
+    return out
 
 
 class _PSWindowAttention(Function):
@@ -640,7 +623,7 @@ class _PSWindowAttention(Function):
         dout = dout.contiguous()
         dqkv = torch.empty_like(qkv)
         dpart, dtable = None, None
-        parts = _lib.load().dhz_ps_attn_bwd_parts_d(B_, H, d) if N == NTOK else _lib.load().dhz_ps_attn_bwd_parts_w(B_, H, d, _win_of(N))
+        parts = ps_attn_bwd_parts(B_, H, d, N)
         if bias is not None:
             dpart = torch.empty((parts, N, N), device=qkv.device, dtype=torch.float32)
         ps_attn_bwd_launch(qkv, dqkv, bias, mask, rank, dout, dpart, B_, H, d, N, pad, nW)
@@ -654,7 +637,8 @@ def ps_window_attention(qkv, table, idx, mask, H, d, pad=None, nW=None):
 
 
 def ps_window_attention_rank(qkv, table, idx, mask, H, d):
-    """Forward only; also returns the saved selection ranks [B_,H,N] (tests / diagnostics)."""
+    """Forward only, fp32 storage; also returns the saved selection ranks [B_,H,N] (tests / diagnostics)."""
+    assert qkv.dtype == torch.float32, qkv.dtype
     T = qkv.shape[0]
     C = H * d
     N = idx.shape[0]
@@ -662,14 +646,7 @@ def ps_window_attention_rank(qkv, table, idx, mask, H, d):
     out = torch.empty((T, C), device=qkv.device, dtype=torch.float32)
     rank = torch.empty((B_, H, N), device=qkv.device, dtype=torch.uint8)
     bias = bias_tile(table, H, N) if table is not None else None
-    nW = mask.shape[0] if mask is not None else 1
-    base = qkv.data_ptr()
-    if N == NTOK:
-        _lib.call("dhz_ps_attn_fwd", base, base + 4 * C, base + 8 * C, 3 * C, _p(idx), _p(bias), _p(mask), _p(out), C,
-                  _p(rank), B_, H, nW, d, _stream())
-    else:
-        _lib.call("dhz_ps_attn_fwd_w", base, base + 4 * C, base + 8 * C, 3 * C, _p(idx), _p(bias), _p(mask), _p(out), C,
-                  _p(rank), B_, H, nW, d, _win_of(N), 0, _stream())
+    ps_attn_fwd_launch(qkv, idx, bias, mask, out, rank, B_, H, d, N)
     return out, rank
 
 
@@ -687,12 +664,8 @@ class _DenseWindowAttention(Function):
         bias = bias_tile(table, H, N)
         nW = mask.shape[0] if mask is not None else 1
         base = qkv.data_ptr()
-        if N == NTOK:
-            _lib.call("dhz_dense_attn_fwd", base, base + 4 * C, base + 8 * C, 3 * C, _p(bias), _p(mask), _p(out), C, B_, H,
-                      nW, d, float(scale), _stream())
-        else:
-            _lib.call("dhz_dense_attn_fwd_w", base, base + 4 * C, base + 8 * C, 3 * C, _p(bias), _p(mask), _p(out), C, B_, H,
-                      nW, d, float(scale), _win_of(N), _stream())
+        _lib.call("dhz_dense_attn_fwd_w", base, base + 4 * C, base + 8 * C, 3 * C, _p(bias), _p(mask), _p(out), C, B_, H,
+                  nW, d, float(scale), _win_of(N), _stream())
         ctx.save_for_backward(qkv, bias, mask)
         ctx.dims = (B_, H, d, nW, float(scale), N)
         return out
@@ -704,15 +677,11 @@ class _DenseWindowAttention(Function):
         C = H * d
         dout = dout.contiguous()
         dqkv = torch.empty_like(qkv)
-        parts = _lib.load().dhz_ps_attn_bwd_parts(B_, H) if N == NTOK else _lib.load().dhz_ps_attn_bwd_parts_w(B_, H, d, _win_of(N))
+        parts = ps_attn_bwd_parts(B_, H, d, N)       # (at win = 8 the count does not depend on d: it is dhz_ps_attn_bwd_parts(B_, H))
         dpart = torch.empty((parts, N, N), device=qkv.device, dtype=torch.float32)
         base, gb = qkv.data_ptr(), dqkv.data_ptr()
-        if N == NTOK:
-            _lib.call("dhz_dense_attn_bwd", base, base + 4 * C, base + 8 * C, 3 * C, _p(bias), _p(mask), _p(dout), C,
-                      gb, gb + 4 * C, gb + 8 * C, 3 * C, _p(dpart), B_, H, nW, d, scale, _stream())
-        else:
-            _lib.call("dhz_dense_attn_bwd_w", base, base + 4 * C, base + 8 * C, 3 * C, _p(bias), _p(mask), _p(dout), C,
-                      gb, gb + 4 * C, gb + 8 * C, 3 * C, _p(dpart), B_, H, nW, d, scale, _win_of(N), _stream())
+        _lib.call("dhz_dense_attn_bwd_w", base, base + 4 * C, base + 8 * C, 3 * C, _p(bias), _p(mask), _p(dout), C,
+                  gb, gb + 4 * C, gb + 8 * C, 3 * C, _p(dpart), B_, H, nW, d, scale, _win_of(N), _stream())
         return dqkv, bias_table_grad(dpart, parts, H, N), None, None, None, None, None
 
 
@@ -727,10 +696,7 @@ def shift_mask(Hres, Wres, shift, device, win=8):
     N = win * win
     _win_of(N)
     m = torch.empty(((Hres // win) * (Wres // win), N, N), device=device, dtype=torch.float32)
-    if win == 8:
-        _lib.call("dhz_shift_mask", _p(m), Hres, Wres, shift, _stream())
-    else:
-        _lib.call("dhz_shift_mask_w", _p(m), Hres, Wres, shift, win, _stream())
+    _lib.call("dhz_shift_mask_w", _p(m), Hres, Wres, shift, win, _stream())
     return m
 
 
@@ -996,12 +962,8 @@ class _LNPartition(Function):
         assert L == Hres * Wres
         y = torch.empty((B * L, C), device=x.device, dtype=x.dtype)
         stats = torch.empty((B * L, 2), device=x.device, dtype=torch.float32)
-        if win == 8:
-            _lib.call("dhz_ln_partition_fwd_dt", _p(x), _p(gamma), _p(beta), _p(y), _p(stats), B, Hres, Wres, C, shift,
-                      int(partition), _dt(x), _stream())
-        else:
-            _lib.call("dhz_ln_partition_fwd_w", _p(x), _p(gamma), _p(beta), _p(y), _p(stats), B, Hres, Wres, C, shift,
-                      int(partition), win, _dt(x), _stream())
+        _lib.call("dhz_ln_partition_fwd_w", _p(x), _p(gamma), _p(beta), _p(y), _p(stats), B, Hres, Wres, C, shift,
+                  int(partition), win, _dt(x), _stream())
         ctx.save_for_backward(x, gamma, stats)
         ctx.geom = (B, Hres, Wres, C, shift, int(partition), win)
         return y
@@ -1013,17 +975,14 @@ class _LNPartition(Function):
         dy = dy.contiguous()
         dx = torch.empty_like(x)
         dgb = torch.zeros((2, C), device=x.device, dtype=torch.float32)
-        if win == 8:
-            _lib.call("dhz_ln_partition_bwd_dt", _p(dy), _p(x), _p(gamma), _p(stats), None, _p(dx), dgb[0].data_ptr(),
-                      dgb[1].data_ptr(), B, Hres, Wres, C, shift, partition, _dt(x), _stream())
-        else:
-            _lib.call("dhz_ln_partition_bwd_w", _p(dy), _p(x), _p(gamma), _p(stats), None, _p(dx), dgb[0].data_ptr(),
-                      dgb[1].data_ptr(), B, Hres, Wres, C, shift, partition, win, _dt(x), _stream())
+        _lib.call("dhz_ln_partition_bwd_w", _p(dy), _p(x), _p(gamma), _p(stats), None, _p(dx), dgb[0].data_ptr(),
+                  dgb[1].data_ptr(), B, Hres, Wres, C, shift, partition, win, _dt(x), _stream())
         return dx, dgb[0], dgb[1], None, None, None, None, None
 
 
 def ln_partition(x, gamma, beta, Hres, Wres, shift, win=8):
-    """LayerNorm -> roll(-shift) -> window_partition  (M1:839-852).  [B,L,C] -> [B*nW*win*win, C]."""
+    """LayerNorm -> roll(-shift) -> window_partition  (M1:839-852).  [B,L,C] -> [B*nW*win*win, C].  dhz_ln_partition_fwd_w / _bwd_w: at
+    win = 8 the kernel instances of dhz_ln_partition_fwd_dt / dhz_ln_partition_bwd_dt."""
     _win_of(win * win)
     return _LNPartition.apply(x, gamma, beta, Hres, Wres, shift, True, win)
 
@@ -1042,12 +1001,8 @@ class _ReverseResidual(Function):
         yw = yw.contiguous()
         B, L, C = shortcut.shape
         out = torch.empty_like(shortcut)
-        if win == 8:
-            _lib.call("dhz_reverse_residual_fwd_dt", _p(yw), _p(shortcut), _p(scale), _p(out), B, Hres, Wres, C, shift,
-                      int(partition), _dt(shortcut), _stream())
-        else:
-            _lib.call("dhz_reverse_residual_fwd_w", _p(yw), _p(shortcut), _p(scale), _p(out), B, Hres, Wres, C, shift,
-                      int(partition), win, _dt(shortcut), _stream())
+        _lib.call("dhz_reverse_residual_fwd_w", _p(yw), _p(shortcut), _p(scale), _p(out), B, Hres, Wres, C, shift,
+                  int(partition), win, _dt(shortcut), _stream())
         ctx.save_for_backward(scale)
         ctx.geom = (B, Hres, Wres, C, shift, int(partition), tuple(yw.shape), win)
         return out
@@ -1058,17 +1013,14 @@ class _ReverseResidual(Function):
         B, Hres, Wres, C, shift, partition, yshape, win = ctx.geom
         dout = dout.contiguous()
         dyw = torch.empty(yshape, device=dout.device, dtype=dout.dtype)
-        if win == 8:
-            _lib.call("dhz_reverse_residual_bwd_dt", _p(dout), _p(scale), _p(dyw), B, Hres, Wres, C, shift, partition,
-                      _dt(dout), _stream())
-        else:
-            _lib.call("dhz_reverse_residual_bwd_w", _p(dout), _p(scale), _p(dyw), B, Hres, Wres, C, shift, partition, win,
-                      _dt(dout), _stream())
+        _lib.call("dhz_reverse_residual_bwd_w", _p(dout), _p(scale), _p(dyw), B, Hres, Wres, C, shift, partition, win,
+                  _dt(dout), _stream())
         return dyw, dout, None, None, None, None, None, None
 
 
 def reverse_residual(yw, shortcut, scale, Hres, Wres, shift, win=8):
-    """window_reverse -> roll(+shift) -> shortcut + drop_path(.)  (M1:859-872)."""
+    """window_reverse -> roll(+shift) -> shortcut + drop_path(.)  (M1:859-872).  dhz_reverse_residual_fwd_w / _bwd_w: at win = 8 the
+    kernel instances of dhz_reverse_residual_fwd_dt / dhz_reverse_residual_bwd_dt."""
     _win_of(win * win)
     return _ReverseResidual.apply(yw, shortcut, scale, Hres, Wres, shift, True, win)
 

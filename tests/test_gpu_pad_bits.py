@@ -299,8 +299,8 @@ def test_fused_forward_with_padding_words(C, heads, res, shift, six_term):
     finally:
         _L().call = real
         fused.ATTN_FUSED_P6, fused.ATTN_FUSED_P6_C, fused.ATTN_FUSED_PAD_P6_C = old
-    assert "dhz_fused_window_attn_fwd_pad" in fused_calls and "dhz_ps_attn_fwd_dt_pad" not in fused_calls
-    assert "dhz_ps_attn_fwd_dt_pad" in calls
+    assert "dhz_fused_window_attn_fwd_pad" in fused_calls and "dhz_ps_attn_fwd_w_pad" not in fused_calls
+    assert "dhz_ps_attn_fwd_w_pad" in calls
     err = (yf - yc).abs().max().item()
     print(f"fused vs chain max err {err:.3e}; padding changes the output by {(yf - yn).abs().max().item():.3e}")
     assert torch.allclose(yf, yc, atol=2e-5, rtol=1e-4), err
@@ -446,7 +446,7 @@ def test_block_under_autograd_equals_the_tensor_route(win, res, shift, B):
 
     yt, dxt, gt, ct = run(False)
     yp, dxp, gp, cp = run(True)
-    fwd, bwd = ("dhz_ps_attn_fwd_dt_pad", "dhz_ps_attn_bwd_dt_pad") if win == 8 else ("dhz_ps_attn_fwd_w_pad", "dhz_ps_attn_bwd_w_pad")
+    fwd, bwd = "dhz_ps_attn_fwd_w_pad", "dhz_ps_attn_bwd_w_pad"                       # (ops calls the `_w` entries at either window side)
     assert fwd in cp and bwd in cp and "dhz_pad_window_bits" in cp and "dhz_fused_window_attn_fwd_pad" not in cp
     assert not [n for n in ct if n.endswith("_pad") or n == "dhz_pad_window_bits"]
     assert set(gt) == set(gp) and "attn.relative_position_bias_table" in gp

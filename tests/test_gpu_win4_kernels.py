@@ -404,6 +404,106 @@ def test_layout_entries_win8_run_the_old_entries():
         assert torch.equal(a, b)
 
 
+# eight padding words, none of them 0: bit j = token j of the window is padding (all of a window, one token, halves, scattered bits)
+_PAD_WORDS = [0x00000000FFFFFFFF, 0xFFFFFFFFFFFFFFFF, 1, 0x8421F00F0FF0A5C3, 1 << 63, 0x00FF00FF0000FFFF, (1 << 31) | (1 << 32), 0xF0F0F0F00F0F0F0F]
+
+
+@pytest.mark.parametrize("d", [16, 32])
+def test_attention_bias_and_mask_entries_win8_run_the_old_entries(d):
+    """The property dehaze_hip.ops rests on when it calls the `_w` entries at either window side: with win = 8 every one of them gives the
+    bits of the entry without `_w`.  16 x 16 map (nW = 4 windows per image), B_ = 8 windows, H = 2, shift mask, bias, non-zero padding
+    words; fp32 and bf16 storage where the entry takes a dtype; every output torch.equal.  The old entry runs twice first and must equal
+    itself, so that a difference cannot come from an entry that is not reproducible to begin with.  The table gradient reads integer-valued
+    partial tiles: its sums are then exact in fp32 whatever order the 64-token kernel's LDS atomics take, and parts = 4 H makes it one slice
+    per head, so one workgroup adds to each table cell."""
+    L = _L()
+    lib = L.load()
+    B_, H, nW, Nt = 8, 2, 4, 64
+    C = H * d
+    g = torch.Generator().manual_seed(40 + d)
+    table = (0.3 * torch.randn(225, H, generator=g)).to(DEV)
+    idx = torch.randint(Nt, (Nt, 25), generator=g).to(torch.uint8).to(DEV)
+    words = torch.tensor([w - (1 << 64) if w >= (1 << 63) else w for w in _PAD_WORDS], dtype=torch.int64).to(DEV)
+    qkv32, gout32 = torch.randn(B_ * Nt, 3 * C, generator=g).to(DEV), torch.randn(B_ * Nt, C, generator=g).to(DEV)
+
+    def twice_old_then_w(run):
+        """run(w): the outputs of the old entries (w = None) or of the `_w` entries with win = w"""
+        old, again, new = run(None), run(None), run(8)
+        torch.cuda.synchronize()
+        assert len(old) == len(new) and all(torch.equal(a, b) for a, b in zip(old, again)), "the old entry does not reproduce itself"
+        for i, (a, b) in enumerate(zip(old, new)):
+            assert torch.equal(a, b), f"output {i}"
+        return old
+
+    def tail(w):
+        return () if w is None else (w,)
+
+    def gather(w):
+        bias = torch.full((H, Nt, Nt), -7.0, device=DEV)
+        L.call("dhz_bias_gather" if w is None else "dhz_bias_gather_w", _p(table), _p(bias), H, *tail(w), _s())
+        return (bias,)
+
+    def shift_mask(w):
+        m = torch.full((nW, Nt, Nt), -7.0, device=DEV)
+        L.call("dhz_shift_mask" if w is None else "dhz_shift_mask_w", _p(m), 16, 16, 4, *tail(w), _s())
+        return (m,)
+
+    (bias,), (mask,) = twice_old_then_w(gather), twice_old_then_w(shift_mask)
+    assert bool((mask != 0).any()) and lib.dhz_ps_attn_bwd_parts_w(B_, H, d, 8) == lib.dhz_ps_attn_bwd_parts_d(B_, H, d) \
+        == lib.dhz_ps_attn_bwd_parts(B_, H)
+    parts = lib.dhz_ps_attn_bwd_parts_w(B_, H, d, 8)
+
+    for dtype, dt in ((torch.float32, 0), (BF, 1)):
+        qkv, gout = qkv32.to(dtype).contiguous(), gout32.to(dtype).contiguous()
+        es, base = qkv.element_size(), qkv.data_ptr()
+        for pad in (False, True):
+            padarg = (_p(words),) if pad else ()
+
+            def chain(w):
+                out = torch.full((B_ * Nt, C), -7.0, device=DEV, dtype=dtype)
+                rank = torch.full((B_, H, Nt), 77, device=DEV, dtype=torch.uint8)
+                dqkv = torch.full((B_ * Nt, 3 * C), -7.0, device=DEV, dtype=dtype)
+                dpart = torch.full((parts, Nt, Nt), -7.0, device=DEV)
+                gb = dqkv.data_ptr()
+                fwd, bwd = ("dhz_ps_attn_fwd_dt", "dhz_ps_attn_bwd_dt") if w is None else ("dhz_ps_attn_fwd_w", "dhz_ps_attn_bwd_w")
+                sfx = "_pad" if pad else ""
+                L.call(fwd + sfx, base, base + es * C, base + 2 * es * C, 3 * C, _p(idx), _p(bias), _p(mask), *padarg, _p(out), C, _p(rank),
+                       B_, H, nW, d, *tail(w), dt, _s())
+                L.call(bwd + sfx, base, base + es * C, base + 2 * es * C, 3 * C, _p(bias), _p(mask), *padarg, _p(rank), _p(gout), C,
+                       gb, gb + es * C, gb + 2 * es * C, 3 * C, _p(dpart), B_, H, nW, d, *tail(w), dt, _s())
+                return out, rank, dqkv, dpart
+
+            out, rank, dqkv, dpart = twice_old_then_w(chain)
+            assert int(rank.max()) == 255 and int(rank.min()) == 0                  # (written: the fill was 77)
+
+    def dense(w):
+        out = torch.full((B_ * Nt, C), -7.0, device=DEV)
+        dqkv = torch.full((B_ * Nt, 3 * C), -7.0, device=DEV)
+        dpart = torch.full((parts, Nt, Nt), -7.0, device=DEV)
+        base, gb = qkv32.data_ptr(), dqkv.data_ptr()
+        sfx = "" if w is None else "_w"
+        L.call("dhz_dense_attn_fwd" + sfx, base, base + 4 * C, base + 8 * C, 3 * C, _p(bias), _p(mask), _p(out), C, B_, H, nW, d, d ** -0.5,
+               *tail(w), _s())
+        L.call("dhz_dense_attn_bwd" + sfx, base, base + 4 * C, base + 8 * C, 3 * C, _p(bias), _p(mask), _p(gout32), C, gb, gb + 4 * C,
+               gb + 8 * C, 3 * C, _p(dpart), B_, H, nW, d, d ** -0.5, *tail(w), _s())
+        return out, dqkv, dpart
+
+    twice_old_then_w(dense)
+
+    tparts = 4 * H
+    ipart = torch.randint(-8, 9, (tparts, Nt, Nt), generator=g).float().to(DEV)
+    start = torch.randint(-8, 9, (225, H), generator=g).float().to(DEV)
+
+    def table_grad(w):
+        fresh, acc = torch.full((225, H), -7.0, device=DEV), start.clone()
+        for dst, accumulate in ((fresh, 0), (acc, 1)):
+            L.call("dhz_bias_table_grad" if w is None else "dhz_bias_table_grad_w", _p(ipart), tparts, _p(dst), H, accumulate, *tail(w), _s())
+        return fresh, acc
+
+    fresh, acc = twice_old_then_w(table_grad)
+    assert torch.equal(acc, fresh + start) and bool((fresh != 0).any())
+
+
 # ----------------------------------------------------------------------------- 6. mask and bias entries
 def test_mask_and_bias_entries_win4():
     L = _L()

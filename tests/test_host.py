@@ -48,6 +48,11 @@ def test_library_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in include/dehaze_hip.h but not exported"
     assert declared == set(_lib.SIGNATURES), declared ^ set(_lib.SIGNATURES)
+    import ctypes
+    for name in declared:                                # the binding is the header's: what load() installed is what SIGNATURES holds
+        fn = getattr(lib, name)
+        assert fn.argtypes == _lib.SIGNATURES[name] and fn.restype is _lib._RESTYPE.get(name, ctypes.c_int), name
+    assert set(_lib._RESTYPE.values()) == {ctypes.c_char_p, ctypes.c_size_t}
     assert lib.dhz_abi_version() == 1
     assert lib.dhz_ps_attn_bwd_parts(8192, 1) == 512 and lib.dhz_ps_attn_bwd_parts(4, 16) == 64
     assert lib.dhz_ps_attn_bwd_parts_d(8192, 1, 32) == 512 and lib.dhz_ps_attn_bwd_parts_d(8192, 2, 64) == 512
