@@ -708,6 +708,30 @@ int dhz_crop_augment_pair_rect(const uint8_t* gt, const uint8_t* hazy, const int
 #define DHZ_RAGGED_DESC_WORDS 5
 int dhz_crop_augment_pair_ragged(const uint8_t* gt_pool, const uint8_t* hazy_pool, const int64_t* desc, float* out_gt, float* out_hazy,
                                  const float* norm, int n, int h, int w, void* stream);
+/*     MixUp (utils/dataset_utils.py:39-45, My_train.py from epoch 6 on) inside the feed: with A[t] what the entry above of the same name
+ *     without `_mix` writes for item t - crop, map k, / 255.f, on the ragged entry's hazy output the normalisation -,
+ *       out[t] = lam[t] * A[t] + (1 - lam[t]) * A[partner[t]]
+ *     as FOUR fp32 operations, each rounded once (1 - lam, two products, one sum; no FMA): bit for bit ATen's
+ *     `lam * x + (1 - lam) * x[partner]` on the outputs of the plain entries.  partner and lam travel in the rows, lam as the bit
+ *     pattern of its fp32 value, so a batch still costs one upload.  The device cannot check partner: the caller keeps 0 <= partner < n.
+ *     dhz_crop_augment_mix_pair_rect: rows of DHZ_MIX_TABLE_WORDS int, (id, r, c, k, partner, lam bits); geometry and the k & (h == w ? 7 : 6)
+ *       rule of dhz_crop_augment_pair_rect (square crops go through here with h == w).
+ *     dhz_crop_augment_mix_pair_ragged: rows of DHZ_RAGGED_MIX_DESC_WORDS int64, the five words of dhz_crop_augment_pair_ragged, then
+ *       [5] partner, [6] lam bits in the low 32 bits; norm as there, applied to either hazy value BEFORE the mix. */
+#define DHZ_MIX_TABLE_WORDS 6
+#define DHZ_RAGGED_MIX_DESC_WORDS 7
+int dhz_crop_augment_mix_pair_rect(const uint8_t* gt, const uint8_t* hazy, const int* table, float* out_gt, float* out_hazy,
+                                   int n, int Hs, int Ws, int h, int w, void* stream);
+int dhz_crop_augment_mix_pair_ragged(const uint8_t* gt_pool, const uint8_t* hazy_pool, const int64_t* desc, float* out_gt, float* out_hazy,
+                                     const float* norm, int n, int h, int w, void* stream);
+/*     dhz_gather_mix_pair: the same for pairs that are resident as float32 [N, per_item] tensors (My_train.py --synthetic, .pt files).
+ *     table: device memory, rows of DHZ_GATHER_MIX_TABLE_WORDS int64, (source item, partner, lam bits in the low 32 bits).  mix == 0:
+ *     out[t] = src[source[t]], a plain gather of both tensors in one launch; mix != 0: lam[t] * src[source[t]] + (1 - lam[t]) *
+ *     src[source[partner[t]]], the four operations above.  16-byte accesses where per_item % 4 == 0 and all four pointers are 16-byte
+ *     aligned, 4-byte ones otherwise.  n * per_item < 2^31; the caller keeps 0 <= source < N and 0 <= partner < n. */
+#define DHZ_GATHER_MIX_TABLE_WORDS 3
+int dhz_gather_mix_pair(const float* gt, const float* hazy, const int64_t* table, float* out_gt, float* out_hazy, int n,
+                        int64_t per_item, int mix, void* stream);
 
 /* K6  shift mask builder: mask[nW,64,64] in {0,-100}  (M1:803-836), Hres x Wres map, win 8. */
 int dhz_shift_mask(float* mask, int Hres, int Wres, int shift, void* stream);

@@ -17,7 +17,9 @@ What is different by design:
     differ in size (I-HAZE, O-HAZE frames instead of pre-cut patches) goes to dataset.ImageStoreHBM and dhz_crop_augment_pair_ragged,
     and the --train_ps crops are drawn from the images that hold one; a `.pt` file
     holding {'target': [N,3,H,W], 'input': [N,3,H,W]} float tensors in [0,1] is accepted too; `--synthetic N` trains
-    on N synthetic haze pairs per epoch.
+    on N synthetic haze pairs per epoch.  MixUp (TR:220, from epoch 6 on) is formed inside that same launch - the stores'
+    batch(..., mixup=), dataset.gather_pair for resident tensors -, bit for bit utils.MixUp_AUG.aug behind the feed out of the same
+    draws; DHZ_FEED_MIXUP=0 restores the composed route.
 """
 import argparse
 import datetime
@@ -36,6 +38,7 @@ import torch.distributed as dist  # noqa: E402
 
 import options  # noqa: E402
 import utils  # noqa: E402
+from dataset import FEED_MIXUP, gather_pair  # noqa: E402
 from dehaze_hip.train import FlatAdamW, GradReducer, psnr, synthetic_batch, train_step  # noqa: E402
 from losses import CharbonnierLoss  # noqa: E402
 from My_CR import ContrastLoss  # noqa: E402
@@ -179,7 +182,7 @@ def main():
     else:
         tgt_all, inp_all = load_pairs(opt.train_dir, dev)
         vt, vi = load_pairs(opt.val_dir, dev)
-        tgt_all, inp_all = tgt_all[rank::world], inp_all[rank::world]
+        tgt_all, inp_all = tgt_all[rank::world].contiguous(), inp_all[rank::world].contiguous()      # (gather_pair reads rows)
     n_train = len(store) if store is not None else tgt_all.shape[0]
     if pick is not None:
         n_train = len(pick)
@@ -227,12 +230,18 @@ def main():
             sel = perm[:n_epoch][i * opt.batch_size:(i + 1) * opt.batch_size]
             if pick is not None:
                 sel = pick[sel]
-            if store is not None:
-                target, input_ = store.batch(sel.tolist(), opt.train_ps)
+            mix = mixup if epoch > 5 else None                  # TR:220
+            if not FEED_MIXUP:                                   # DHZ_FEED_MIXUP=0: the feed, then MixUp_AUG.aug as passes of its own
+                if store is not None:
+                    target, input_ = store.batch(sel.tolist(), opt.train_ps)
+                else:
+                    target, input_ = tgt_all[sel.to(dev)], inp_all[sel.to(dev)]
+                if mix is not None:
+                    target, input_ = mix.aug(target, input_)
+            elif store is not None:                              # crop, augmentation and MixUp: one launch, one pinned upload
+                target, input_ = store.batch(sel.tolist(), opt.train_ps, mixup=mix)
             else:
-                target, input_ = tgt_all[sel.to(dev)], inp_all[sel.to(dev)]
-            if epoch > 5:
-                target, input_ = mixup.aug(target, input_)
+                target, input_ = gather_pair(tgt_all, inp_all, sel, mixup=mix)
             if ssim_term is None:
                 loss, loss_rec, loss_cr = train_step(model, char, cr, optimizer, reducer, input_, target,
                                                      opt.w_loss_CharbonnierLoss, opt.w_loss_vgg7)

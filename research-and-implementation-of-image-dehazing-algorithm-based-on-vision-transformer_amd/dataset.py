@@ -7,7 +7,9 @@ window, applies one of 8 rotate/flip augmentations and ships float32 through Dat
 patches: 2 x 5.4 GB of 288 GB) and produces a batch with one kernel launch (dhz_crop_augment_pair: gather + crop +
 rotate/flip + /255 to float32 CHW), drawing (r, c, augmentation) per item from the same host generators in the same
 order as DataLoaderTrain.__getitem__, so a batch equals what the reference dataset returns for those items and draws.
+With `mixup=` the same launch also forms My_train.py's MixUp of the batch (the `_mix` entries; `gather_pair` for resident tensors).
 """
+import collections
 import os
 import random
 
@@ -127,6 +129,51 @@ class DataLoaderTestSR(Dataset):                       # dataset.py:205-232: PNG
         return _chw(f), os.path.split(f)[-1]
 
 
+FEED_MIXUP = os.environ.get("DHZ_FEED_MIXUP", "1") != "0"      # A/B switch: off = My_train.py mixes with MixUp_AUG.aug after the feed
+_RECENT_TABLES = collections.deque(maxlen=8)                   # gather_pair's pinned tables (the stores keep theirs in _table)
+
+
+def _mix_table(rows, mixup, device):
+    """rows [n, k] (int32 or int64, host) -> pinned [n, k + 2] table of the `_mix` entries: the rows, then MixUp's partner and the bit
+    pattern of its fp32 lam, both from mixup.draw(n) - called HERE, after the caller drew every row's geometry.  The kernels index the
+    table with partner unchecked, so it is checked here."""
+    n = rows.shape[0]
+    partner, lam = mixup.draw(n)
+    assert partner.shape == (n,) and lam.shape == (n,) and lam.dtype == torch.float32
+    assert n > 0 and 0 <= int(partner.min()) and int(partner.max()) < n, "MixUp partner outside the batch"
+    tab = torch.empty((n, rows.shape[1] + 2), dtype=rows.dtype, pin_memory=torch.device(device).type == "cuda")
+    tab[:, :-2] = rows
+    tab[:, -2] = partner
+    tab[:, -1] = lam.contiguous().view(torch.int32)                # (a lam is positive: the int32 is the bit pattern in an int64 row too)
+    return tab
+
+
+def gather_pair(tgt_all, inp_all, sel, mixup=None):
+    """(tgt_all[sel], inp_all[sel]) of two resident float32 tensors [N, ...] of one shape in ONE launch (dhz_gather_mix_pair); with a
+    utils.MixUp_AUG, mixup.aug of that pair bit for bit, out of the same draws.  sel: host LongTensor or a list of item ids; it travels
+    in the pinned table - no sel.to(device), no blocking copy."""
+    from dehaze_hip import _lib
+    from dehaze_hip.ops import _p, _stream
+    assert tgt_all.is_cuda and tgt_all.dtype == inp_all.dtype == torch.float32 and tgt_all.shape == inp_all.shape
+    assert tgt_all.is_contiguous() and inp_all.is_contiguous() and tgt_all.device == inp_all.device
+    sel = torch.as_tensor(sel, dtype=torch.int64).reshape(-1)
+    assert not sel.is_cuda, "gather_pair: sel is a host tensor (it goes into the pinned table)"
+    n, N = sel.numel(), tgt_all.shape[0]
+    assert n > 0 and 0 <= int(sel.min()) and int(sel.max()) < N, "gather_pair: item id outside the resident tensors"
+    if mixup is not None:
+        tab = _mix_table(sel.view(n, 1), mixup, tgt_all.device)
+    else:
+        tab = torch.zeros((n, 3), dtype=torch.int64, pin_memory=True)
+        tab[:, 0] = sel
+    tab_d = tab.to(tgt_all.device, non_blocking=True)
+    target = torch.empty((n,) + tuple(tgt_all.shape[1:]), device=tgt_all.device, dtype=torch.float32)
+    input_ = torch.empty_like(target)
+    _RECENT_TABLES.append(tab)                                      # keep the pinned buffer alive until the copy ran
+    _lib.call("dhz_gather_mix_pair", _p(tgt_all), _p(inp_all), tab_d.data_ptr(), _p(target), _p(input_), n, tgt_all[0].numel(),
+              int(mixup is not None), _stream())
+    return target, input_
+
+
 class PatchStoreHBM:
     """All (gt, hazy) patch pairs of a directory as uint8 [N,H,W,3] tensors in HBM + the batch kernel."""
 
@@ -157,9 +204,13 @@ class PatchStoreHBM:
     def __len__(self):
         return self.N
 
-    def batch(self, indices, ps):
+    def batch(self, indices, ps, mixup=None):
         """indices: iterable of patch ids.  Returns (clean, noisy) float32 [n,3,ps,ps] on the device; per item the crop
         origin and the augmentation are drawn like DataLoaderTrain.__getitem__ does, in item order.
+
+        mixup: None, or a utils.MixUp_AUG - the batch is then mixup.aug(*batch(indices, ps)) bit for bit, out of the same draws in the
+        same order (every item's geometry first, then mixup.draw(n)), from ONE launch of dhz_crop_augment_mix_pair_rect and one pinned
+        upload: no gathers, no temporaries, no blocking copy.
 
         ps may also be (h, w) - an h x w crop, [n,3,h,w] - or None: the stored size, i.e. whole images (FFA_main.py --whole_img).  These go
         through dhz_crop_augment_pair_rect; an int keeps the square entry.  The table is drawn by draw_rect_aug: for h == w exactly
@@ -176,6 +227,20 @@ class PatchStoreHBM:
                 raise ValueError(f"PatchStoreHBM.batch: a {h} x {w} crop does not fit the stored {self.H} x {self.W} images")
         idx = [int(i) % self.N for i in indices]
         n = len(idx)
+        if mixup is not None:
+            if not rect:
+                h = w = ps                                          # the rect entry equals the square one on h == w
+                if not (0 < ps <= self.H and ps <= self.W):
+                    raise ValueError(f"PatchStoreHBM.batch: a {ps} x {ps} crop does not fit the stored {self.H} x {self.W} images")
+            rows = [(i,) + tuple(draw_rect_aug(self.H, self.W, h, w) if rect else draw_crop_aug(self.H, self.W, ps)) for i in idx]
+            tab = _mix_table(torch.tensor(rows, dtype=torch.int32), mixup, self.device)
+            self._table = tab                                       # keep the pinned buffer alive until the copy ran
+            tab_d = tab.to(self.device, non_blocking=True)
+            clean = torch.empty((n, 3, h, w), device=self.device, dtype=torch.float32)
+            noisy = torch.empty_like(clean)
+            _lib.call("dhz_crop_augment_mix_pair_rect", self.gt.data_ptr(), self.hazy.data_ptr(), tab_d.data_ptr(), _p(clean), _p(noisy),
+                      n, self.H, self.W, h, w, _stream())
+            return clean, noisy
         tab = torch.empty((n, 4), dtype=torch.int32)
         if self.device.type == "cuda":
             tab = tab.pin_memory()
@@ -339,12 +404,14 @@ class ImageStoreHBM:
         bucket = self._buckets[self.hazy_hw[anchor]]
         return bucket[torch.randint(len(bucket), (bs,))]
 
-    def batch(self, indices, ps, normalize=None):
+    def batch(self, indices, ps, normalize=None, mixup=None):
         """(clean, noisy) float32 [n,3,h,w] on the device.  ps: an int, (h, w), or None - whole images, which then must share one size.  Per
         item, in item order, (r, c, k) = draw_rect_aug(H_i, W_i, h, w) with the item's own size (an int ps: draw_crop_aug), so on a store
         whose images share one size the draws and the output are PatchStoreHBM.batch's bit for bit.  normalize: None, or (mean, std) of
         three floats each - the hazy output becomes (v / 255 - mean) / std in fp32 (ToTensor + Normalize, data_utils.py:78-79); the clear
-        output never is.  One pinned descriptor upload per batch."""
+        output never is.  mixup: None, or a utils.MixUp_AUG - the batch is then mixup.aug(*batch(indices, ps, normalize)) bit for bit out
+        of the same draws (geometry of every item first, then mixup.draw(n)), in the same single launch
+        (dhz_crop_augment_mix_pair_ragged; _table gets two more words per row, _draws stays).  One pinned descriptor upload per batch."""
         import ctypes
         from dehaze_hip import _lib
         from dehaze_hip.ops import _p, _stream
@@ -370,7 +437,9 @@ class ImageStoreHBM:
             rows.append((self.hazy_off[i] + r * W + c, W, self.clear_off[j] + (top + r) * Wc + left + c, Wc, k))
             draws.append((i, r, c, k))
         tab = torch.tensor(rows, dtype=torch.int64)
-        if self.device.type == "cuda":
+        if mixup is not None:
+            tab = _mix_table(tab, mixup, self.device)               # (after every item's geometry: the order of batch + MixUp_AUG.aug)
+        elif self.device.type == "cuda":
             tab = tab.pin_memory()
         self._table = tab                                       # keep the pinned buffer alive until the copy ran
         self._draws = torch.tensor(draws, dtype=torch.int32)    # (id, r, c, k) per item: PatchStoreHBM's table
@@ -381,8 +450,8 @@ class ImageStoreHBM:
             norm = (ctypes.c_float * 6)(*[float(v) for v in tuple(mean) + tuple(std)])
         clean = torch.empty((n, 3, h, w), device=self.device, dtype=torch.float32)
         noisy = torch.empty_like(clean)
-        _lib.call("dhz_crop_augment_pair_ragged", self.gt_pool.data_ptr(), self.hazy_pool.data_ptr(), tab_d.data_ptr(), _p(clean),
-                  _p(noisy), norm, n, h, w, _stream())
+        _lib.call("dhz_crop_augment_pair_ragged" if mixup is None else "dhz_crop_augment_mix_pair_ragged", self.gt_pool.data_ptr(),
+                  self.hazy_pool.data_ptr(), tab_d.data_ptr(), _p(clean), _p(noisy), norm, n, h, w, _stream())
         return clean, noisy
 
 

@@ -36,6 +36,12 @@ class MixUp_AUG:
     def __init__(self):
         self.dist = torch.distributions.beta.Beta(torch.tensor([1.2]), torch.tensor([1.2]))
 
+    def draw(self, bs):
+        """(indices, lam) of one batch on the host, lam float32 [bs]: aug's two draws from the global torch generator in aug's order,
+        for the feed kernels that mix inside their launch (dataset.PatchStoreHBM.batch / ImageStoreHBM.batch / gather_pair)"""
+        indices = torch.randperm(bs)
+        return indices, self.dist.rsample((bs, 1)).view(-1)
+
     def aug(self, rgb_gt, rgb_noisy):
         bs = rgb_gt.size(0)
         indices = torch.randperm(bs)
