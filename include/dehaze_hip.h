@@ -1024,6 +1024,35 @@ int dhz_ssim_loss_fwd(float* loss, const float* x, const float* y, int B, int C,
 int dhz_ssim_loss_bwd(float* dx, const float* gloss, const float* x, const float* y, int B, int C, int H, int W, int K, const float* window,
                       int valid, double C1, double C2, int clamp01, void* ws, size_t ws_bytes, void* stream);
 
+/* K16  Total-variation losses (csrc/tv_loss.hip): the two smoothness terms of Uformer_ProbSparse/losses.py (L) and their gradients.
+ *      x: contiguous fp32 [B, C, H, W]; all arithmetic in double (a difference of two fp32 values is exact there); sums are per plane.
+ *      form == 0, "beta" (`tv_loss`, L:8-18): on the (H - 1) x (W - 1) sites i < H - 1, j < W - 1 of a plane
+ *        s = (x[i,j+1] - x[i,j])^2 + (x[i+1,j] - x[i,j])^2,   loss = coeff sum s^beta / (B C H W)          (coeff = reg_coeff, L:18)
+ *        the last row and column hold no site; the divisor is the full element count, as in L.
+ *      form == 1, "sq" (`TVLoss.forward`, L:25-33): with sum_v, sum_h the sums of the squared vertical / horizontal first differences
+ *        loss = coeff 2 (sum_v / (C (H - 1) W) + sum_h / (C H (W - 1))) / B                                (coeff = tv_loss_weight, L:33)
+ *        beta is checked and otherwise unused.
+ *      Zero-site rule (the one deviation from autograd of L): a site with s == 0 - both differences exactly zero, a function of the input
+ *        bits - contributes 0 to the gradient; the value is unaffected (0^beta = 0).  Autograd of L gives inf * 0 = NaN there for beta < 1,
+ *        on every pixel of such a site, and a prediction clamped to [0, 1] always has such sites.  The other sites a pixel belongs to
+ *        contribute as ever.
+ *      dhz_tv_loss_fwd: loss[0] = (float) of the above, WRITTEN.
+ *      dhz_tv_loss_bwd: dx = gloss[0] * d loss / d x, WRITTEN, not accumulated, recomputed from x alone in gather form (pixel (i, j) reads
+ *        the sites (i, j), (i, j - 1), (i - 1, j) under beta, its four neighbours under sq): no saved maps, no workspace, no atomics.
+ *        gloss is a device scalar (no host sync).
+ *      Cuts: bands of 64 columns x 64 rows, one workgroup and one double partial sum each; a one-workgroup launch adds them in a fixed
+ *      order.  Every cut is a function of the shapes: the same bits from run to run, under any dhz_set_reserved_cus, with the
+ *      deterministic mode on or off (the mode's workspace is not used).
+ *      ws: dhz_tv_loss_workspace_bytes(B, C, H, W) bytes - one double per band; 0 for an unsupported shape - 8-byte aligned.  A null
+ *      pointer, a form outside {0, 1}, beta <= 0 or not finite, B or C < 1, H or W < 2 (no site; the Python module routes such planes to
+ *      the ATen formula), B C > 65535, H > 4194240, B C H W >= 2^31, a missing, too small or misaligned workspace: DHZ_EINVAL before any
+ *      launch. */
+size_t dhz_tv_loss_workspace_bytes(int B, int C, int H, int W);
+int dhz_tv_loss_fwd(float* loss, const float* x, int B, int C, int H, int W, int form, double beta, double coeff, void* ws, size_t ws_bytes,
+                    void* stream);
+int dhz_tv_loss_bwd(float* dx, const float* gloss, const float* x, int B, int C, int H, int W, int form, double beta, double coeff,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -101,6 +101,11 @@ def parse(argv=None):
     parser.add_argument('--ssimloss', type=nonneg_float, default=0,
                         help="weight of the SSIM loss 1 - ssim(out, y) on the HIP kernels (FFA_model/metrics.py's ssim: 11 x 11 Gaussian "
                              "window, both images clamped); 0: off")
+    parser.add_argument('--tvloss', type=nonneg_float, default=0,
+                        help="weight of the total-variation term of losses.py on the output, on the HIP kernels; 0: off")
+    parser.add_argument('--tv_form', choices=('sq', 'beta'), default='sq',
+                        help="--tvloss: sq = TVLoss() (squared differences), beta = tv_loss(x, --tv_beta) (sum of s ** beta, reg_coeff 5)")
+    parser.add_argument('--tv_beta', type=float, default=0.5, help="--tv_form beta: the exponent (> 0)")
     parser.add_argument('--pairing', choices=('sorted', 'reside'), default='sorted',
                         help="how <train_dir>/hazy maps to <train_dir>/gt: sorted = one to one in sorted order; reside = hazy `1400_1.png` "
                              "-> gt `1400` + --clear_format (FFA_model/data_utils.py:58-60)")
@@ -180,6 +185,14 @@ def main(argv=None):
     if opt.ssimloss > 0:
         from dehaze_hip.ssim_loss import SSIMLoss          # opt-in: a default run never imports it
         ssim_term = SSIMLoss()
+    extra = {}                                     # keywords of the opt-in terms: a default run passes none
+    if ssim_term is not None:
+        extra.update(ssim_loss=ssim_term, w_ssim=opt.ssimloss)
+    tv_term = None
+    if opt.tvloss > 0:
+        from dehaze_hip.tv_loss import TVTerm              # opt-in: a default run never imports it
+        tv_term = TVTerm(opt.tv_form, opt.tv_beta)
+        extra.update(tv_term=tv_term, w_tv=opt.tvloss)
 
     losses, ssims, psnrs = [], [], []
     start_step, max_ssim, max_psnr = 0, 0.0, 0.0
@@ -250,15 +263,14 @@ def main(argv=None):
             y, x = store.batch(sel.tolist(), None if opt.whole_img else opt.crop_size)
         else:
             y, x = tgt_all[sel.to(dev)], inp_all[sel.to(dev)]
-        if ssim_term is None:
-            loss, _, _ = ffa_train_step(net, perloss, optimizer, None, x, y)
-        else:
-            loss, _, _ = ffa_train_step(net, perloss, optimizer, None, x, y, ssim_loss=ssim_term, w_ssim=opt.ssimloss)
+        loss, _, _ = ffa_train_step(net, perloss, optimizer, None, x, y, **extra)
         pending.append(loss)
         if step % opt.log_every == 0 or step % opt.eval_step == 0 or step == opt.steps:
             losses += torch.stack(pending).tolist()
             pending = []
             ssim_txt = f'| ssim loss : {ssim_term.last_value.item():.5f}' if ssim_term is not None else ''
+            if tv_term is not None:
+                ssim_txt += f'| tv loss : {tv_term.last_value.item():.5f}'
             print(f'\rtrain loss : {losses[-1]:.5f}{ssim_txt}| step :{step}/{opt.steps}|lr :{lr :.7f} '
                   f'|time_used :{(time.time() - t0) / 60 :.1f}', end='', flush=True)
         if step % opt.eval_step == 0:

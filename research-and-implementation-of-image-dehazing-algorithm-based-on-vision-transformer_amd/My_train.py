@@ -72,8 +72,20 @@ def build_parser():
     return parser
 
 
+def train_parser():
+    """the parser main() reads the command line with: build_parser() (whose option set tests/test_feed_mixup_host.py pins) plus the
+    options of the total-variation term"""
+    parser = build_parser()
+    parser.add_argument('--w_loss_tv', type=nonneg_float, default=0,
+                        help='weight of the total-variation term of losses.py on the clamped prediction, on the HIP kernels; 0: off')
+    parser.add_argument('--tv_form', choices=('sq', 'beta'), default='sq',
+                        help='--w_loss_tv: sq = TVLoss() (squared differences), beta = tv_loss(x, --tv_beta) (sum of s ** beta, reg_coeff 5)')
+    parser.add_argument('--tv_beta', type=float, default=0.5, help='--tv_form beta: the exponent (> 0)')
+    return parser
+
+
 def main():
-    opt = build_parser().parse_args()
+    opt = train_parser().parse_args()
     torch.backends.cudnn.benchmark = True      # TR:35 - on ROCm: MIOpen measures its convolution algorithms at first use
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -155,6 +167,14 @@ def main():
     if opt.w_loss_ssim > 0:
         from dehaze_hip.ssim_loss import SSIMLoss          # opt-in: a default run never imports it
         ssim_term = SSIMLoss(clamp=False)                  # on the clamped prediction: the Charbonnier path carries the clamp's gradient
+    extra = {}                                             # keywords of the opt-in terms: a default run passes none
+    if ssim_term is not None:
+        extra.update(ssim_loss=ssim_term, w_ssim=opt.w_loss_ssim)
+    tv_term = None
+    if opt.w_loss_tv > 0:
+        from dehaze_hip.tv_loss import TVTerm              # opt-in: a default run never imports it
+        tv_term = TVTerm(opt.tv_form, opt.tv_beta)
+        extra.update(tv_term=tv_term, w_tv=opt.w_loss_tv)
     if world > 1:
         # identical replicas above (same seed -> same initial weights); from here on every rank draws its own permutations,
         # crops, augmentations, MixUp lambdas, DropPath masks and sampled keys
@@ -242,16 +262,13 @@ def main():
                 target, input_ = store.batch(sel.tolist(), opt.train_ps, mixup=mix)
             else:
                 target, input_ = gather_pair(tgt_all, inp_all, sel, mixup=mix)
-            if ssim_term is None:
-                loss, loss_rec, loss_cr = train_step(model, char, cr, optimizer, reducer, input_, target,
-                                                     opt.w_loss_CharbonnierLoss, opt.w_loss_vgg7)
-            else:
-                loss, loss_rec, loss_cr = train_step(model, char, cr, optimizer, reducer, input_, target,
-                                                     opt.w_loss_CharbonnierLoss, opt.w_loss_vgg7, ssim_loss=ssim_term,
-                                                     w_ssim=opt.w_loss_ssim)
+            loss, loss_rec, loss_cr = train_step(model, char, cr, optimizer, reducer, input_, target,
+                                                 opt.w_loss_CharbonnierLoss, opt.w_loss_vgg7, **extra)
             epoch_loss += loss
             if is_main and (i % opt.log_every == 0):
                 ssim_txt = f'; ssim:{ssim_term.last_value.item():.5f}' if ssim_term is not None else ''
+                if tv_term is not None:
+                    ssim_txt += f'; tv:{tv_term.last_value.item():.5f}'
                 print(f'\r{i}/{steps_per_epoch}: loss:{loss.item():.5f} = Charbonnier:{loss_rec.item():.5f}; '
                       f'contrast:{(loss_cr.item() if loss_cr is not None else 0):.5f}{ssim_txt} |time_used (Min):'
                       f'{(time.time() - t0) / 60:.1f}', end='', flush=True)

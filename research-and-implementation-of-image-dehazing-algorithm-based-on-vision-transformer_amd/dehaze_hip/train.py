@@ -480,16 +480,21 @@ class SideStream:
 
 
 def train_step(model, char_loss, cr_loss, optimizer, reducer, input_, target, w_char=1.0, w_cr=1.0, side=None, ssim_loss=None,
-               w_ssim=0.0):
+               w_ssim=0.0, tv_term=None, w_tv=0.0):
     """One optimisation step, the body of TR:212-250 in fp32: zero_grad -> restored = model(input_) ->
     clamp(0,1) -> w_char*Charbonnier + w_cr*Contrast -> backward (bucketed all-reduce overlapped) ->
     AdamW.  Returns (loss, loss_rec, loss_cr) as device scalars (no host sync here; the reference's
     per-step .item() calls, TR:250-254, are left to the caller's logging cadence).
     side: a SideStream - the contrastive loss' no-gradient feature passes (target, input_) run on it beside the model's forward.
     ssim_loss, w_ssim: an ssim_loss.SSIMLoss(clamp=False) and its weight - w_ssim * (1 - ssim) is added on the clamped prediction (the
-    Charbonnier path carries the clamp's gradient); the term itself stays in ssim_loss.last_value.  None / 0: the step as it was."""
+    Charbonnier path carries the clamp's gradient); the term itself stays in ssim_loss.last_value.  None / 0: the step as it was.
+    tv_term, w_tv: a tv_loss.TVTerm and its weight - w_tv * tv_term(clamped prediction) is added (a clamped image always has sites
+    whose differences are exactly zero: the term's zero-site rule keeps their gradient defined); the term itself stays in
+    tv_term.last_value.  None / 0: the step as it was."""
     if ssim_loss is not None and not w_ssim >= 0:
         raise ValueError(f"train_step: w_ssim={w_ssim} (a weight >= 0; 0 switches the term off)")
+    if tv_term is not None and not w_tv >= 0:
+        raise ValueError(f"train_step: w_tv={w_tv} (a weight >= 0; 0 switches the term off)")
     if isinstance(optimizer, FlatAdamW):
         if getattr(model, "act_dtype", None) == torch.bfloat16:
             if ops.BF16_SHADOW is None or optimizer._flat is None or ops.BF16_SHADOW[0] is not optimizer._flat["p"]:
@@ -531,6 +536,8 @@ def train_step(model, char_loss, cr_loss, optimizer, reducer, input_, target, w_
         loss = loss + w_cr * loss_cr
     if ssim_loss is not None and w_ssim > 0:
         loss = loss + w_ssim * ssim_loss(clamped, target)
+    if tv_term is not None and w_tv > 0:
+        loss = loss + w_tv * tv_term(clamped)
     loss.backward()
     if reducer is not None:
         reducer.wait()
@@ -545,14 +552,18 @@ def lr_schedule_cosdecay(t, T, init_lr):
     return 0.5 * (1 + math.cos(t * math.pi / T)) * init_lr
 
 
-def ffa_train_step(model, perloss, optimizer, reducer, input_, target, w_per=0.04, ssim_loss=None, w_ssim=0.0):
+def ffa_train_step(model, perloss, optimizer, reducer, input_, target, w_per=0.04, ssim_loss=None, w_ssim=0.0, tv_term=None, w_tv=0.0):
     """One step of FFA-Net's own recipe (FFA_model/main.py:84-96): out = model(x); loss = L1(out, y), unclamped, + w_per * perloss(out, y)
     when `perloss` (PerceptualLoss.LossNetwork) is given; backward; Adam (FlatAdamW with weight_decay 0).  The L1 mean runs on
     dhz_l1_pair_fwd / _bwd with n = NULL (vgg.l1_pair; dhz_l1_pair_fwd_any / _bwd_any where 3 B H W is no multiple of 4).  Returns (loss, loss_l1, loss_per) as device scalars - no host sync here.
     ssim_loss, w_ssim: an ssim_loss.SSIMLoss() (clamp=True, the reference metric's own behaviour) and its weight - w_ssim * (1 - ssim) is
-    added on the raw output; the term itself stays in ssim_loss.last_value.  None / 0: the step as it was."""
+    added on the raw output; the term itself stays in ssim_loss.last_value.  None / 0: the step as it was.
+    tv_term, w_tv: a tv_loss.TVTerm and its weight - w_tv * tv_term(out) is added on the raw output; the term itself stays in
+    tv_term.last_value.  None / 0: the step as it was."""
     if ssim_loss is not None and not w_ssim >= 0:
         raise ValueError(f"ffa_train_step: w_ssim={w_ssim} (a weight >= 0; 0 switches the term off)")
+    if tv_term is not None and not w_tv >= 0:
+        raise ValueError(f"ffa_train_step: w_tv={w_tv} (a weight >= 0; 0 switches the term off)")
     if getattr(model, "act_dtype", None) == torch.bfloat16 or input_.dtype != torch.float32 \
             or any(p.dtype != torch.float32 for p in model.parameters()):
         raise NotImplementedError("ffa_train_step: fp32 only (the squared-error taps and the VGG16 engine have no bf16 form)")
@@ -576,6 +587,8 @@ def ffa_train_step(model, perloss, optimizer, reducer, input_, target, w_per=0.0
         loss = loss + w_per * loss_per
     if ssim_loss is not None and w_ssim > 0:
         loss = loss + w_ssim * ssim_loss(out, target)
+    if tv_term is not None and w_tv > 0:
+        loss = loss + w_tv * tv_term(out)
     loss.backward()
     if reducer is not None:
         reducer.wait()
