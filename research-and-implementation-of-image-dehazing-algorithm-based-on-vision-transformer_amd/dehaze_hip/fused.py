@@ -113,31 +113,52 @@ class _Rec:
 # of 18 launches of ~11 us.  With a gradient reducer attached (ops.GRAD_READY set: N > 1 ranks) every table is reduced where it is produced,
 # so that its bucket's all-reduce is not held back to the end of the pass.
 DEFER_TABLE_GRADS = True
-_PENDING_TABLES = []
+# id of a running backward pass (the engine's graph task) -> the [(dpart, parts, grad, H)] that its end-of-pass callback reduces.  A key
+# IS the queued state: it is there from the moment the callback is queued until the callback has run.  The state is not read off the
+# entries, and not kept in one flag either: the engine runs no callback of a pass that raised, so whatever such a pass left would pass
+# for "queued" in the next one, whose table gradients would then never be reduced.  Per pass, because a backward pass can run inside
+# another one (re-entrant checkpointing), each with its own end.
+_PENDING_TABLES = {}
 
 
-def _flush_table_grads():
-    pend = list(_PENDING_TABLES)
-    _PENDING_TABLES.clear()
-    arr, ints = _ptr_array, _int_array
-    for i0 in range(0, len(pend), 32):
-        part = pend[i0: i0 + 32]
-        _lib.call("dhz_bias_table_grad_multi", arr([_p(d) for d, _, _, _ in part]), ints([n for _, n, _, _ in part]),
-                  arr([_p(g) for _, _, g, _ in part]), ints([H for _, _, _, H in part]), len(part), _stream())
+def _backward_pass():
+    """the engine's id of the backward pass this thread is running, -1 outside one"""
+    return torch._C._current_graph_task_id()
+
+
+def _drop_stale_tables(task=None):
+    """forget what backward passes left that raised before their end: outside a backward pass that is every entry; inside pass `task`,
+    those of later passes (ids count up, and a pass started within this one has ended by the time this one runs a node again)"""
+    task = _backward_pass() if task is None else task
+    for k in [k for k in _PENDING_TABLES if task < 0 or k > task]:
+        del _PENDING_TABLES[k]
+
+
+def _flush_table_grads(task):
+    pend = _PENDING_TABLES.get(task, ())
+    try:
+        arr, ints = _ptr_array, _int_array
+        for i0 in range(0, len(pend), 32):
+            part = pend[i0: i0 + 32]
+            _lib.call("dhz_bias_table_grad_multi", arr([_p(d) for d, _, _, _ in part]), ints([n for _, n, _, _ in part]),
+                      arr([_p(g) for _, _, g, _ in part]), ints([H for _, _, _, H in part]), len(part), _stream())
+    finally:
+        _PENDING_TABLES.pop(task, None)
 
 
 def _table_backward(dpart, parts, table_p, H):
     gt = _grad_buf(table_p)
     if gt is not None and DEFER_TABLE_GRADS and ops.GRAD_READY is None:
-        queued = bool(_PENDING_TABLES)
-        if not queued:
+        task = _backward_pass()
+        _drop_stale_tables(task)
+        if task >= 0 and task not in _PENDING_TABLES:
             try:                                        # (only valid inside a running backward pass)
-                torch.autograd.Variable._execution_engine.queue_callback(_flush_table_grads)
-                queued = True
+                torch.autograd.Variable._execution_engine.queue_callback(lambda: _flush_table_grads(task))
+                _PENDING_TABLES[task] = []
             except RuntimeError:
-                queued = False
-        if queued:
-            _PENDING_TABLES.append((dpart, parts, gt, H))
+                pass
+        if task in _PENDING_TABLES:
+            _PENDING_TABLES[task].append((dpart, parts, gt, H))
             return None
     if gt is not None:
         ops.bias_table_grad(dpart, parts, H, out=gt, accumulate=True)
@@ -173,7 +194,8 @@ def stage_block_operands(entries, device, pad=False):
     STAGED_BIAS.clear()
     STAGED_PREPACK.clear()
     STAGED_PACK6.clear()
-    _PENDING_TABLES.clear()          # (a backward pass that died before its end-of-pass callback)
+    if _PENDING_TABLES:
+        _drop_stale_tables()         # (a backward pass that died before its end-of-pass callback)
     arr, ints = _ptr_array, _int_array
     tabs = [(t, H) for t, H, _, _ in entries if t is not None]
     if tabs:
@@ -435,6 +457,8 @@ class _AttnNode(Function):
     @staticmethod
     def forward(ctx, fused, x, gamma, beta, wq, bq, wk, bk, wv, bv, wo, bo, table, idx, mask, dscale, Hres, Wres, shift, H, pad, grad_mode):
         train = grad_mode and any(ctx.needs_input_grad)      # grad mode reads False inside Function.forward: passed in
+        if _PENDING_TABLES:
+            _drop_stale_tables()
         out, rec = (_attn_fused_fwd if fused else _attn_chain_fwd)(train, x, gamma, beta, wq, bq, wk, bk, wv, bv, wo, bo, table, idx, mask,
                                                                    dscale, Hres, Wres, shift, H, pad)
         if rec is not None:
@@ -673,6 +697,8 @@ class _BlockNode(Function):
     def forward(ctx, fused, x, *args):
         a, l, grad_mode = args[:_BlockNode.NA], args[_BlockNode.NA:_BlockNode.NA + _BlockNode.NL], args[-1]
         train = grad_mode and any(ctx.needs_input_grad)
+        if _PENDING_TABLES:
+            _drop_stale_tables()
         x1, ra = (_attn_fused_fwd if fused else _attn_chain_fwd)(train, x, *a)
         out, rl = _leff_fwd(train, x1, *l)
         if train:

@@ -476,10 +476,28 @@ class BasicUformerLayer(nn.Module):
     def extra_repr(self):
         return f"dim={self.dim}, input_resolution={self.input_resolution}, depth={self.depth}"
 
+    @staticmethod
+    def _replay(blk):
+        """blk as a function of x that runs on what Uformer.forward staged for THIS forward, however often it is called.  The block
+        consumes its staged sample table, DropPath vectors and padding words on use, and they were drawn outside it: checkpoint's
+        recomputation would find them gone, draw new ones (the RNG state it restores is the block's, not the model's) and differentiate
+        another function than the forward computed.  Nothing staged (a layer run on its own): the block draws inside, under the RNG
+        state that checkpoint restores, as the reference's does."""
+        idx, pad = blk._staged_idx, blk._staged_pad
+        scales = list(blk._staged_scales) if blk._staged_scales else None
+
+        def run(x):
+            blk._staged_idx, blk._staged_pad = idx, pad
+            blk._staged_scales = list(scales) if scales else None
+            return blk(x)
+        return run
+
     def forward(self, x, mask=None):
         for blk in self.blocks:
             if self.use_checkpoint:
-                x = torch.utils.checkpoint.checkpoint(blk, x)
+                # (M1:943 hands the block x alone: the mask is dropped there too.)  Not re-entrant: the forward runs in grad mode, so it
+                # launches the kernels of the plain forward and the two builds agree bit for bit
+                x = torch.utils.checkpoint.checkpoint(self._replay(blk), x, use_reentrant=False)
             else:
                 x = blk(x, mask)
         return x

@@ -122,6 +122,19 @@ def test_ps_attention_oracle(dev, ops, B_, H, d, use_mask):
         assert torch.allclose(out_d.cpu(), out_o, atol=2e-5, rtol=1e-4)
         assert torch.allclose(qkv_d.grad.cpu(), qkv_o.grad, atol=1e-4, rtol=1e-3)
         assert torch.allclose(table_d.grad.cpu(), table_o.grad, atol=2e-4 * B_ ** 0.5, rtol=2e-3)
+    # whatever `bad` is: outputs and gradients against float64 under the KERNEL's selection (tests/_autograd_ref.py), same tolerances
+    import _autograd_ref as R
+    top_d = (rank.cpu() < 25).to(torch.int8).sort(dim=-1, descending=True, stable=True)[1][..., :25]
+    qkv_r = qkv_c.double().requires_grad_()
+    table_r = table_c.double().requires_grad_()
+    q, k, v = (qkv_r[:, i * C:(i + 1) * C].view(B_, 64, H, d).transpose(1, 2) for i in range(3))
+    bias_r = table_r[ridx].reshape(64, 64, H).permute(2, 0, 1)
+    ctx_r = R.Reference(tops=[top_d])._prob_attention(q, k, v, idx, bias_r, mask_c.double() if use_mask else None)
+    out_r = ctx_r.transpose(1, 2).reshape(B_ * 64, C)
+    (out_r * gout_c.double()).sum().backward()
+    assert torch.allclose(out_d.detach().cpu().double(), out_r.detach(), atol=2e-5, rtol=1e-4)
+    assert torch.allclose(qkv_d.grad.cpu().double(), qkv_r.grad, atol=1e-4, rtol=1e-3)
+    assert torch.allclose(table_d.grad.cpu().double(), table_r.grad, atol=2e-4 * B_ ** 0.5, rtol=2e-3)
 
 
 def test_bias_gather_and_shift_mask(dev, ops):
