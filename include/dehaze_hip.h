@@ -1053,6 +1053,28 @@ int dhz_tv_loss_fwd(float* loss, const float* x, int B, int C, int H, int W, int
 int dhz_tv_loss_bwd(float* dx, const float* gloss, const float* x, int B, int C, int H, int W, int form, double beta, double coeff,
                     void* stream);
 
+/* K17  Fourier and variance analysis of feature maps (csrc/fourier.hip): what the reference's fourier_analysis.ipynb and
+ *      featuremap_variance.ipynb compute from a latent, in one read of it and without a 2-D transform.  Per n x n map f = (b, c) of x:
+ *        A[b, c, k] = log(|F[k][k]| + 1e-6), k = 0 .. n/2 - 1, F = the 2-D DFT of f: the notebook's fft2 -> log(abs + 1e-6) -> shift ->
+ *                     .diag()[n/2:], before its mean over batch and channels;
+ *        V[b, c]    = the unbiased variance of f over its n^2 positions (latent.var(dim=[-1, -2]));
+ *        sumA[k], sumV[0] = the sums of A[., ., k] and of V over the M = B C maps m = b C + c, in a fixed order: partial j = the maps
+ *                     j, j + 16, j + 32, ... added in ascending order, j = 0 .. 15, then the partials added in ascending j.
+ *      The diagonal comes from g[s] = sum of f[y][x] over (y + x) mod n = s:  F[k][k] = sum_s g[s] exp(-2 pi i k s / n), summed over
+ *      s = 0 .. n - 1 in that order with the twiddle index (k s) mod n reduced in integers.  V is accumulated around the map's first
+ *      element: V = (sum d^2 - (sum d)^2 / n^2) / (n^2 - 1), d = f - f[0][0].  All arithmetic is double, no atomics, every cut (rows per
+ *      workgroup, channel tiles) a function of the shapes: the same bits from run to run, under any dhz_set_reserved_cus, with the
+ *      deterministic mode on or off (the mode's workspace is not used).
+ *      x: layout 0 = tokens [B, n n, C] (what the Uformer blocks hold), layout 1 = NCHW [B, C, n, n]; contiguous; dtype DHZ_F32 or DHZ_BF16.
+ *      A [B, C, n/2], V [B, C], sumA [n/2], sumV [1]: doubles, all WRITTEN.  n even, 2 <= n <= 2048; 1 <= B, C <= 65535.
+ *      ws: dhz_fourier_diag_workspace_bytes(B, C, n, layout) bytes (the partial g vectors and variance sums of the row cuts; 0 for an
+ *      unsupported shape), 8-byte aligned like the four outputs.  An odd n, n out of range, a layout or dtype code outside {0, 1}, B or C out
+ *      of range, a null pointer, a missing, too small (the message names the bytes needed) or misaligned workspace: DHZ_EINVAL before any
+ *      launch. */
+size_t dhz_fourier_diag_workspace_bytes(int B, int C, int n, int layout);
+int dhz_fourier_diag(double* A, double* V, double* sumA, double* sumV, const void* x, int B, int C, int n, int layout, int dtype, void* ws,
+                     size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -364,6 +364,10 @@ class LeFF(nn.Module):
 class LeWinTransformerBlock(nn.Module):
     """M1:738-875."""
 
+    # analysis.taps sets this on an instance for one forward: a callable handed the tensor between the two branches (after the attention
+    # residual).  That tensor exists only when the branches run as two calls, so a tapped block does not take fused.block.
+    _tap = None
+
     def __init__(self, dim, input_resolution, num_heads, win_size=8, shift_size=0, mlp_ratio=4., qkv_bias=True,
                  qk_scale=None, drop=0., attn_drop=0., drop_path=0., act_layer=nn.GELU, norm_layer=nn.LayerNorm,
                  token_projection='linear', token_mlp='leff', se_layer=False, variant="probsparse"):
@@ -437,7 +441,7 @@ class LeWinTransformerBlock(nn.Module):
                 idx = draw_sample_index(1, ops.NTOK)[0]
             if idx.device != x.device or idx.dtype != torch.uint8:
                 idx = idx.to(device=x.device, dtype=torch.uint8)
-            if fused.BLOCK_NODE and self.token_mlp == 'leff':
+            if fused.BLOCK_NODE and self.token_mlp == 'leff' and self._tap is None:
                 # both branches as one node: the gradient between them never takes the token-order detour (fused.block)
                 return fused.block(x, self.norm1, self.attn.ProbSpare, table, idx.contiguous(), attn_mask, self._scale(x), H, W,
                                    self.shift_size, self.num_heads, self.norm2, self.mlp, self._scale(x), pad)
@@ -449,6 +453,8 @@ class LeWinTransformerBlock(nn.Module):
             aw = self.attn(xw.view(-1, self.win_size * self.win_size, C), mask=attn_mask, idx=idx, pad=pad,
                            nW=(H // self.win_size) * (W // self.win_size))
             x = ops.reverse_residual(aw.reshape(-1, C), x, self._scale(x), H, W, self.shift_size, self.win_size)  # reverse+unroll+res
+        if self._tap is not None:
+            self._tap(x)
         if self.token_mlp == 'ffn':
             # Mlp branch (norm2 -> fc1 -> GELU -> fc2 -> residual) as one autograd node
             return fused.ffn_branch(x, self.norm2, self.mlp, self._scale(x))
