@@ -681,53 +681,57 @@ int dhz_contrast_combine_fwd(const float* sums, const float* inv_cnt, const floa
 int dhz_contrast_combine_bwd(const float* d, const float* w, int k, int ablation, const float* g_loss, const float* g_ap,
                              const float* g_an, float* g, void* stream);
 
-/* F2  training feed (dataset.py:17-77): batch item t = table[t] = (patch id, r, c, k) -> ps x ps crop at (r, c) of the
- *     uint8 [N,Hs,Ws,3] RGB patch pair in HBM, augmentation k of utils/dataset_utils.py:6-40 (0 id, 1-3 rot90 k with
- *     dims=[-1,-2], 4-7 the same followed by flip(-2)), float32 [n,3,ps,ps] = value / 255. */
-int dhz_crop_augment_pair(const uint8_t* gt, const uint8_t* hazy, const int* table, float* out_gt, float* out_hazy,
-                          int n, int Hs, int Ws, int ps, void* stream);
-/*     dhz_crop_augment_pair_rect: the same for an h x w crop (h <= Hs, w <= Ws; h = Hs, w = Ws: whole images), float32 [n,3,h,w].  For
- *     h != w only the four shape-preserving maps exist and the kernel reads k & 6 (0 id, 2 rot180, 4 flip(-2), 6 flip(-1)); for h == w all
- *     eight, bit for bit dhz_crop_augment_pair.  The caller keeps r + h <= Hs and c + w <= Ws. */
-int dhz_crop_augment_pair_rect(const uint8_t* gt, const uint8_t* hazy, const int* table, float* out_gt, float* out_hazy,
-                               int n, int Hs, int Ws, int h, int w, void* stream);
-/*     dhz_crop_augment_pair_ragged: the same feed for images that each have their own size - what FFA_model/data_utils.py:51-81 does per
- *     item on the host (PIL open, CenterCrop of the clear frame, RandomCrop, flip / rotate, ToTensor, Normalize).  gt_pool / hazy_pool are
- *     uint8 pools in device memory, every image HWC (RGB) at its own offset; a pool may exceed 4 GiB, all addresses are formed in 64 bits.
- *     desc: device memory, one row of DHZ_RAGGED_DESC_WORDS int64 per batch item, computed on the host:
+/* F2  training feed (dataset.py:17-77, FFA_model/data_utils.py:51-81): batch item t -> an h x w crop of a uint8 HWC (RGB) image pair in HBM,
+ *     one of eight rotate / flip maps, float32 [n,3,h,w] = value / 255 for the clear (out_gt) and the hazy (out_hazy) image.  Five entries,
+ *     one kernel; they differ in the row format that carries an item's geometry and in whether MixUp is formed in the same launch.
+ *     Table rows (`table`, device memory, 4 int per item): (image id, r, c, k) - the crop at (r, c) of image id of two uint8 [N,Hs,Ws,3]
+ *       stores.  h <= Hs, w <= Ws (h = Hs, w = Ws: whole images); the caller keeps r + h <= Hs and c + w <= Ws.
+ *     Descriptor rows (`desc`, device memory, DHZ_RAGGED_DESC_WORDS int64 per item, computed on the host) - images that each have their own
+ *       size, what data_utils.py:51-81 does per item on the host (PIL open, CenterCrop of the clear frame, RandomCrop, flip / rotate,
+ *       ToTensor, Normalize).  gt_pool / hazy_pool are uint8 pools, every image HWC at its own offset; a pool may exceed 4 GiB, all
+ *       addresses are formed in 64 bits.
  *       [0] pixel offset (bytes / 3) in hazy_pool of the crop's origin: image base + r * hazy stride + c
  *       [1] hazy row stride in pixels (the hazy image's width)
  *       [2] pixel offset in gt_pool of the crop's origin: image base + (top + r) * clear stride + left + c, (top, left) the centre-crop
  *           origin of the larger clear frame
  *       [3] clear row stride in pixels (the clear image's width)
- *       [4] the map k, 0..7 as in dhz_crop_augment_pair; on h != w the kernel reads k & 6 as the rect entry does
- *     Output float32 [n,3,h,w] for both, position for position the rect entry's.  norm: NULL, or six floats in HOST memory (mean[3],
- *     std[3]) read during the call; then out_hazy = ((float)v / 255.f - mean[ch]) / std[ch], two IEEE operations after the division
- *     (ToTensor + Normalize in fp32); out_gt is never normalised.  n * h * w < 2^31.  The entry cannot see the images' sizes: the caller
- *     keeps every crop inside its image (dataset.ImageStoreHBM.batch checks it). */
+ *       [4] the map k
+ *       The entry cannot see the images' sizes: the caller keeps every crop inside its image (dataset.ImageStoreHBM.batch checks it).
+ *     Map k, 0..7, of utils/dataset_utils.py:6-40: 0 id, 1-3 rot90 k with dims=[-1,-2], 4-7 the same followed by flip(-2).  For h != w only
+ *       the four shape-preserving maps exist and the kernel reads k & 6 (0 id, 2 rot180, 4 flip(-2), 6 flip(-1)); for h == w all eight.
+ *     norm (descriptor entries): NULL, or six floats in HOST memory (mean[3], std[3]) read during the call; then out_hazy =
+ *       ((float)v / 255.f - mean[ch]) / std[ch], two IEEE operations after the division (ToTensor + Normalize in fp32); out_gt is never
+ *       normalised.
+ *     MixUp (`_mix` entries; utils/dataset_utils.py:39-45, My_train.py from epoch 6 on): with A[t] what the entry of the same name without
+ *       `_mix` writes for item t - crop, map k, / 255.f, on the hazy output the normalisation -,
+ *         out[t] = lam[t] * A[t] + (1 - lam[t]) * A[partner[t]]
+ *       as FOUR fp32 operations, each rounded once (1 - lam, two products, one sum; no FMA): bit for bit ATen's
+ *       `lam * x + (1 - lam) * x[partner]` on the outputs of the plain entries; norm is applied to either hazy value BEFORE the mix.
+ *       partner and lam travel in the rows, lam as the bit pattern of its fp32 value, so a batch still costs one upload: table rows of
+ *       DHZ_MIX_TABLE_WORDS int, (id, r, c, k, partner, lam bits); descriptor rows of DHZ_RAGGED_MIX_DESC_WORDS int64, the five words
+ *       above, then [5] partner, [6] lam bits in the low 32 bits.  The device cannot check partner: the caller keeps 0 <= partner < n.
+ *     Every entry refuses, before a launch, a null pointer, sizes that are not positive or exceed the store, and n * h * w >= 2^31.
+ *     dhz_crop_augment_pair: table rows, the ps x ps crop - dhz_crop_augment_pair_rect with h = w = ps, bit for bit.  (It used to launch
+ *       whatever n * ps * ps it was given; two float32 outputs of 8 GiB and more each are now refused like everywhere else.)
+ *     dhz_crop_augment_pair_rect, dhz_crop_augment_mix_pair_rect (square crops go through it with h == w): table rows.
+ *     dhz_crop_augment_pair_ragged, dhz_crop_augment_mix_pair_ragged: descriptor rows; position for position the rect entries' output. */
 #define DHZ_RAGGED_DESC_WORDS 5
-int dhz_crop_augment_pair_ragged(const uint8_t* gt_pool, const uint8_t* hazy_pool, const int64_t* desc, float* out_gt, float* out_hazy,
-                                 const float* norm, int n, int h, int w, void* stream);
-/*     MixUp (utils/dataset_utils.py:39-45, My_train.py from epoch 6 on) inside the feed: with A[t] what the entry above of the same name
- *     without `_mix` writes for item t - crop, map k, / 255.f, on the ragged entry's hazy output the normalisation -,
- *       out[t] = lam[t] * A[t] + (1 - lam[t]) * A[partner[t]]
- *     as FOUR fp32 operations, each rounded once (1 - lam, two products, one sum; no FMA): bit for bit ATen's
- *     `lam * x + (1 - lam) * x[partner]` on the outputs of the plain entries.  partner and lam travel in the rows, lam as the bit
- *     pattern of its fp32 value, so a batch still costs one upload.  The device cannot check partner: the caller keeps 0 <= partner < n.
- *     dhz_crop_augment_mix_pair_rect: rows of DHZ_MIX_TABLE_WORDS int, (id, r, c, k, partner, lam bits); geometry and the k & (h == w ? 7 : 6)
- *       rule of dhz_crop_augment_pair_rect (square crops go through here with h == w).
- *     dhz_crop_augment_mix_pair_ragged: rows of DHZ_RAGGED_MIX_DESC_WORDS int64, the five words of dhz_crop_augment_pair_ragged, then
- *       [5] partner, [6] lam bits in the low 32 bits; norm as there, applied to either hazy value BEFORE the mix. */
 #define DHZ_MIX_TABLE_WORDS 6
 #define DHZ_RAGGED_MIX_DESC_WORDS 7
+int dhz_crop_augment_pair(const uint8_t* gt, const uint8_t* hazy, const int* table, float* out_gt, float* out_hazy,
+                          int n, int Hs, int Ws, int ps, void* stream);
+int dhz_crop_augment_pair_rect(const uint8_t* gt, const uint8_t* hazy, const int* table, float* out_gt, float* out_hazy,
+                               int n, int Hs, int Ws, int h, int w, void* stream);
 int dhz_crop_augment_mix_pair_rect(const uint8_t* gt, const uint8_t* hazy, const int* table, float* out_gt, float* out_hazy,
                                    int n, int Hs, int Ws, int h, int w, void* stream);
+int dhz_crop_augment_pair_ragged(const uint8_t* gt_pool, const uint8_t* hazy_pool, const int64_t* desc, float* out_gt, float* out_hazy,
+                                 const float* norm, int n, int h, int w, void* stream);
 int dhz_crop_augment_mix_pair_ragged(const uint8_t* gt_pool, const uint8_t* hazy_pool, const int64_t* desc, float* out_gt, float* out_hazy,
                                      const float* norm, int n, int h, int w, void* stream);
 /*     dhz_gather_mix_pair: the same for pairs that are resident as float32 [N, per_item] tensors (My_train.py --synthetic, .pt files).
  *     table: device memory, rows of DHZ_GATHER_MIX_TABLE_WORDS int64, (source item, partner, lam bits in the low 32 bits).  mix == 0:
  *     out[t] = src[source[t]], a plain gather of both tensors in one launch; mix != 0: lam[t] * src[source[t]] + (1 - lam[t]) *
- *     src[source[partner[t]]], the four operations above.  16-byte accesses where per_item % 4 == 0 and all four pointers are 16-byte
+ *     src[source[partner[t]]], MixUp's four operations above.  16-byte accesses where per_item % 4 == 0 and all four pointers are 16-byte
  *     aligned, 4-byte ones otherwise.  n * per_item < 2^31; the caller keeps 0 <= source < N and 0 <= partner < n. */
 #define DHZ_GATHER_MIX_TABLE_WORDS 3
 int dhz_gather_mix_pair(const float* gt, const float* hazy, const int64_t* table, float* out_gt, float* out_hazy, int n,

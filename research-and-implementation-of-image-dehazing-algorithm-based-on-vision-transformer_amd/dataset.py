@@ -130,21 +130,29 @@ class DataLoaderTestSR(Dataset):                       # dataset.py:205-232: PNG
 
 
 FEED_MIXUP = os.environ.get("DHZ_FEED_MIXUP", "1") != "0"      # A/B switch: off = My_train.py mixes with MixUp_AUG.aug after the feed
-_RECENT_TABLES = collections.deque(maxlen=8)                   # gather_pair's pinned tables (the stores keep theirs in _table)
+_RECENT_TABLES = collections.deque(maxlen=8)                   # the last pinned tables: each stays alive until its upload ran
 
 
-def _mix_table(rows, mixup, device):
-    """rows [n, k] (int32 or int64, host) -> pinned [n, k + 2] table of the `_mix` entries: the rows, then MixUp's partner and the bit
-    pattern of its fp32 lam, both from mixup.draw(n) - called HERE, after the caller drew every row's geometry.  The kernels index the
-    table with partner unchecked, so it is checked here."""
-    n = rows.shape[0]
-    partner, lam = mixup.draw(n)
-    assert partner.shape == (n,) and lam.shape == (n,) and lam.dtype == torch.float32
-    assert n > 0 and 0 <= int(partner.min()) and int(partner.max()) < n, "MixUp partner outside the batch"
-    tab = torch.empty((n, rows.shape[1] + 2), dtype=rows.dtype, pin_memory=torch.device(device).type == "cuda")
-    tab[:, :-2] = rows
-    tab[:, -2] = partner
-    tab[:, -1] = lam.contiguous().view(torch.int32)                # (a lam is positive: the int32 is the bit pattern in an int64 row too)
+def _mix_table(rows, mixup, device, dtype=None):
+    """The host table of ONE feed launch - every caller's: rows [n, k] (a list of int tuples, or a host tensor) as `dtype` (default: the
+    tensor's own, int32 or int64), in pinned memory when `device` is a GPU, kept alive here until the non-blocking upload ran.  With a
+    mixup the table is [n, k + 2], the table of the `_mix` entries: the rows, then MixUp's partner and the bit pattern of its fp32 lam,
+    both from mixup.draw(n) - called HERE, after the caller drew every row's geometry.  The kernels index the table with partner
+    unchecked, so it is checked here."""
+    rows = torch.as_tensor(rows, dtype=dtype)
+    pin = torch.device(device).type == "cuda"
+    if mixup is None:
+        tab = rows.pin_memory() if pin else rows
+    else:
+        n = rows.shape[0]
+        partner, lam = mixup.draw(n)
+        assert partner.shape == (n,) and lam.shape == (n,) and lam.dtype == torch.float32
+        assert n > 0 and 0 <= int(partner.min()) and int(partner.max()) < n, "MixUp partner outside the batch"
+        tab = torch.empty((n, rows.shape[1] + 2), dtype=rows.dtype, pin_memory=pin)
+        tab[:, :-2] = rows
+        tab[:, -2] = partner
+        tab[:, -1] = lam.contiguous().view(torch.int32)            # (a lam is positive: the int32 is the bit pattern in an int64 row too)
+    _RECENT_TABLES.append(tab)
     return tab
 
 
@@ -160,15 +168,12 @@ def gather_pair(tgt_all, inp_all, sel, mixup=None):
     assert not sel.is_cuda, "gather_pair: sel is a host tensor (it goes into the pinned table)"
     n, N = sel.numel(), tgt_all.shape[0]
     assert n > 0 and 0 <= int(sel.min()) and int(sel.max()) < N, "gather_pair: item id outside the resident tensors"
-    if mixup is not None:
-        tab = _mix_table(sel.view(n, 1), mixup, tgt_all.device)
-    else:
-        tab = torch.zeros((n, 3), dtype=torch.int64, pin_memory=True)
-        tab[:, 0] = sel
-    tab_d = tab.to(tgt_all.device, non_blocking=True)
+    rows = sel.view(n, 1)
+    if mixup is None:
+        rows = torch.nn.functional.pad(rows, (0, 2))                # (the entry reads rows of three words with mix == 0 too)
+    tab_d = _mix_table(rows, mixup, tgt_all.device).to(tgt_all.device, non_blocking=True)
     target = torch.empty((n,) + tuple(tgt_all.shape[1:]), device=tgt_all.device, dtype=torch.float32)
     input_ = torch.empty_like(target)
-    _RECENT_TABLES.append(tab)                                      # keep the pinned buffer alive until the copy ran
     _lib.call("dhz_gather_mix_pair", _p(tgt_all), _p(inp_all), tab_d.data_ptr(), _p(target), _p(input_), n, tgt_all[0].numel(),
               int(mixup is not None), _stream())
     return target, input_
@@ -220,45 +225,22 @@ class PatchStoreHBM:
         frames come out with black corners and cut-off ends; that artefact is deliberately not restated here."""
         from dehaze_hip import _lib
         from dehaze_hip.ops import _p, _stream
-        rect = not isinstance(ps, int)
-        if rect:
-            h, w = (self.H, self.W) if ps is None else (int(ps[0]), int(ps[1]))
-            if not (0 < h <= self.H and 0 < w <= self.W):
-                raise ValueError(f"PatchStoreHBM.batch: a {h} x {w} crop does not fit the stored {self.H} x {self.W} images")
+        square = isinstance(ps, int)
+        h, w = (ps, ps) if square else (self.H, self.W) if ps is None else (int(ps[0]), int(ps[1]))
+        if not (0 < h <= self.H and 0 < w <= self.W):
+            raise ValueError(f"PatchStoreHBM.batch: a {h} x {w} crop does not fit the stored {self.H} x {self.W} images")
         idx = [int(i) % self.N for i in indices]
         n = len(idx)
-        if mixup is not None:
-            if not rect:
-                h = w = ps                                          # the rect entry equals the square one on h == w
-                if not (0 < ps <= self.H and ps <= self.W):
-                    raise ValueError(f"PatchStoreHBM.batch: a {ps} x {ps} crop does not fit the stored {self.H} x {self.W} images")
-            rows = [(i,) + tuple(draw_rect_aug(self.H, self.W, h, w) if rect else draw_crop_aug(self.H, self.W, ps)) for i in idx]
-            tab = _mix_table(torch.tensor(rows, dtype=torch.int32), mixup, self.device)
-            self._table = tab                                       # keep the pinned buffer alive until the copy ran
-            tab_d = tab.to(self.device, non_blocking=True)
-            clean = torch.empty((n, 3, h, w), device=self.device, dtype=torch.float32)
-            noisy = torch.empty_like(clean)
-            _lib.call("dhz_crop_augment_mix_pair_rect", self.gt.data_ptr(), self.hazy.data_ptr(), tab_d.data_ptr(), _p(clean), _p(noisy),
-                      n, self.H, self.W, h, w, _stream())
-            return clean, noisy
-        tab = torch.empty((n, 4), dtype=torch.int32)
-        if self.device.type == "cuda":
-            tab = tab.pin_memory()
-        for j, i in enumerate(idx):
-            r, c, k = draw_rect_aug(self.H, self.W, h, w) if rect else draw_crop_aug(self.H, self.W, ps)
-            tab[j, 0], tab[j, 1], tab[j, 2], tab[j, 3] = i, r, c, k
-        self._table = tab                                       # keep the pinned buffer alive until the copy ran
-        tab_d = tab.to(self.device, non_blocking=True)
-        if rect:
-            clean = torch.empty((n, 3, h, w), device=self.device, dtype=torch.float32)
-            noisy = torch.empty_like(clean)
-            _lib.call("dhz_crop_augment_pair_rect", self.gt.data_ptr(), self.hazy.data_ptr(), tab_d.data_ptr(), _p(clean), _p(noisy),
-                      n, self.H, self.W, h, w, _stream())
-            return clean, noisy
-        clean = torch.empty((n, 3, ps, ps), device=self.device, dtype=torch.float32)
+        rows = [(i,) + draw_rect_aug(self.H, self.W, h, w) for i in idx]         # (h == w: draw_crop_aug's draws)
+        self._table = _mix_table(rows, mixup, self.device, torch.int32)
+        tab_d = self._table.to(self.device, non_blocking=True)
+        clean = torch.empty((n, 3, h, w), device=self.device, dtype=torch.float32)
         noisy = torch.empty_like(clean)
-        _lib.call("dhz_crop_augment_pair", self.gt.data_ptr(), self.hazy.data_ptr(), tab_d.data_ptr(), _p(clean), _p(noisy),
-                  n, self.H, self.W, ps, _stream())
+        if mixup is not None:                                   # (the rect entry equals the square one on h == w)
+            entry, sizes = "dhz_crop_augment_mix_pair_rect", (h, w)
+        else:
+            entry, sizes = ("dhz_crop_augment_pair", (ps,)) if square else ("dhz_crop_augment_pair_rect", (h, w))
+        _lib.call(entry, self.gt.data_ptr(), self.hazy.data_ptr(), tab_d.data_ptr(), _p(clean), _p(noisy), n, self.H, self.W, *sizes, _stream())
         return clean, noisy
 
 
@@ -436,14 +418,9 @@ class ImageStoreHBM:
             Wc = self.clear_hw[j][1]
             rows.append((self.hazy_off[i] + r * W + c, W, self.clear_off[j] + (top + r) * Wc + left + c, Wc, k))
             draws.append((i, r, c, k))
-        tab = torch.tensor(rows, dtype=torch.int64)
-        if mixup is not None:
-            tab = _mix_table(tab, mixup, self.device)               # (after every item's geometry: the order of batch + MixUp_AUG.aug)
-        elif self.device.type == "cuda":
-            tab = tab.pin_memory()
-        self._table = tab                                       # keep the pinned buffer alive until the copy ran
+        self._table = _mix_table(rows, mixup, self.device, torch.int64)     # (after every item's geometry: the order of batch + MixUp_AUG.aug)
         self._draws = torch.tensor(draws, dtype=torch.int32)    # (id, r, c, k) per item: PatchStoreHBM's table
-        tab_d = tab.to(self.device, non_blocking=True)
+        tab_d = self._table.to(self.device, non_blocking=True)
         norm = None
         if normalize is not None:
             mean, std = normalize

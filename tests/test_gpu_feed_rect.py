@@ -97,6 +97,39 @@ def test_square_request_through_the_rect_entry_equals_the_square_entry():
     assert torch.equal(c0.view(torch.int32), c1.view(torch.int32)) and torch.equal(n0.view(torch.int32), n1.view(torch.int32))
 
 
+@pytest.mark.parametrize("ps", [17, 16, 3])
+def test_the_square_entry_itself_on_full_and_partial_blocks(ps):
+    """dhz_crop_augment_pair called directly on a 20 x 23 store of 3 images, one block of 256 pixels per item at a time: ps = 17 is 289
+    pixels, two blocks with a tail of 33; 16 exactly one full block; 3 one partial block.  n = 9: every k of 0 .. 7 and several (r, c).
+    Bit for bit the numpy restatement, and bit for bit dhz_crop_augment_pair_rect on the same table."""
+    import dataset
+    from dehaze_hip import _lib
+    Hs, Ws, n = 20, 23, 9
+    g = torch.Generator().manual_seed(33)
+    gt = torch.randint(0, 256, (3, Hs, Ws, 3), generator=g, dtype=torch.uint8)
+    hazy = torch.randint(0, 256, (3, Hs, Ws, 3), generator=g, dtype=torch.uint8)
+    store = dataset.PatchStoreHBM(gt, hazy, "cuda")
+    table = [(t % 3, (2 * t) % (Hs - ps + 1), (5 * t) % (Ws - ps + 1), t % 8) for t in range(n)]
+    assert {k for *_, k in table} == set(range(8)) and len({(r, c) for _, r, c, _ in table}) >= 2
+    tab = torch.tensor(table, dtype=torch.int32).cuda()
+    m = n * 3 * ps * ps
+    outs = {}
+    for entry, sizes in (("dhz_crop_augment_pair", (ps,)), ("dhz_crop_augment_pair_rect", (ps, ps))):
+        clean = torch.full((m + 64,), float("nan"), device="cuda")
+        noisy = torch.full((m + 64,), float("nan"), device="cuda")
+        _lib.call(entry, store.gt.data_ptr(), store.hazy.data_ptr(), tab.data_ptr(), clean.data_ptr(), noisy.data_ptr(), n, Hs, Ws, *sizes,
+                  torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        assert torch.isnan(clean[m:]).all() and torch.isnan(noisy[m:]).all(), "written past the end"
+        outs[entry] = (clean[:m].cpu().view(n, 3, ps, ps), noisy[:m].cpu().view(n, 3, ps, ps))
+    clean, noisy = outs["dhz_crop_augment_pair"]
+    for j, (i, r, c, k) in enumerate(table):
+        assert np.array_equal(clean[j].numpy(), restate(gt[i].numpy(), r, c, k, ps, ps)), (j, k)
+        assert np.array_equal(noisy[j].numpy(), restate(hazy[i].numpy(), r, c, k, ps, ps)), (j, k)
+    rect_clean, rect_noisy = outs["dhz_crop_augment_pair_rect"]
+    assert torch.equal(clean.view(torch.int32), rect_clean.view(torch.int32)) and torch.equal(noisy.view(torch.int32), rect_noisy.view(torch.int32))
+
+
 def test_a_crop_larger_than_the_store_is_refused():
     from dehaze_hip import _lib
     store, _, _ = make_store()

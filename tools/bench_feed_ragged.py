@@ -2,9 +2,9 @@
 """The feed for pools of images of any sizes (dhz_crop_augment_pair_ragged) next to the feed it generalises (dhz_crop_augment_pair_rect) on
 IDENTICAL uniform data: the same uint8 images, the same (id, r, c, k) per item, outputs compared bit for bit before anything is timed.
   32 crops of 128 x 128 from 256 x 256 patches      4 whole 460 x 620 frames      1 whole 1200 x 1600 frame
-Per shape --rounds alternated passes of  rect | ragged | ragged + norm ; in a pass every launch is timed by its own pair of device events
-after --warmup launches, and the pass reports the median launch and the mean over the whole window (first event to last).  Output bytes /
-time counts the two float32 outputs.  The rect entry's spread from pass to pass is the yardstick: the ragged entry is "no slower" when its
+Per shape --rounds alternated passes of  rect | ragged | ragged + norm  (and, where the crop is square,  square : dhz_crop_augment_pair on
+the rect entry's table); in a pass every launch is timed by its own pair of device events after --warmup launches, and the pass reports
+the median launch and the mean over the whole window (first event to last).  Output bytes / time counts the two float32 outputs.  The rect entry's spread from pass to pass is the yardstick: the ragged entry is "no slower" when its
 median pass lies within the rect passes' range.
 Then the step of FFA_main.py (ffa_train_step, FFA(3, --blocks), 4 x 240 x 240 crops of 256 x 256 patches, L1 only), batch drawn and fed
 from PatchStoreHBM and from ImageStoreHBM in alternated passes.  Writes profiles/feed_ragged.txt.
@@ -83,6 +83,9 @@ def feed_shape(label, N, H, W, n, crop, a, say):
         "ragged + norm": lambda: _lib.call("dhz_crop_augment_pair_ragged", new.gt_pool.data_ptr(), new.hazy_pool.data_ptr(), tab_new.data_ptr(),
                                            c1.data_ptr(), n1.data_ptr(), norm, n, h, w, stream),
     }
+    if h == w:                                               # the square entry reads the rect entry's table
+        routes["square"] = lambda: _lib.call("dhz_crop_augment_pair", old.gt.data_ptr(), old.hazy.data_ptr(), tab_old.data_ptr(), c0.data_ptr(),
+                                             n0.data_ptr(), n, H, W, h, stream)
     times = {name: [] for name in routes}
     for _ in range(a.rounds):                                # alternated: a drift of the machine hits all routes alike
         for name, fn in routes.items():
@@ -99,7 +102,7 @@ def feed_shape(label, N, H, W, n, crop, a, say):
     for k, what in ((0, "median launch"), (1, "window mean")):
         rect = [t[k] for t in times["rect"]]
         lo, hi = min(rect), max(rect)
-        for name in ("ragged", "ragged + norm"):
+        for name in [r for r in routes if r != "rect"]:
             m = median([t[k] for t in times[name]])
             verdicts.append(f"  {label}, {what}: rect passes {1e3 * lo:.1f} .. {1e3 * hi:.1f} us (spread {100 * (hi - lo) / lo:.1f} %), {name} median "
                             f"pass {1e3 * m:.1f} us -> " + ("faster than every rect pass" if m < lo else "within the rect spread" if m <= hi else "SLOWER"))
