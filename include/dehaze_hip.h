@@ -1079,6 +1079,28 @@ size_t dhz_fourier_diag_workspace_bytes(int B, int C, int n, int layout);
 int dhz_fourier_diag(double* A, double* V, double* sumA, double* sumV, const void* x, int B, int C, int n, int layout, int dtype, void* ws,
                      size_t ws_bytes, void* stream);
 
+/* K18  Frequency-band noise (csrc/freq_noise.hip): the reference's FreqAttack._fourier_mask (ops/adversarial.py: fft2 -> shift -> mask ->
+ *      unshift -> ifft2 -> real part) without a 2-D transform.  A width w (even, 0 <= w <= n) keeps the frequencies
+ *      B(w) = {-w/2 .. w/2 - 1} on each axis; the band is B(w1) x B(w1) minus B(w2) x B(w2).  With
+ *        c_w[t] = (1/n) sum_{k in B(w)} cos(2 pi k t / n),   s_w[t] = (1/n) sum_{k in B(w)} sin(2 pi k t / n),
+ *      C_w[a][b] = c_w[(a - b) mod n] and S_w likewise, per n x n plane
+ *        band(d)  = (C_w1 d C_w1^T - S_w1 d S_w1^T) - (C_w2 d C_w2^T - S_w2 d S_w2^T),
+ *        d        = delta (take_sign 0) or sign(delta) with sign(+-0) = 0 (take_sign 1),
+ *        noise    = scale * band(d)              doubles, WRITTEN where the pointer is non-null,
+ *        out      = (float)((double)x + noise)   one rounding.
+ *      x, delta, out: [M, n, n] fp32, contiguous, M planes (B C; any channel count).  out must not overlap x or delta.  n even,
+ *      2 <= n <= 512; 1 <= M <= 65535; M n n < 2^31.  w1 = w2 (0, 0 included): out = x bit for bit, noise = +0.0, no band work.
+ *      All arithmetic is double; the twiddles come from the index (k t) mod n reduced in integers (csrc/twiddle.h); sums run over k, then b,
+ *      then (vector, a) in ascending order; no atomics; every cut (64 x 64 tiles, runs of 32) is a function of the shapes: the same bits
+ *      from run to run, under any dhz_set_reserved_cus, with the deterministic mode on or off (the mode's workspace is not used).
+ *      ws: dhz_band_noise_workspace_bytes(M, n) bytes (the four vectors and the four row products d C^T, d S^T per width; 0 for an
+ *      unsupported shape), 8-byte aligned like noise.  An odd n, n, M or M n n out of range, an odd width or one outside [0, n], w2 > w1,
+ *      a take_sign outside {0, 1}, a null out, x or delta, an out that overlaps x or delta, a missing, too small (the message names the
+ *      bytes needed) or misaligned workspace: DHZ_EINVAL before any launch. */
+size_t dhz_band_noise_workspace_bytes(int M, int n);
+int dhz_band_noise(float* out, double* noise, const float* x, const float* delta, int M, int n, int w1, int w2, double scale, int take_sign,
+                   void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "twiddle.h"
 
 namespace {
 
@@ -194,21 +195,6 @@ __global__ __launch_bounds__(256) void fourier_partial_nchw_kernel(const T* __re
     }
 }
 
-// (cos, sin)(2 pi j / n), 0 <= j < n, from an argument in [0, pi / 4]: quadrant q = floor(4 j / n) and remainder r = 4 j - q n in
-// integers, the remainder folded to 2 r <= n by swapping sine and cosine, then the quadrant's rotation
-__device__ __forceinline__ double2 twiddle(int j, int n) {
-    const int q = (4 * j) / n;
-    int r = 4 * j - q * n;
-    const bool fold = 2 * r > n;
-    if (fold) r = n - r;
-    const double a = (double)r / (double)(2 * n);
-    const double sa = sinpi(a), ca = cospi(a);
-    const double s0 = fold ? ca : sa, c0 = fold ? sa : ca;
-    const double c = q == 0 ? c0 : q == 1 ? -s0 : q == 2 ? -c0 : s0;
-    const double s = q == 0 ? s0 : q == 1 ? c0 : q == 2 ? -s0 : -c0;
-    return make_double2(c, s);
-}
-
 // grid (ceil(C / FT), B); LDS: g [n][FT] doubles, then the twiddles [n][2]
 template <int LAYOUT>
 __global__ __launch_bounds__(256) void fourier_finish_kernel(const double* __restrict__ wg, const double* __restrict__ wv, double* __restrict__ A,
@@ -235,7 +221,7 @@ __global__ __launch_bounds__(256) void fourier_finish_kernel(const double* __res
         gl[s * FT + cl] = acc;
     }
     for (int j = tid; j < n; j += 256) {
-        const double2 t = twiddle(j, n);
+        const double2 t = dhz_twiddle(j, n);
         tw[2 * j] = t.x;
         tw[2 * j + 1] = t.y;
     }
